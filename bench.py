@@ -22,6 +22,13 @@ native tar walk + Required + CR strip / printable extraction into double-
 buffered pinned arenas, H2D, kernels, exact tail -- the batching/arena packing
 path; value counts the input bytes of the files analyzed).
 
+A plain run (`--gpus 1 --steps N --warmup W`) does what the headline figure needs and
+no more: set up, warm up, time the N steps, print the line.  --full adds the legs that
+take runs of their own, after the timed steps: the ingest-inclusive leg (c2) and the
+pinned H2D peak it is compared with, the oracle parity sample, the CPU baseline and
+the every-file diff against it (a mismatch exits non-zero).  --dump-outputs DIR writes
+what the last timed step returned to its caller as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -501,6 +508,39 @@ def _bind_numa(device):
         return None
 
 
+DUMP_MAX_ROWS = 1000000  # --dump-outputs: findings rows kept (6 float64 each; C2's 20 GB holds ~62,000)
+
+
+def dump_outputs(dirname, rank, world, result, last_stats):
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files (every
+    value an integer below 2^53, so exact).  Resident / ingest workloads: `findings`, one row per
+    finding of the step's ScanResult in the order the caller receives them (tsg_result_records:
+    file then finding order) -- file index, rule index, StartLine, EndLine, and the 64-bit digest
+    of the finding's Match and Code lines as its high and low 32 bits (`findings_count`: the
+    number of findings; past DUMP_MAX_ROWS the rows are a fixed, seeded sample).  Analyzer
+    workloads (c4, c1fs; the timed walks return counts, not objects): `analysis_counts` -- files
+    analyzed, their input bytes, findings.  N > 1: one file per rank (`<name>_rank<k>`)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    if result is not None:
+        rec = result.records()
+        np.save(os.path.join(dirname, "findings_count%s.npy" % sfx), np.array([len(rec)], dtype=np.float64))
+        if len(rec) > DUMP_MAX_ROWS:  # a fixed, seeded sample of the rows, in order (48 MB)
+            keep = np.random.default_rng(0x5EC2E7).choice(len(rec), DUMP_MAX_ROWS, replace=False)
+            rec = rec[np.sort(keep)]
+        out = np.empty((len(rec), 6), dtype=np.float64)
+        for k, name in enumerate(("file", "rule", "start_line", "end_line")):
+            out[:, k] = rec[name]
+        out[:, 4] = rec["digest"] >> np.uint64(32)
+        out[:, 5] = rec["digest"] & np.uint64(0xFFFFFFFF)
+        np.save(os.path.join(dirname, "findings%s.npy" % sfx), out)
+    else:
+        out = np.array([last_stats["added"], last_stats["input_bytes"], last_stats["scan_findings"]],
+                       dtype=np.float64)
+        np.save(os.path.join(dirname, "analysis_counts%s.npy" % sfx), out)
+
+
 def _launch_ranks(argv, n):
     """--gpus N (N > 1) without a torchrun environment: start the N rank processes of this same
     command through torch.distributed.run (one rank per GPU, LOCAL_RANK = device) and return
@@ -579,7 +619,15 @@ def main():
     ap.add_argument("--gb", type=float, default=None, help="corpus size per GPU (GB = 1e9 B)")
     ap.add_argument("--cpu-sample-mb", type=float, default=None, help="CPU-baseline sample (first files)")
     ap.add_argument("--parity-mb", type=float, default=None, help="oracle parity sample (first files)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs that take runs of their own: the ingest-inclusive "
+                         "leg (c2) and the pinned H2D peak, the oracle parity sample, the CPU baseline and the "
+                         "every-file diff against it (exit non-zero on a mismatch).  Off: the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned to its caller as "
+                         "DIR/<name>.npy (float64; the same arguments give the same inputs, so two builds compare "
+                         "output for output): see dump_outputs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the parity sample and CPU baseline")
     ap.add_argument("--depth", type=int, default=None,
                     help="scans in flight (pipelined submission); default 4, c3f 8 (its exact host pass is the "
                          "bound: 773 / 755 / 670 GB/s at depth 8 / 6 / 4, profiles/r06/c3f/depth/)")
@@ -591,7 +639,7 @@ def main():
     ap.add_argument("--ingest", action="store_true",
                     help="c2/c3: host-resident corpus (page-locked), H2D inside the timed region")
     ap.add_argument("--ingest-steps", type=int, default=3,
-                    help="c2 resident runs: steps of the extra ingest-inclusive leg (0: skip)")
+                    help="c2 resident runs with --full: steps of the extra ingest-inclusive leg (0: skip)")
     ap.add_argument("--arena-mb", type=int, default=256, help="c4: collector arena size")
     ap.add_argument("--layers", type=int, default=1,
                     help="c4: the step's bytes as an image of this many layers (sizes 34/26/20/12/8 %% ... of "
@@ -704,9 +752,9 @@ def main():
         R = corpus.generate(int(args.gb * 1e9), seed=corpus.SEED + rank, crlf_share=args.crlf)
         C = R.stripped() if args.crlf > 0 else R
         r_crlf, r_bytes = int(R.crlf.sum()), int(R.n_bytes)
-        # R feeds only the ingest leg (single-process C2 runs): otherwise free it -- under torchrun
-        # each rank would hold its corpus twice (2 x 20 GB of host memory per GPU)
-        if args.crlf <= 0 or world > 1 or args.ingest or args.ingest_steps <= 0:
+        # R feeds only the ingest leg (single-process C2 runs with --full): otherwise free it -- under
+        # torchrun each rank would hold its corpus twice (2 x 20 GB of host memory per GPU)
+        if args.crlf <= 0 or world > 1 or args.ingest or args.ingest_steps <= 0 or not args.full:
             R = None
     t_gen = time.time() - t_gen
     kinds_raw = np.ones(R.n_files, dtype=np.uint8) if R is not None else None  # every text file: CR strip
@@ -721,7 +769,7 @@ def main():
             # host-resident corpus in a page-locked pool (the caller's pinned arena pool): every
             # step streams it through the engine's staging ring (RunHost)
             unregister = secret.HostRegister(C.arena)
-            h2d_peak = measure_h2d(dev)
+            h2d_peak = measure_h2d(dev) if args.full else None  # (a run of its own: 4 GB, four times)
             d_arena = d_offs = d_paths = d_poffs = None
         else:
             d_arena = torch.from_numpy(C.arena).to(dev)
@@ -860,8 +908,11 @@ def main():
     ingest = None
     unregister_leg = None
     res_timed = last_res[0]  # the timed steps' last result (parity below)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, res_timed, last)
     # (single-process runs only: under torchrun every rank would page-lock its whole corpus)
-    if layer is None and args.workload == "c2" and not args.ingest and args.ingest_steps > 0 and world == 1:
+    if args.full and layer is None and args.workload == "c2" and not args.ingest and args.ingest_steps > 0 \
+            and world == 1:
         del d_arena, d_offs
         torch.cuda.empty_cache()
         unregister_leg = secret.HostRegister(C.arena if R is None else R.arena)
@@ -1003,7 +1054,7 @@ def main():
     if rank == 0:
         cpu = None
         parity = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cores = min(16, os.cpu_count() or 1)
             if layer is None:
                 want, _ = oracle_sample(C, int(args.parity_mb * 1e6), cores, tmpdir, cfg_path)
@@ -1052,7 +1103,9 @@ def main():
             "cpu_baseline": cpu,
             "parity": parity,
             "gather": gathered,
-            "legs": ("N=1: resident steps, ingest leg (c2), oracle parity sample, CPU baseline" if world == 1 else
+            "legs": ("the timed steps only (--full adds the ingest leg (c2), the oracle parity sample and the CPU "
+                     "baseline)" if not args.full else
+                     "N=1: resident steps, ingest leg (c2), oracle parity sample, CPU baseline" if world == 1 else
                      "N>1: resident steps and the rank-0 findings gather only; the ingest leg, the parity sample "
                      "and the CPU baseline run at N=1 (every rank would page-lock its corpus / rerun the CPU "
                      "reference)"),
@@ -1077,7 +1130,7 @@ def main():
         shutil.rmtree(layer, ignore_errors=True)
     if cfg_path:
         os.remove(cfg_path)
-    if h2d_peak:
+    if args.ingest and layer is None:
         unregister()
     if unregister_leg is not None:
         unregister_leg()

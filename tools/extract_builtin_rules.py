@@ -113,6 +113,14 @@ def extract(ref_root: str) -> dict:
 
 
 DST = Path(__file__).resolve().parent.parent / "trivy_amd/secret/builtin_rules.json"
+PIN = Path(__file__).resolve().parent.parent / "tests/golden/builtin_rules.sha256.json"
+
+
+def digest(data: dict) -> str:
+    """SHA-256 of the rule data in a canonical JSON form (sorted keys, ASCII, no spaces)."""
+    import hashlib
+    text = json.dumps(data, sort_keys=True, ensure_ascii=True, separators=(",", ":"))
+    return hashlib.sha256(text.encode("ascii")).hexdigest()
 
 
 def main(ref_root: str) -> None:
@@ -120,6 +128,11 @@ def main(ref_root: str) -> None:
     rules, allow, dst = out["rules"], out["allow_rules"], DST
     dst.write_text(json.dumps(out, indent=1, ensure_ascii=False) + "\n")
     print("wrote %d rules, %d allow rules -> %s" % (len(rules), len(allow), dst))
+    # the extraction's digest, taken from the reference and not from the file written above:
+    # tests/test_rules_data.py pins builtin_rules.json to it where the reference tree is absent
+    PIN.write_text(json.dumps({"source": out["source"], "rules": len(rules), "allow_rules": len(allow),
+                               "sha256": digest(out)}, indent=1) + "\n")
+    print("wrote %s" % PIN)
 
 
 if __name__ == "__main__":

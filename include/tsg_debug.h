@@ -101,6 +101,16 @@ int tsg_debug_scanner_engine(struct tsg_scanner* s, uint64_t out[4]);
  * previous mode, -1 for a scanner without a GPU engine.  (A/B and parity tests.) */
 int tsg_debug_scanner_gpu_findings(struct tsg_scanner* s, int mode);
 
+/* Device-only batches (tsg_batch.host_arena NULL): the size of the device staging
+ * buffer the candidate files are packed into (a round carries at most this much)
+ * and the length from which a file is copied straight from the arena instead
+ * (defaults: TSG_FETCH_STAGE_MB, 256, and TSG_FETCH_DIRECT_MB, 8, read at scanner
+ * creation).  stage_bytes is rounded down to the packing granule (16 KiB, at
+ * least one); both take effect with the next scan.  Returns -1 for a scanner
+ * without a GPU engine.  (Tests reach several rounds and the direct route on
+ * kilobyte inputs with it.) */
+int tsg_debug_scanner_fetch(struct tsg_scanner* s, uint64_t stage_bytes, uint64_t direct_bytes);
+
 /* Thread-local text of the last error. */
 const char* tsg_last_error(void);
 

@@ -82,20 +82,40 @@ void tsg_scanner_free(tsg_scanner* s);
 /* 1 if path is globally allowed (Global.AllowPath), else 0. */
 int tsg_scanner_allow_path(const tsg_scanner* s, const char* path, uint64_t len);
 
+/* A batch of files, back to back in one arena.  Where the bytes are:
+ *   host_arena only             a host-resident batch, streamed to the GPU;
+ *   host_arena + dev_arena      a mirrored batch: the GPU scans dev_arena, the exact
+ *                               host pass reads host_arena (the same bytes);
+ *   dev_arena only              a device-only batch (host_arena NULL): no host copy
+ *                               of the bytes exists.  The GPU scans dev_arena and the
+ *                               files that got candidates -- only those, whole -- are
+ *                               copied back to pinned host memory for the exact pass
+ *                               (tsg_result_fetch_stats says how much);
+ *   gather_base (tsg_batch_ext) host_arena NULL, the files in mapped host memory.
+ * host_arena NULL with neither dev_arena nor gather_base is an argument error
+ * (status <0 before any GPU work), as is gather_base together with dev_arena.
+ * host_offsets is always required: it is small, and the host needs the sizes.
+ * dev_arena, in every mode: 16-B aligned, with 64 readable bytes past its end
+ * (host_offsets[n_files]); the library never pads it by copying. */
 typedef struct tsg_batch {
   uint32_t n_files;
-  const uint8_t* host_arena;     /* concatenated contents, required (exact pass) */
-  const uint64_t* host_offsets;  /* n_files + 1 */
-  const void* dev_arena;         /* optional: same bytes already in HBM (16-B aligned, 64 readable
-                                    bytes past the end) */
-  const void* dev_offsets;       /* optional: device copy of host_offsets */
+  const uint8_t* host_arena;     /* concatenated contents; NULL: a device-only batch (dev_arena set)
+                                    or a gathered one */
+  const uint64_t* host_offsets;  /* n_files + 1, required */
+  const void* dev_arena;         /* optional: the batch's bytes in HBM -- the same bytes as host_arena
+                                    where that is given, the only copy where it is NULL (16-B aligned,
+                                    64 readable bytes past the end) */
+  const void* dev_offsets;       /* optional: device copy of host_offsets (without it the library
+                                    uploads one for the scan) */
   const char* const* paths;      /* ScanArgs.FilePath per file */
   const uint64_t* path_lens;     /* optional */
   const uint8_t* binary;         /* optional ScanArgs.Binary per file */
-  /* optional, per file: the analyzer's pre-scan transform, run on the GPU
-   * (then host_arena / host_offsets hold the bytes as read, and dev_arena
-   * must be NULL): 0 as is, 1 every '\r' removed (secret.go:121), 2
-   * utils.ExtractPrintableBytes (.pyc, secret.go:112-117, utils.go:128-160) */
+  /* optional, per file: the analyzer's pre-scan transform, run on the GPU:
+   * 0 as is, 1 every '\r' removed (secret.go:121), 2
+   * utils.ExtractPrintableBytes (.pyc, secret.go:112-117, utils.go:128-160).
+   * host_arena / host_offsets then hold the bytes as read.  With dev_arena
+   * the bytes as read are resident: dev_arena holds them, host_offsets lays
+   * them out as read, and host_arena is NULL or holds the same bytes. */
   const uint8_t* transform;
   /* optional: the FilePath bytes packed in HBM (dev_path_offsets: n_files + 1
    * u64, device) -- the global allow-path rules (scanner.go:381-386) are then
@@ -208,6 +228,24 @@ typedef struct tsg_stats {
   double ms_xform_kernel;    /* GPU pre-transform (batch.transform; part of ms_gpu_total) */
 } tsg_stats;
 int tsg_result_stats(const tsg_result* r, tsg_stats* out);
+
+/* What a device-only batch's scan brought back from HBM for the exact pass
+ * (versioned like tsg_batch_ext: the caller sets struct_size, an unknown size
+ * is refused; tsg_stats is unversioned and does not grow).  files / bytes: the
+ * files that got candidates and their lengths, summed; direct_files: those of
+ * them copied straight from the arena, one copy each (files of
+ * TSG_FETCH_DIRECT_MB or more, default 8 MiB), the others being packed on the
+ * GPU into a staging buffer (TSG_FETCH_STAGE_MB, default 256 MiB) and copied
+ * in `rounds` rounds; ms_fetch: the fetch's GPU work and copies.  All zero for
+ * a batch with a host arena. */
+typedef struct tsg_fetch_stats {
+  uint32_t struct_size;
+  uint32_t rounds;
+  uint64_t files, bytes, direct_files;
+  double ms_fetch;
+} tsg_fetch_stats;
+#define TSG_FETCH_STATS_SIZE_V1 ((uint32_t)(offsetof(tsg_fetch_stats, ms_fetch) + sizeof(double)))
+int tsg_result_fetch_stats(const tsg_result* r, tsg_fetch_stats* out);
 
 /* Page-lock a caller's host buffer (hipHostRegister) so batches in it stream
  * to the GPU asynchronously (the engine's staging ring: copies of this and of

@@ -1,0 +1,126 @@
+"""Mirrored vs device-only scans of an HBM-resident C2-generator corpus (measured, not gated).
+
+The corpus (trivy_amd.corpus.generate, CR-stripped, a few GB) is resident in HBM.  After a warm-up,
+blocks of `--block` mirrored scans (host arena + device arena: the exact pass reads the host
+copy) alternate with blocks of device-only scans (host_arena NULL: the candidate files are
+fetched from HBM), `--steps` scans of each in all, in one process on one scanner, pipelined
+`--depth` deep as bench.py's C2 steps are.  Printed, and written as one JSON line:
+
+  ms per step of both modes (wall time of a block / its scans),
+  the fetched files and bytes per step, ms_fetch (plan + pack + copies, HIP events),
+  the rounds and direct files,
+  overlap_ms: how much of the fetch ran beside other work of the pipeline --
+      ms_gpu_total + ms_fetch - the device-only ms per step, clamped to [0, ms_fetch]
+      (0: every fetch extended its step by its whole length; ms_fetch: it was hidden).
+
+Usage: python tools/device_only_bench.py [--gb 4] [--steps 20] [--warmup 5] [--depth 3] [--out FILE]
+"""
+import argparse
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gb", type=float, default=4.0)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--block", type=int, default=5, help="scans of one mode before the other takes its turn")
+    ap.add_argument("--depth", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+
+    import torch
+    import trivy_amd.secret as secret
+    from trivy_amd import corpus
+
+    R = corpus.generate(int(args.gb * 1e9), seed=corpus.SEED, crlf_share=0.05)
+    C = R.stripped()
+    del R
+    dev = torch.device("cuda", 0)
+    d_arena = torch.from_numpy(C.arena).to(dev)  # (the generator's arena carries the 64 bytes of slack)
+    d_offs = torch.from_numpy(C.offsets.view(np.int64)).to(dev)
+    torch.cuda.synchronize()
+    sc = secret.NewScanner(None, device=0, calibration=C.arena[:min(C.n_bytes, 16_000_000)])
+
+    def submit(device_only):
+        if device_only:
+            return sc.scan_device_async(d_arena, C.offsets, C.path_ptrs, dev_offsets=d_offs)
+        return sc.scan_arena_async(C.arena, C.offsets, C.path_ptrs, dev_arena=d_arena.data_ptr(),
+                                   dev_offsets=d_offs.data_ptr())
+
+    def block(device_only, n):
+        """n pipelined scans of one mode: (seconds, their results' stats, fetch stats)."""
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        inflight, st, fs = [], [], []
+        for _ in range(n):
+            inflight.append(submit(device_only))
+            if len(inflight) >= args.depth:
+                r = inflight.pop(0).wait()
+                st.append(r.stats())
+                fs.append(r.fetch_stats())
+        while inflight:
+            r = inflight.pop(0).wait()
+            st.append(r.stats())
+            fs.append(r.fetch_stats())
+        return time.perf_counter() - t0, st, fs
+
+    for mode in (False, True):
+        block(mode, args.warmup)
+    per = {False: [], True: []}
+    stats = {False: [], True: []}
+    fetch = []
+    done = 0
+    while done < args.steps:
+        n = min(args.block, args.steps - done)
+        for mode in (False, True):
+            s, st, fs = block(mode, n)
+            per[mode].append(1e3 * s / n)
+            stats[mode] += st
+            if mode:
+                fetch += fs
+        done += n
+    findings = {m: stats[m][-1]["findings"] for m in (False, True)}
+    assert findings[False] == findings[True], findings
+
+    def med(xs):
+        return float(statistics.median(xs))
+
+    ms_m, ms_d = med(per[False]), med(per[True])
+    ms_gpu = med([s["ms_gpu_total"] for s in stats[True]])
+    ms_fetch = med([f["ms_fetch"] for f in fetch])
+    out = {
+        "tool": "device_only_bench", "gb": C.n_bytes / 1e9, "files": int(C.n_files), "steps": args.steps,
+        "block": args.block, "depth": args.depth,
+        "mirrored_ms_per_step": ms_m, "device_only_ms_per_step": ms_d,
+        "mirrored_blocks_ms": per[False], "device_only_blocks_ms": per[True],
+        "mirrored_gbps": C.n_bytes / 1e6 / ms_m, "device_only_gbps": C.n_bytes / 1e6 / ms_d,
+        "ms_gpu_total": ms_gpu,
+        "mirrored_ms_gpu_total": med([s["ms_gpu_total"] for s in stats[False]]),
+        "fetch_files_per_step": med([f["files"] for f in fetch]),
+        "fetch_bytes_per_step": med([f["bytes"] for f in fetch]),
+        "fetch_rounds": med([f["rounds"] for f in fetch]),
+        "fetch_direct_files": med([f["direct_files"] for f in fetch]),
+        "ms_fetch": ms_fetch,
+        "fetch_gbps": med([f["bytes"] for f in fetch]) / 1e6 / ms_fetch if ms_fetch > 0 else 0.0,
+        "overlap_ms": max(0.0, min(ms_fetch, ms_gpu + ms_fetch - ms_d)),
+        "candidates": int(stats[True][-1]["candidates"]), "findings": int(findings[True]),
+    }
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -14,6 +14,7 @@ struct tsg_scanner {
 struct tsg_result {
   tsg::BatchResult files;
   tsg_stats stats;
+  tsg::FetchStats fetch;  // tsg_result_fetch_stats (device-only batches; zero otherwise)
   std::string json;        // tsg_result_json: every file (built once)
   std::string json_range;  // tsg_result_json_range: the last range asked for
   const tsg::SecretScanner* owner;

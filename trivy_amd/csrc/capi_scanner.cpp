@@ -286,13 +286,35 @@ ExtFields ExtOf(const tsg_batch_ext* b) {
 
 int ScanImpl(tsg_scanner* s, const tsg_batch* b, const ExtFields& x, tsg_result** out);
 
+// Argument errors of a batch, before any GPU work (and before a scanner is asked for its engine).
+bool CheckBatch(const tsg_batch* b, const ExtFields& x) {
+  if (!b) {
+    tsg::SetError("tsg_scan: NULL batch");
+    return false;
+  }
+  if (x.gather_base && (!x.gather_src || !b->transform || b->dev_arena)) {
+    tsg::SetError("tsg_scan: a gathered batch needs gather_src and transform, and no dev_arena");
+    return false;
+  }
+  if (b->n_files && !b->host_arena && !b->dev_arena && !x.gather_base) {  // (an empty batch reads no bytes)
+    tsg::SetError("tsg_scan: host_arena is NULL and the batch has no dev_arena (a device-only batch) or gather_base");
+    return false;
+  }
+  if (b->n_files && !b->host_offsets) {
+    tsg::SetError("tsg_scan: host_offsets is required (a device-only batch too: the host needs the sizes)");
+    return false;
+  }
+  return true;
+}
+
 }  // namespace
 
 int tsg_scan_submit_ext(tsg_scanner* s, const tsg_batch_ext* b, tsg_pending** out) {
   if (!CheckExtSize(b)) return -1;
-  std::unique_ptr<tsg_pending> p(new tsg_pending());
   const tsg_batch bc = b->base;
   const ExtFields x = ExtOf(b);
+  if (!CheckBatch(&bc, x)) return -1;
+  std::unique_ptr<tsg_pending> p(new tsg_pending());
   tsg_pending* pp = p.get();
   pp->th = std::thread([s, bc, x, pp] {
     pthread_setname_np(pthread_self(), "tsg-scan");
@@ -330,6 +352,7 @@ int tsg_scan_ext(tsg_scanner* s, const tsg_batch_ext* b, tsg_result** out) {
 namespace {
 
 int ScanImpl(tsg_scanner* s, const tsg_batch* b, const ExtFields& x, tsg_result** out) {
+  if (!CheckBatch(b, x)) return -1;
   tsg::BatchInput in;
   in.n_files = b->n_files;
   in.host_arena = b->host_arena;
@@ -346,16 +369,12 @@ int ScanImpl(tsg_scanner* s, const tsg_batch* b, const ExtFields& x, tsg_result*
   in.host_path_off = x.host_path_off;
   in.gather_base = x.gather_base;
   in.gather_src = x.gather_src;
-  if (in.gather_base && (!in.gather_src || !in.transform || in.dev_arena)) {
-    tsg::SetError("tsg_scan: a gathered batch needs gather_src and transform, and no dev_arena");
-    return -1;
-  }
   std::unique_ptr<tsg_result> r(new tsg_result());
   r->owner = s->s.get();
   tsg::BatchStats gs;
   tsg::HostStats hs;
   std::string err;
-  if (!s->s->Scan(in, &r->files, &gs, &hs, &err)) {
+  if (!s->s->Scan(in, &r->files, &gs, &hs, &err, &r->fetch)) {
     tsg::SetError(err);
     return -1;
   }
@@ -539,6 +558,24 @@ int tsg_result_stats(const tsg_result* r, tsg_stats* out) {
   return 0;
 }
 
+int tsg_result_fetch_stats(const tsg_result* r, tsg_fetch_stats* out) {
+  if (!r || !out) {
+    tsg::SetError("tsg_result_fetch_stats: NULL argument");
+    return -1;
+  }
+  if (out->struct_size != TSG_FETCH_STATS_SIZE_V1) {
+    tsg::SetError("tsg_result_fetch_stats: tsg_fetch_stats.struct_size " + std::to_string(out->struct_size) +
+                  " is not a size this library knows (v1 = " + std::to_string(TSG_FETCH_STATS_SIZE_V1) + ")");
+    return -1;
+  }
+  out->rounds = r->fetch.rounds;
+  out->files = r->fetch.files;
+  out->bytes = r->fetch.bytes;
+  out->direct_files = r->fetch.direct_files;
+  out->ms_fetch = r->fetch.ms_fetch;
+  return 0;
+}
+
 static void FillInfo(const tsg::CompiledRules& cr, tsg_table_info* out) {
   out->n_rules = uint32_t(cr.rules.size());
   out->n_keywords = uint32_t(cr.keywords.size());
@@ -677,6 +714,12 @@ int tsg_debug_scanner_engine(tsg_scanner* s, uint64_t out[4]) {
     out[2] = std::max<uint64_t>(out[2], m.cand_cap);
     out[3] += m.slot_bytes;
   }
+  return 0;
+}
+
+int tsg_debug_scanner_fetch(tsg_scanner* s, uint64_t stage_bytes, uint64_t direct_bytes) {
+  if (!s || !s->s || s->s->n_engines() == 0) return -1;
+  for (size_t i = 0; i < s->s->n_engines(); i++) s->s->engine_at(i)->SetFetchSizes(stage_bytes, direct_bytes);
   return 0;
 }
 

@@ -6,6 +6,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <deque>
+#include <memory>
 #include <string>
 #include <mutex>
 #include <thread>
@@ -64,6 +65,37 @@ struct TailOut {
   uint64_t xform_bytes = 0;  // transformed arena bytes of the whole batch
 };
 
+// The candidate files of a device-only batch (no host copy of the bytes),
+// brought back from HBM for the exact pass (fetch.h).  The caller sets
+// h_offsets (the batch's n_files + 1 host offsets) and passes the struct to
+// Run / Enqueue + Collect / FetchFiles; on return buf holds the fetched files:
+// file f's bytes start at buf + off[f] where fetched[f] is set (its length is
+// the batch's), off[n_files] is the bytes of buf in use.  Files below the
+// direct threshold come packed in file order, each rounded up to 16 B; the
+// others follow, copied straight from the arena.  buf is pinned memory on
+// loan from the engine: it goes back when the struct is released or destroyed
+// (before the engine is).
+class GpuEngine;
+class FetchPool;
+struct FetchOut {
+  const uint64_t* h_offsets = nullptr;
+  const uint8_t* buf = nullptr;
+  std::vector<uint64_t> off;
+  std::vector<uint8_t> fetched;
+  uint64_t files = 0, bytes = 0, direct_files = 0;
+  uint32_t rounds = 0;   // staging rounds that carried packed bytes
+  double ms_fetch = 0;   // plan + pack + copies (HIP events; direct copies by the host clock)
+  FetchOut() = default;
+  FetchOut(const FetchOut&) = delete;
+  FetchOut& operator=(const FetchOut&) = delete;
+  ~FetchOut() { Release(); }
+  void Release();
+  // the loan (GpuEngine::TakeFetchBuf / GiveFetchBuf)
+  GpuEngine* owner = nullptr;
+  void* lease = nullptr;
+  size_t lease_cap = 0;
+};
+
 struct BatchStats {
   uint64_t bytes = 0, files = 0, hits = 0, candidates = 0, special_files = 0, fullscan_tasks = 0, fold_sites = 0;
   uint64_t flagged_blocks = 0;
@@ -88,8 +120,15 @@ class GpuEngine {
   // Run the kernels over a device-resident arena.  Offsets: n_files+1 u64
   // (device); the arena must have 64 readable bytes past n_bytes.  The
   // candidates are copied back into `cands`.
+  // With fetch (a device-only batch): the candidate files' bytes are brought
+  // back too, sized exactly (the candidates are known before the fetch is issued).
   bool Run(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
-           std::vector<Candidate>* cands, BatchStats* st);
+           std::vector<Candidate>* cands, BatchStats* st, FetchOut* fetch = nullptr);
+  // The files want[f] != 0 of a device-resident arena into *out (synchronous;
+  // the caller holds the engine's lock).  For the files a GPU pre-transform of
+  // resident bytes left as they were read.
+  bool FetchFiles(const uint8_t* d_arena, const uint64_t* d_offsets, uint32_t n_files,
+                  const std::vector<uint8_t>& want, FetchOut* out);
 
   // Host-resident batch (PCIe-inclusive path): streamed in chunks through the
   // engine's staging ring (below), copies overlapping the kernels of earlier
@@ -103,6 +142,9 @@ class GpuEngine {
   // must be the only lock guarding this engine's Run / Enqueue calls.  A
   // failure's text comes back in *err (err_ is shared with the other users of
   // the engine, so it is not the channel for a call that runs beside them).
+  // d_src (optional, with kinds): the bytes as read are resident in HBM at d_src
+  // (h_arena may be NULL): each chunk is copied device to device into its
+  // staging buffer instead of from the host.
   // gather_base / gather_src (optional, with kinds): the files are not in
   // h_arena (NULL then) but at gather_base + gather_src[f] in page-locked,
   // device-mapped host memory (a registered tar layer); each chunk is gathered
@@ -111,7 +153,7 @@ class GpuEngine {
   bool RunHost(const uint8_t* h_arena, uint64_t n_bytes, const uint64_t* h_offsets, uint32_t n_files,
                std::vector<Candidate>* cands, BatchStats* st, const uint8_t* kinds, TailOut* tail,
                std::mutex* dev_mu, std::string* err, const uint8_t* gather_base = nullptr,
-               const uint64_t* gather_src = nullptr);
+               const uint64_t* gather_src = nullptr, const uint8_t* d_src = nullptr);
 
   // Split form of Run for pipelined callers: Enqueue (with the engine's lock
   // held) puts the whole GPU phase and the copies of the counters and of the
@@ -128,13 +170,31 @@ class GpuEngine {
   // above the copied part reruns the scan (as an overflow does).  Errors of
   // Enqueue / Collect are returned in *err (Collect runs without the engine's
   // lock, so it must not write err_).
+  // With fetch (a device-only batch; the same struct to Enqueue and Collect):
+  // the fetch of the candidate files is enqueued right behind the finalize
+  // kernel -- marked, laid out and packed on the GPU, copied to pinned memory
+  // on the fetch stream beside the next scan's kernels -- for a pre-sized
+  // amount that follows the recent scans'; Collect sets *rerun when the marked
+  // bytes exceed it (Run then fetches the exact amount and the next Enqueue
+  // sizes for it).  Files of the direct threshold or more are copied by
+  // Collect, one hipMemcpyAsync each on the fetch stream.
   struct Ticket {
     int slot = -1;
     uint32_t cand_copy = 0;  // candidates copied back
   };
   bool Enqueue(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files, Ticket* t,
-               std::string* err);
-  bool Collect(Ticket* t, std::vector<Candidate>* cands, BatchStats* st, bool* rerun, std::string* err);
+               std::string* err, FetchOut* fetch = nullptr);
+  bool Collect(Ticket* t, std::vector<Candidate>* cands, BatchStats* st, bool* rerun, std::string* err,
+               FetchOut* fetch = nullptr);
+
+  // Device-only batches: the staging buffer's size (a round packs at most this
+  // much; TSG_FETCH_STAGE_MB, default 256 MiB) and the length from which a file
+  // is copied straight from the arena (TSG_FETCH_DIRECT_MB, default 8 MiB).
+  // Rounded to the packing granule; takes effect with the next scan.
+  void SetFetchSizes(uint64_t stage_bytes, uint64_t direct_bytes);
+  // pinned fetch buffers on loan to a FetchOut
+  void* TakeFetchBuf(size_t need, size_t* cap);
+  void GiveFetchBuf(void* p, size_t cap);
 
   // Device buffers of the last run (for tests / bench).
   hipEvent_t ev_scan0() const { return ev_[1]; }
@@ -154,6 +214,15 @@ class GpuEngine {
     bool busy = false, has_fs = false;
     uint64_t n_bytes = 0;
     uint32_t n_files = 0;
+    // device-only batches: the fetch enqueued with the scan
+    bool has_fetch = false;
+    hipEvent_t ev_f[2] = {};          // before the plan (scan stream) / after the last copy (fetch stream)
+    void* h_fctr = nullptr;           // pinned FetchCounters
+    void* lease = nullptr;            // pinned fetch buffer (TakeFetchBuf)
+    size_t lease_cap = 0;
+    uint64_t fetch_copy = 0;          // packed bytes copied back
+    uint64_t stage = 0, direct = 0;   // the sizes the fetch was enqueued with
+    const uint8_t* d_arena = nullptr; // (direct copies are issued by Collect)
   };
   static constexpr int kSlots = 4;
   std::atomic<uint32_t> cand_recent_{0};  // largest candidate count of the recently collected scans
@@ -173,6 +242,26 @@ class GpuEngine {
   bool reap_stop_ = false;           // (reap_mu_)
   std::thread reaper_;               // started with the first retirement
   std::atomic<uint64_t> retired_pending_{0}, retired_freed_{0};
+  // Device-only batches (fetch.h).  The plan's scratch, the staging buffer and
+  // the counters are shared by the scans in flight, in stream order: a pack
+  // waits (ev_drained_) for the copy of the round before it, of this scan or of
+  // the one before, and the copy (fetch_stream_) for its pack (ev_packed_).
+  bool IssueFetch(const uint8_t* d_arena, const uint64_t* d_offsets, uint32_t n_files, const uint32_t* h_flags,
+                  uint64_t direct, uint64_t stage, uint64_t copy_bytes, uint8_t* h_dst, void* h_ctr, hipEvent_t ev0);
+  bool FetchNow(const uint8_t* d_arena, const uint64_t* d_offsets, uint32_t n_files, std::vector<uint8_t> want,
+                bool upload_flags, FetchOut* out);
+  void NoteFetch(uint64_t packed, uint64_t total);
+  bool EnsureFetchStream();
+  std::atomic<uint64_t> fetch_stage_bytes_{uint64_t(256) << 20}, fetch_direct_bytes_{uint64_t(8) << 20};
+  std::atomic<uint64_t> fetch_recent_packed_{0}, fetch_recent_total_{0};
+  hipStream_t fetch_stream_ = nullptr;
+  hipEvent_t ev_packed_ = nullptr, ev_drained_ = nullptr, ev_run_f_[2] = {};
+  void* d_fscratch_ = nullptr; size_t cap_fscratch_ = 0;
+  void* d_fstage_ = nullptr; size_t cap_fstage_ = 0;
+  void* d_fctr_ = nullptr;
+  void* h_run_fctr_ = nullptr;  // pinned FetchCounters of Run / FetchFiles
+  void* h_fflags_ = nullptr; size_t cap_h_fflags_ = 0;  // pinned flags upload (FetchFiles)
+  std::unique_ptr<FetchPool> fetch_pool_;  // pinned buffers not on loan (fetch_host.h)
 
  public:
   // Host memory bookkeeping (tests, tsg_debug_scanner_engine): retired

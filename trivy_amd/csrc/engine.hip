@@ -33,6 +33,8 @@
 #include <type_traits>
 
 #include "engine.h"
+#include "fetch.h"
+#include "fetch_host.h"
 #include "xform.h"
 #include "filter.h"
 
@@ -2287,6 +2289,13 @@ bool Upload(std::string* err, T** dst, const T* src, size_t n) {
 }  // namespace
 
 GpuEngine::GpuEngine(const CompiledRules& cr, int device) : device_(device) {
+  fetch_pool_.reset(new FetchPool(
+      size_t(kSlots) + 2,
+      [](size_t n) -> void* {
+        void* p = nullptr;
+        return hipHostMalloc(&p, n, hipHostMallocDefault) == hipSuccess ? p : nullptr;
+      },
+      [this](void* p) { RetireHost(p); }));
   if (hipSetDevice(device) != hipSuccess) {
     err_ = "hipSetDevice failed (no HIP device?)";
     return;
@@ -2301,6 +2310,13 @@ GpuEngine::GpuEngine(const CompiledRules& cr, int device) : device_(device) {
   for (auto& e : ev_x_) hipEventCreate(&e);
   if (const char* cm = std::getenv("TSG_INGEST_CHUNK_MB")) chunk_bytes_ = uint64_t(std::atoll(cm)) << 20;
   if (chunk_bytes_ < (uint64_t(1) << 20)) chunk_bytes_ = uint64_t(1) << 20;
+  {  // device-only batches (fetch.h): the staging size and the direct-copy threshold
+    const char* sm = std::getenv("TSG_FETCH_STAGE_MB");
+    const char* dm = std::getenv("TSG_FETCH_DIRECT_MB");
+    if (sm || dm)
+      SetFetchSizes(sm ? uint64_t(std::max(1ll, std::atoll(sm))) << 20 : fetch_stage_bytes_.load(),
+                    dm ? uint64_t(std::max(1ll, std::atoll(dm))) << 20 : fetch_direct_bytes_.load());
+  }
   for (auto& e : ev_) hipEventCreate(&e);
   if (const char* dm = std::getenv("TSG_DIAG_SCAN")) diag_mode_ = uint32_t(std::atoi(dm));
   if (const char* dc = std::getenv("TSG_DIAG_CONFIRM")) diag_confirm_ = uint32_t(std::atoi(dc));
@@ -2656,7 +2672,19 @@ GpuEngine::~GpuEngine() {
     if (S.done) hipEventDestroy(S.done);
     if (S.h_cnt) hipHostFree(S.h_cnt);
     if (S.h_cands) hipHostFree(S.h_cands);
+    for (auto& e : S.ev_f)
+      if (e) hipEventDestroy(e);
+    if (S.h_fctr) hipHostFree(S.h_fctr);
+    if (S.lease) hipHostFree(S.lease);
   }
+  for (void* p : {d_fscratch_, d_fstage_, d_fctr_})
+    if (p) hipFree(p);
+  for (void* h : {h_run_fctr_, h_fflags_})
+    if (h) hipHostFree(h);
+  for (void* p : fetch_pool_->Drain()) hipHostFree(p);
+  for (hipEvent_t e : {ev_packed_, ev_drained_, ev_run_f_[0], ev_run_f_[1]})
+    if (e) hipEventDestroy(e);
+  if (fetch_stream_) hipStreamDestroy(fetch_stream_);
   for (void* p : retired_host_) hipHostFree(p);  // (the reaper was joined first)
   for (auto& e : ev_h2d_)
     if (e) hipEventDestroy(e);
@@ -2779,6 +2807,7 @@ struct GpuEngine::HostCall {
   const uint8_t* kinds;
   const uint8_t* gather_dev = nullptr;  // device address of the mapped gather_base (RunHost)
   const uint64_t* gather_src = nullptr;
+  const uint8_t* d_src = nullptr;  // the bytes as read are resident in HBM (RunHost d_src)
   bool cancelled = false;  // ring_mu_: a chunk failed; the call's later slots are not copied
   hipEvent_t ev0 = nullptr, ev1 = nullptr;  // first copy issued / last chunk scanned
   bool ev0_recorded = false;
@@ -2872,6 +2901,20 @@ bool GpuEngine::CopyChunk(const StageJob& j, std::string* err) {
       return fail("chunk gather", x);
     return true;
   }
+  if (c.d_src) {  // resident bytes as read: the chunk device to device, the rest as for a host chunk
+    for (uint64_t p = a; p < e; p += uint64_t(1) << 30)
+      if ((x = hipMemcpyAsync(d + (p - a), c.d_src + p, std::min<uint64_t>(e - p, uint64_t(1) << 30),
+                              hipMemcpyDeviceToDevice, copy_stream_)) != hipSuccess)
+        return fail("chunk copy (device)", x);
+    if ((x = hipMemsetAsync(d + (e - a), 0, 64, copy_stream_)) != hipSuccess ||
+        (x = hipMemcpyAsync(d_stage_off_[b], h_off_[b], (size_t(nf) + 1) * 8, hipMemcpyHostToDevice,
+                            copy_stream_)) != hipSuccess ||
+        (c.kinds && (x = hipMemcpyAsync(d_kind_[b], c.kinds + j.f0, nf, hipMemcpyHostToDevice, copy_stream_)) !=
+                        hipSuccess) ||
+        (x = hipEventRecord(ev_copied_[b], copy_stream_)) != hipSuccess)
+      return fail("chunk copy (device)", x);
+    return true;
+  }
   // in pieces of at most 1 GiB (a lone file can make a chunk of many GiB)
   for (uint64_t p = a; p < e; p += uint64_t(1) << 30)
     if ((x = hipMemcpyAsync(d + (p - a), c.h_arena + p, std::min<uint64_t>(e - p, uint64_t(1) << 30),
@@ -2919,7 +2962,7 @@ void GpuEngine::CopierLoop() {
 bool GpuEngine::RunHost(const uint8_t* h_arena, uint64_t n_bytes, const uint64_t* h_offsets, uint32_t n_files,
                         std::vector<Candidate>* cands, BatchStats* st, const uint8_t* kinds, TailOut* tail,
                         std::mutex* dev_mu, std::string* err, const uint8_t* gather_base,
-                        const uint64_t* gather_src) {
+                        const uint64_t* gather_src, const uint8_t* d_src) {
   if (!dev_mu) dev_mu = &dev_mu_;
   cands->clear();
   BatchStats local;
@@ -2940,6 +2983,7 @@ bool GpuEngine::RunHost(const uint8_t* h_arena, uint64_t n_bytes, const uint64_t
   };
   if (kinds && !tail) return set_err("RunHost: a transformed batch needs a tail output");
   if (gather_base && (!gather_src || !kinds)) return set_err("RunHost: a gathered batch needs source offsets and kinds");
+  if (d_src && (!kinds || gather_base)) return set_err("RunHost: a device source needs kinds and no gather");
   if (n_files == 0) return true;
   const uint8_t* gather_dev = nullptr;
   if (gather_base) {  // the device address of the mapped host buffer (tsg_host_register_mapped)
@@ -2962,6 +3006,7 @@ bool GpuEngine::RunHost(const uint8_t* h_arena, uint64_t n_bytes, const uint64_t
   HostCall call{h_arena, h_offsets, kinds};
   call.gather_dev = gather_dev;
   call.gather_src = gather_src;
+  call.d_src = d_src;
   if (hipSetDevice(device_) != hipSuccess || hipEventCreate(&call.ev0) != hipSuccess ||
       hipEventCreate(&call.ev1) != hipSuccess) {
     if (call.ev0) hipEventDestroy(call.ev0);
@@ -3194,7 +3239,7 @@ void GpuEngine::InitCaps(uint64_t n_bytes) {
 }
 
 bool GpuEngine::Enqueue(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
-                        Ticket* t, std::string* err) {
+                        Ticket* t, std::string* err, FetchOut* fetch) {
   t->slot = -1;
   if (n_files == 0 || n_bytes >= (uint64_t(1) << 36) - 64 || d_item_diag_ || diag_mode_ != 0) return false;
   int k = -1;
@@ -3212,6 +3257,11 @@ bool GpuEngine::Enqueue(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t
     // copies into the slot's pinned buffers may be queued: let them finish
     // before the slot (and its buffers) can be reused or freed
     (void)hipStreamSynchronize(stream_);
+    if (fetch && fetch_stream_) (void)hipStreamSynchronize(fetch_stream_);
+    if (S.lease) GiveFetchBuf(S.lease, S.lease_cap);
+    S.lease = nullptr;
+    S.lease_cap = 0;
+    S.has_fetch = false;
     *err = err_.empty() ? "Enqueue failed" : err_;
     std::lock_guard<std::mutex> g(slot_mu_);
     S.busy = false;
@@ -3256,14 +3306,43 @@ bool GpuEngine::Enqueue(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t
   }
   uint64_t n_chunks = (n_bytes + kChunk - 1) / kChunk;
   if (n_chunks == 0) n_chunks = 1;
+  S.has_fetch = false;
+  if (fetch) {  // a device-only batch: the slot's fetch events, counters and pinned buffer
+    bool ok = EnsureFetchStream();
+    if (ok && !S.h_fctr)
+      ok = hipHostMalloc(&S.h_fctr, sizeof(FetchCounters), hipHostMallocDefault) == hipSuccess &&
+           hipEventCreate(&S.ev_f[0]) == hipSuccess && hipEventCreate(&S.ev_f[1]) == hipSuccess;
+    if (ok) {
+      S.stage = fetch_stage_bytes_.load();
+      S.direct = fetch_direct_bytes_.load();
+      // The packed bytes copied back follow the recent scans' (as the candidate
+      // read-back does), never more than every file of the batch rounded up.
+      const uint64_t rp = fetch_recent_packed_.load(), rt = fetch_recent_total_.load();
+      const uint64_t all = n_bytes + 16 * uint64_t(n_files);
+      const uint64_t copy = std::min(rp + rp / 8 + std::min<uint64_t>(uint64_t(1) << 20, S.stage), all);
+      S.fetch_copy = (copy + 15) & ~uint64_t(15);
+      S.lease = TakeFetchBuf(size_t(std::max(S.fetch_copy, std::min(rt + rt / 8, all)) + 64), &S.lease_cap);
+      ok = S.lease != nullptr;
+    }
+    if (!ok) {
+      if (err_.empty()) err_ = "Enqueue: fetch stream / pinned fetch buffer";
+      return fail();
+    }
+  }
   if (!EnqueuePhase(d_arena, n_bytes, d_offsets, n_files, n_chunks, S.ev, S.ev_fs) ||
       hipMemcpyAsync(S.h_cnt, d_counters_, 64, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
       hipMemcpyAsync(S.h_cands, d_cands_, size_t(n_copy) * sizeof(Candidate), hipMemcpyDeviceToHost, stream_) !=
           hipSuccess ||
-      hipEventRecord(S.done, stream_) != hipSuccess) {
+      // the fetch right behind: no host round trip between the candidates and its launch
+      (fetch && (!IssueFetch(d_arena, d_offsets, n_files, nullptr, S.direct, S.stage, S.fetch_copy,
+                             static_cast<uint8_t*>(S.lease), S.h_fctr, S.ev_f[0]) ||
+                 hipEventRecord(S.ev_f[1], fetch_stream_) != hipSuccess)) ||
+      hipEventRecord(S.done, fetch ? fetch_stream_ : stream_) != hipSuccess) {
     if (err_.empty()) err_ = "Enqueue: HIP call failed";
     return fail();
   }
+  S.has_fetch = fetch != nullptr;
+  S.d_arena = d_arena;
   S.n_bytes = n_bytes;
   S.n_files = n_files;
   S.has_fs = n_fullscan_rules_ > 0;
@@ -3272,7 +3351,8 @@ bool GpuEngine::Enqueue(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t
   return true;
 }
 
-bool GpuEngine::Collect(Ticket* t, std::vector<Candidate>* cands, BatchStats* st, bool* rerun, std::string* err) {
+bool GpuEngine::Collect(Ticket* t, std::vector<Candidate>* cands, BatchStats* st, bool* rerun, std::string* err,
+                        FetchOut* fetch) {
   *rerun = false;
   if (t->slot < 0 || t->slot >= kSlots) {
     *err = "Collect: no ticket";
@@ -3280,6 +3360,10 @@ bool GpuEngine::Collect(Ticket* t, std::vector<Candidate>* cands, BatchStats* st
   }
   Slot& S = slots_[t->slot];
   auto release = [&] {
+    if (S.lease) GiveFetchBuf(S.lease, S.lease_cap);  // (not handed to the caller)
+    S.lease = nullptr;
+    S.lease_cap = 0;
+    S.has_fetch = false;
     std::lock_guard<std::mutex> g(slot_mu_);
     S.busy = false;
     t->slot = -1;
@@ -3314,6 +3398,62 @@ bool GpuEngine::Collect(Ticket* t, std::vector<Candidate>* cands, BatchStats* st
   for (uint32_t i = 0; i < cnt[1]; i++)  // closed keyword gates (finalize_kernel) never reach the host
     if (!(S.h_cands[i].flags & kCandDrop)) cands->push_back(S.h_cands[i]);
   st->candidates = cands->size();
+  if (S.has_fetch) {
+    bool ok = fetch != nullptr && fetch->h_offsets != nullptr;
+    if (!ok) *err = "Collect: the ticket's scan was enqueued with a fetch";
+    HostFetchPlan P;
+    if (ok) {
+      std::vector<uint8_t> want(S.n_files, 0);
+      for (const Candidate& c : *cands)
+        if (c.file < S.n_files) want[c.file] = 1;
+      PlanFetchOnHost(std::move(want), fetch->h_offsets, S.n_files, S.direct, fetch, &P);
+      const FetchCounters& C = *static_cast<const FetchCounters*>(S.h_fctr);
+      ok = SameFetchPlan(C.packed_bytes, C.n_direct, C.n_files, C.file_bytes, P, err);
+    }
+    if (ok) {
+      NoteFetch(P.packed, P.total);
+      if (P.packed > S.fetch_copy || P.total + 64 > S.lease_cap) {  // more marked than pre-sized: Run fetches it all
+        *rerun = true;
+        release();
+        return true;
+      }
+      float ms = 0;
+      if (P.files) hipEventElapsedTime(&ms, S.ev_f[0], S.ev_f[1]);  // (nothing marked: nothing was fetched)
+      double ms_direct = 0;
+      if (!P.direct.empty()) {
+        // files copied where they lie: one copy each on the fetch stream, beside whatever the scan
+        // stream runs (the arena is the caller's, the buffer this ticket's: no engine state is touched)
+        const auto t0 = std::chrono::steady_clock::now();
+        hipError_t e = hipSetDevice(device_);
+        for (size_t i = 0; i < P.direct.size() && e == hipSuccess; i++) {
+          const uint32_t f = P.direct[i];
+          e = hipMemcpyAsync(static_cast<uint8_t*>(S.lease) + fetch->off[f], S.d_arena + fetch->h_offsets[f],
+                             size_t(fetch->h_offsets[f + 1] - fetch->h_offsets[f]), hipMemcpyDeviceToHost,
+                             fetch_stream_);
+        }
+        if (e == hipSuccess) e = hipEventRecord(S.ev_f[1], fetch_stream_);
+        if (e == hipSuccess) e = WaitEvent(S.ev_f[1]);
+        if (e != hipSuccess) {
+          *err = std::string("Collect: direct fetch: ") + hipGetErrorString(e);
+          ok = false;
+        }
+        ms_direct = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      }
+      if (ok) {
+        FinishFetch(P, S.stage, double(ms) + ms_direct, fetch);
+        fetch->buf = static_cast<const uint8_t*>(S.lease);
+        fetch->owner = this;
+        fetch->lease = S.lease;
+        fetch->lease_cap = S.lease_cap;
+        S.lease = nullptr;
+        S.lease_cap = 0;
+      }
+    }
+    if (!ok) {
+      release();
+      return false;
+    }
+  }
   hipEventElapsedTime(&st->ms_scan, S.ev[1], S.ev[2]);
   hipEventElapsedTime(&st->ms_confirm, S.ev[2], S.ev[3]);
   hipEventElapsedTime(&st->ms_careful, S.ev[3], S.ev[4]);
@@ -3556,8 +3696,147 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
   return true;
 }
 
+// ---------------------------------------------------------------------------
+// Device-only batches: the candidate files' bytes back to the host (fetch.h)
+// ---------------------------------------------------------------------------
+
+void FetchOut::Release() {
+  if (owner && lease) owner->GiveFetchBuf(lease, lease_cap);
+  owner = nullptr;
+  lease = nullptr;
+  lease_cap = 0;
+  buf = nullptr;
+}
+
+void GpuEngine::SetFetchSizes(uint64_t stage_bytes, uint64_t direct_bytes) {
+  fetch_stage_bytes_.store(std::max<uint64_t>(kFetchSeg, stage_bytes / kFetchSeg * kFetchSeg));
+  fetch_direct_bytes_.store(std::max<uint64_t>(1, direct_bytes));
+}
+
+// Pinned fetch buffers (fetch_host.h FetchPool): allocated here, retired through RetireHost.
+void* GpuEngine::TakeFetchBuf(size_t need, size_t* cap) { return fetch_pool_->Take(need, cap); }
+void GpuEngine::GiveFetchBuf(void* p, size_t cap) { fetch_pool_->Give(p, cap); }
+
+bool GpuEngine::EnsureFetchStream() {
+  if (fetch_stream_) return true;
+  HIP_OK(hipStreamCreateWithFlags(&fetch_stream_, hipStreamNonBlocking));
+  HIP_OK(hipEventCreateWithFlags(&ev_packed_, hipEventDisableTiming));
+  HIP_OK(hipEventCreateWithFlags(&ev_drained_, hipEventDisableTiming));
+  HIP_OK(hipEventCreate(&ev_run_f_[0]));
+  HIP_OK(hipEventCreate(&ev_run_f_[1]));
+  HIP_OK(hipMalloc(&d_fctr_, sizeof(FetchCounters)));
+  HIP_OK(hipHostMalloc(&h_run_fctr_, sizeof(FetchCounters), hipHostMallocDefault));
+  return true;
+}
+
+// The sizes the next Enqueue pre-sizes its fetch by: the largest of the recent
+// scans', decaying by an eighth per scan (one large batch does not make every
+// later scan copy as much).
+void GpuEngine::NoteFetch(uint64_t packed, uint64_t total) {
+  const uint64_t rp = fetch_recent_packed_.load(), rt = fetch_recent_total_.load();
+  fetch_recent_packed_.store(std::max(packed, rp - rp / 8));
+  fetch_recent_total_.store(std::max(total, rt - rt / 8));
+}
+
+// Plan + rounds of one fetch on the scan stream, the copies of the rounds on
+// the fetch stream (engine.h).  h_flags: the marked files from the host
+// (pinned, n_files u32) instead of the candidate list of the scan just
+// enqueued.  copy_bytes (a multiple of 16) of the packed layout reach h_dst.
+bool GpuEngine::IssueFetch(const uint8_t* d_arena, const uint64_t* d_offsets, uint32_t n_files,
+                           const uint32_t* h_flags, uint64_t direct, uint64_t stage, uint64_t copy_bytes,
+                           uint8_t* h_dst, void* h_ctr, hipEvent_t ev0) {
+  if (!EnsureFetchStream()) return false;
+  const size_t stage_need = size_t(std::max<uint64_t>(std::min(stage, copy_bytes), 16));
+  if (d_fstage_ && cap_fstage_ < stage_need) HIP_OK(hipStreamSynchronize(fetch_stream_));  // a copy may read it still
+  if (!Ensure(&d_fscratch_, &cap_fscratch_, FetchScratchBytes(n_files)) ||
+      !Ensure(&d_fstage_, &cap_fstage_, stage_need))
+    return false;
+  FetchCounters* ctr = static_cast<FetchCounters*>(d_fctr_);
+  HIP_OK(hipEventRecord(ev0, stream_));
+  if (h_flags)
+    HIP_OK(hipMemcpyAsync(FetchFlags(d_fscratch_, n_files), h_flags, size_t(n_files) * 4, hipMemcpyHostToDevice,
+                          stream_));
+  HIP_OK(FetchPlan(h_flags ? nullptr : static_cast<const Candidate*>(d_cands_), d_counters_ + 1, cand_cap_, d_offsets,
+                   n_files, direct, d_fscratch_, ctr, stream_));
+  HIP_OK(hipMemcpyAsync(h_ctr, ctr, sizeof(FetchCounters), hipMemcpyDeviceToHost, stream_));
+  uint8_t* st = static_cast<uint8_t*>(d_fstage_);
+  for (uint64_t w0 = 0; w0 < copy_bytes; w0 += stage) {
+    const uint64_t w1 = std::min(w0 + stage, copy_bytes);
+    HIP_OK(hipStreamWaitEvent(stream_, ev_drained_, 0));  // the staging buffer's last copy is done
+    HIP_OK(FetchPack(d_arena, d_offsets, n_files, d_fscratch_, ctr, w0, w1, st, stream_));
+    HIP_OK(hipEventRecord(ev_packed_, stream_));
+    HIP_OK(hipStreamWaitEvent(fetch_stream_, ev_packed_, 0));
+    HIP_OK(hipMemcpyAsync(h_dst + w0, st, size_t(w1 - w0), hipMemcpyDeviceToHost, fetch_stream_));
+    HIP_OK(hipEventRecord(ev_drained_, fetch_stream_));
+  }
+  if (copy_bytes == 0) {  // the fetch stream's events still follow the plan
+    HIP_OK(hipEventRecord(ev_packed_, stream_));
+    HIP_OK(hipStreamWaitEvent(fetch_stream_, ev_packed_, 0));
+  }
+  return true;
+}
+
+// A fetch sized exactly, waited for (Run's, and FetchFiles'): the marked files
+// are known on the host before it is issued.
+bool GpuEngine::FetchNow(const uint8_t* d_arena, const uint64_t* d_offsets, uint32_t n_files,
+                         std::vector<uint8_t> want, bool upload_flags, FetchOut* out) {
+  if (!out->h_offsets) {
+    err_ = "fetch: the batch's host offsets are missing";
+    return false;
+  }
+  const uint64_t stage = fetch_stage_bytes_.load(), direct = fetch_direct_bytes_.load();
+  HostFetchPlan P;
+  PlanFetchOnHost(std::move(want), out->h_offsets, n_files, direct, out, &P);
+  NoteFetch(P.packed, P.total);
+  out->files = out->bytes = out->direct_files = 0;
+  out->rounds = 0;
+  out->ms_fetch = 0;
+  if (P.files == 0) return true;  // nothing to bring back
+  size_t cap = 0;
+  void* lease = TakeFetchBuf(size_t(P.total) + 64, &cap);
+  if (!lease) {
+    err_ = "fetch: hipHostMalloc failed for " + std::to_string(P.total) + " bytes";
+    return false;
+  }
+  out->owner = this;  // (from here on a failure's lease goes back with *out)
+  out->lease = lease;
+  out->lease_cap = cap;
+  out->buf = static_cast<const uint8_t*>(lease);
+  const uint32_t* h_flags = nullptr;
+  if (upload_flags) {
+    if (!EnsureHost(&h_fflags_, &cap_h_fflags_, size_t(n_files) * 4 + 4)) return false;
+    uint32_t* hf = static_cast<uint32_t*>(h_fflags_);
+    for (uint32_t f = 0; f < n_files; f++) hf[f] = out->fetched[f];
+    h_flags = hf;
+  }
+  if (!IssueFetch(d_arena, d_offsets, n_files, h_flags, direct, stage, P.packed, static_cast<uint8_t*>(lease),
+                  h_run_fctr_, ev_run_f_[0]))
+    return false;
+  for (uint32_t f : P.direct)  // contiguous in the arena: straight to their place
+    HIP_OK(hipMemcpyAsync(static_cast<uint8_t*>(lease) + out->off[f], d_arena + out->h_offsets[f],
+                          size_t(out->h_offsets[f + 1] - out->h_offsets[f]), hipMemcpyDeviceToHost, fetch_stream_));
+  HIP_OK(hipEventRecord(ev_run_f_[1], fetch_stream_));
+  HIP_OK(WaitEvent(ev_run_f_[1]));
+  std::string why;
+  const FetchCounters& C = *static_cast<const FetchCounters*>(h_run_fctr_);
+  if (!SameFetchPlan(C.packed_bytes, C.n_direct, C.n_files, C.file_bytes, P, &why)) {
+    err_ = why;
+    return false;
+  }
+  float ms = 0;
+  hipEventElapsedTime(&ms, ev_run_f_[0], ev_run_f_[1]);
+  FinishFetch(P, stage, ms, out);
+  return true;
+}
+
+bool GpuEngine::FetchFiles(const uint8_t* d_arena, const uint64_t* d_offsets, uint32_t n_files,
+                           const std::vector<uint8_t>& want, FetchOut* out) {
+  HIP_OK(hipSetDevice(device_));
+  return FetchNow(d_arena, d_offsets, n_files, want, true, out);
+}
+
 bool GpuEngine::Run(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
-                    std::vector<Candidate>* cands, BatchStats* st) {
+                    std::vector<Candidate>* cands, BatchStats* st, FetchOut* fetch) {
   HIP_OK(hipSetDevice(device_));
   cands->clear();
   BatchStats local;
@@ -3646,6 +3925,12 @@ bool GpuEngine::Run(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_
     st->fold_sites = cnt[9];
     hipEventElapsedTime(&st->ms_chunkmap, ev_[0], ev_[1]);
     hipEventElapsedTime(&st->ms_total, ev_[0], ev_[6]);
+    if (fetch) {  // a device-only batch: the candidate files' bytes, sized exactly
+      std::vector<uint8_t> want(n_files, 0);
+      for (const Candidate& c : *cands)
+        if (c.file < n_files) want[c.file] = 1;
+      if (!FetchNow(d_arena, d_offsets, n_files, std::move(want), false, fetch)) return false;
+    }
     return true;
   }
   err_ = "candidate buffers kept overflowing";

@@ -1455,8 +1455,10 @@ void SecretScanner::GpuFindingsInput(const uint8_t* content, const Candidate* c,
   out->gpu = true;
 }
 
-bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst, HostStats* hst, std::string* err) {
+bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst, HostStats* hst, std::string* err,
+                         FetchStats* fst) {
   double t0 = NowMs();
+  if (fst) *fst = FetchStats();
   struct Active {
     std::atomic<int>& n;
     explicit Active(std::atomic<int>& c) : n(c) { n.fetch_add(1); }
@@ -1484,31 +1486,67 @@ bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst
   bool ok;
   std::string gpu_err;
   TailOut tail;  // GPU pre-transform: the transformed bytes of the files with candidates
-  if (in.transform && in.dev_arena) {
-    allow_thread.join();
-    *err = "a pre-transformed batch must be host-resident";
-    return false;
+  // A device-only batch (no host copy of the bytes): the candidate files come
+  // back from HBM with the candidates (GpuEngine, fetch.h).  A batch with a
+  // host arena takes the paths below exactly as before.
+  const bool dev_only = in.dev_arena && !in.host_arena;
+  FetchOut fetch;
+  fetch.h_offsets = in.host_offsets;
+  FetchOut* fp = dev_only && !in.transform ? &fetch : nullptr;
+  // dev_offsets is optional: without it the offsets are uploaded for this scan
+  struct DevOffsets {
+    void* p = nullptr;
+    ~DevOffsets() {
+      if (p) (void)hipFree(p);
+    }
+  } own_off;
+  const uint64_t* dev_offsets = in.dev_offsets;
+  if (in.dev_arena && !dev_offsets && in.n_files) {
+    const size_t nb = (size_t(in.n_files) + 1) * 8;
+    if (hipSetDevice(engine->device()) != hipSuccess || hipMalloc(&own_off.p, nb) != hipSuccess ||
+        hipMemcpy(own_off.p, in.host_offsets, nb, hipMemcpyHostToDevice) != hipSuccess) {
+      allow_thread.join();
+      *err = "tsg_scan: uploading the offsets of a resident batch failed";
+      return false;
+    }
+    dev_offsets = static_cast<const uint64_t*>(own_off.p);
   }
   GpuEngine::Ticket ticket;
-  if (!in.dev_arena) {  // the staging ring orders concurrent host batches; it takes the lock per chunk
+  if (in.transform && in.dev_arena) {
+    // resident bytes as read: RunHost's chunk pipeline with a device source; the transformed
+    // candidate files come back in `tail`, the ones the transform left alone through the fetch
+    ok = engine->RunHost(nullptr, n_bytes, in.host_offsets, in.n_files, &cands, gst, in.transform, &tail,
+                         &gpu_mu_[slot], &gpu_err, nullptr, nullptr, in.dev_arena);
+    if (ok && !in.host_arena) {
+      std::vector<uint8_t> want(in.n_files, 0);
+      bool any = false;
+      for (const Candidate& c : cands)
+        if (c.file < in.n_files && tail.raw[c.file]) want[c.file] = 1, any = true;
+      if (any) {
+        std::lock_guard<std::mutex> g(gpu_mu_[slot]);
+        ok = engine->FetchFiles(in.dev_arena, dev_offsets, in.n_files, want, &fetch);
+        if (!ok) gpu_err = engine->error();
+      }
+    }
+  } else if (!in.dev_arena) {  // the staging ring orders concurrent host batches; it takes the lock per chunk
     ok = engine->RunHost(in.host_arena, n_bytes, in.host_offsets, in.n_files, &cands, gst, in.transform,
                          in.transform ? &tail : nullptr, &gpu_mu_[slot], &gpu_err, in.gather_base, in.gather_src);
   } else {
     std::lock_guard<std::mutex> g(gpu_mu_[slot]);
     static const bool tickets = !std::getenv("TSG_TICKETS") || std::atoi(std::getenv("TSG_TICKETS")) != 0;
     std::string enq_err;  // a failed Enqueue (no free ticket, or a HIP error) falls back to Run
-    if (tickets && engine->Enqueue(in.dev_arena, n_bytes, in.dev_offsets, in.n_files, &ticket, &enq_err))
+    if (tickets && engine->Enqueue(in.dev_arena, n_bytes, dev_offsets, in.n_files, &ticket, &enq_err, fp))
       ok = true;  // collected below, after the lock is released
     else
-      ok = engine->Run(in.dev_arena, n_bytes, in.dev_offsets, in.n_files, &cands, gst);
+      ok = engine->Run(in.dev_arena, n_bytes, dev_offsets, in.n_files, &cands, gst, fp);
     if (!ok && gpu_err.empty()) gpu_err = engine->error();
   }
   if (ticket.slot >= 0) {
     bool rerun = false;
-    ok = engine->Collect(&ticket, &cands, gst, &rerun, &gpu_err);
+    ok = engine->Collect(&ticket, &cands, gst, &rerun, &gpu_err, fp);
     if (ok && rerun) {  // a buffer overflowed: grow and rescan synchronously
       std::lock_guard<std::mutex> g(gpu_mu_[slot]);
-      ok = engine->Run(in.dev_arena, n_bytes, in.dev_offsets, in.n_files, &cands, gst);
+      ok = engine->Run(in.dev_arena, n_bytes, dev_offsets, in.n_files, &cands, gst, fp);
       if (!ok) gpu_err = engine->error();  // read under the engine's lock
     }
   }
@@ -1518,6 +1556,7 @@ bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst
     return false;
   }
   BatchInput tin = in;  // the exact pass reads the transformed bytes
+  tin.dev_offsets = dev_offsets;
   std::vector<const uint8_t*> fdata;
   std::vector<uint64_t> flen;
   if (in.transform) {  // gathered files from tail.buf, identity-transformed ones in place
@@ -1527,7 +1566,8 @@ bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst
       const uint32_t f = c.file;
       if (f >= in.n_files || fdata[f]) continue;
       if (tail.raw[f]) {  // as read: in the batch arena, or where the gather took it from
-        fdata[f] = in.gather_base ? in.gather_base + in.gather_src[f] : in.host_arena + in.host_offsets[f];
+        if (dev_only) fdata[f] = fetch.buf + fetch.off[f];  // (fetched: no host arena to read it from)
+        else fdata[f] = in.gather_base ? in.gather_base + in.gather_src[f] : in.host_arena + in.host_offsets[f];
         flen[f] = in.host_offsets[f + 1] - in.host_offsets[f];
       } else {
         fdata[f] = tail.buf.data() + tail.off[f];
@@ -1536,6 +1576,24 @@ bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst
     }
     tin.file_data = fdata.data();
     tin.file_len = flen.data();
+  } else if (dev_only) {  // the fetched files, where the fetch put them
+    fdata.assign(in.n_files, nullptr);
+    flen.assign(in.n_files, 0);
+    for (uint32_t f = 0; f < in.n_files && f < fetch.fetched.size(); f++) {
+      if (!fetch.fetched[f]) continue;
+      fdata[f] = fetch.buf + fetch.off[f];
+      flen[f] = in.host_offsets[f + 1] - in.host_offsets[f];
+    }
+    tin.file_data = fdata.data();
+    tin.file_len = flen.data();
+    tin.file_data_is_arena = true;
+  }
+  if (fst) {
+    fst->rounds = fetch.rounds;
+    fst->files = fetch.files;
+    fst->bytes = fetch.bytes;
+    fst->direct_files = fetch.direct_files;
+    fst->ms_fetch = fetch.ms_fetch;
   }
   double t1 = NowMs();
   if (const char* dump = std::getenv("TSG_DUMP_CANDS")) {  // profiling aid (tools/host_tail_bench.py)
@@ -1764,7 +1822,7 @@ bool SecretScanner::HostTail(const BatchInput& in, std::vector<Candidate>* cands
   // the GPU pass costs GPU time beside the next scans' kernels, which a GPU-bound pipeline (C2) pays)
   const int gf_mode = gpu_findings_.load();
   const bool gpu_mat = mat_ && gpu_windows && (gf_mode == 1 || (gf_mode == 2 && host_bound_.load())) &&
-                       in.dev_arena && in.dev_offsets && !in.file_data;
+                       in.dev_arena && in.dev_offsets && (!in.file_data || in.file_data_is_arena);
   auto scan_group = [&](size_t k) {
     const size_t a = starts[k], b = starts[k + 1];
     const uint32_t f = group_file(k);

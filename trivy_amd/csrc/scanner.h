@@ -219,19 +219,23 @@ struct BatchResult {
 
 struct BatchInput {
   uint32_t n_files = 0;
-  const uint8_t* host_arena = nullptr;  // required: the exact pass reads it
+  const uint8_t* host_arena = nullptr;  // the exact pass reads it; NULL with dev_arena: a device-only batch
+                                        // (the candidate files are fetched from HBM, engine.h FetchOut)
   const uint64_t* host_offsets = nullptr;
   const uint8_t* dev_arena = nullptr;   // optional: resident in HBM already
-  const uint64_t* dev_offsets = nullptr;
+  const uint64_t* dev_offsets = nullptr;  // optional (uploaded per scan without it)
   const char* const* paths = nullptr;
   const uint64_t* path_lens = nullptr;  // optional (else strlen)
   const uint8_t* binary = nullptr;      // optional per-file Binary flag
   const uint8_t* transform = nullptr;   // optional per-file pre-transform (xform.h) run on the GPU: then
-                                        // host_arena holds the bytes as read (host-resident batches only)
+                                        // host_arena / dev_arena hold the bytes as read
   // optional, per file: where the exact pass reads file f (file_data[f], file_len[f] bytes) instead of
   // host_arena + host_offsets[f] (a GPU pre-transformed batch: the gathered transformed files)
   const uint8_t* const* file_data = nullptr;
   const uint64_t* file_len = nullptr;
+  // file_data holds the bytes of dev_arena (a device-only batch's fetched files): the GPU findings
+  // pass may read the resident arena for them
+  bool file_data_is_arena = false;
   const uint8_t* dev_paths = nullptr;   // optional: the paths packed in HBM (the allow-path prefilter runs
   const uint64_t* dev_path_off = nullptr;  // on the GPU, pathfilter.h); n_files + 1 offsets, device
   const uint8_t* host_paths = nullptr;      // optional: the paths packed in host memory (copied to HBM for
@@ -245,6 +249,13 @@ struct BatchInput {
 struct HostStats {
   double ms_gpu = 0, ms_allow = 0, ms_exact = 0, ms_total = 0;
   uint64_t candidates = 0, files_with_candidates = 0, findings = 0;
+};
+
+// What a device-only batch's scan brought back from HBM for the exact pass (all zero otherwise).
+struct FetchStats {
+  uint32_t rounds = 0;
+  uint64_t files = 0, bytes = 0, direct_files = 0;
+  double ms_fetch = 0;
 };
 
 class SecretScanner {
@@ -264,7 +275,8 @@ class SecretScanner {
   const std::string& error() const { return err_; }
 
   // Thread-safe: concurrent scans report failures through *err only (no shared state).
-  bool Scan(const BatchInput& in, BatchResult* out, BatchStats* gst, HostStats* hst, std::string* err);
+  bool Scan(const BatchInput& in, BatchResult* out, BatchStats* gst, HostStats* hst, std::string* err,
+            FetchStats* fst = nullptr);
   // The exact host tail over a given candidate list (what Scan runs after the GPU).
   // The exact host pass over the GPU's candidates.  `allowed` (per-file
   // global AllowPath results) is computed here when not supplied.

@@ -83,6 +83,14 @@ class _CStats(c.Structure):
                 ("ms_xform_kernel", c.c_double)]
 
 
+class _CFetchStats(c.Structure):  # tsg_fetch_stats (versioned: struct_size first)
+    _fields_ = [("struct_size", c.c_uint32), ("rounds", c.c_uint32), ("files", c.c_uint64),
+                ("bytes", c.c_uint64), ("direct_files", c.c_uint64), ("ms_fetch", c.c_double)]
+
+
+FETCH_STATS_SIZE_V1 = c.sizeof(_CFetchStats)  # TSG_FETCH_STATS_SIZE_V1
+
+
 class _CTableInfo(c.Structure):
     _fields_ = [(n, c.c_uint32) for n in ("n_rules", "n_keywords", "n_anchors", "n_filter_items",
                                           "n_filter_buckets", "filter_window", "n_fullscan_rules",
@@ -107,6 +115,8 @@ def _declare(L):
     L.tsg_result_json_range.argtypes = [c.c_void_p, c.c_uint32, c.c_uint32, c.POINTER(c.c_void_p),
                                         c.POINTER(c.c_uint64)]
     L.tsg_result_stats.argtypes = [c.c_void_p, c.POINTER(_CStats)]
+    if hasattr(L, "tsg_result_fetch_stats"):
+        L.tsg_result_fetch_stats.argtypes = [c.c_void_p, c.POINTER(_CFetchStats)]
     if hasattr(L, "tsg_result_records"):
         L.tsg_result_records.argtypes = [c.c_void_p, c.c_void_p, c.c_uint64]
         L.tsg_result_records.restype = c.c_uint64
@@ -253,6 +263,7 @@ class Scanner:
         if rc != 0:
             raise RuntimeError("tsg_scanner_new failed: %s" % _lib.last_error(L))
         self._h = h
+        self.device = None if host_only else int(device)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -296,6 +307,8 @@ class Scanner:
         """transform: per-file pre-transform kinds (uint8; 1 = CR strip, 2 = printable runs) run on the
         GPU over the host arena (the bytes as read)."""
         n = len(offsets) - 1
+        if arena is None and dev_arena is None:
+            raise ValueError("a batch needs arena, dev_arena or both")
         arena_buf = np.frombuffer(arena, dtype=np.uint8) if isinstance(arena, (bytes, bytearray)) else arena
         offs = np.ascontiguousarray(offsets, dtype=np.uint64)
         plen = None
@@ -309,17 +322,20 @@ class Scanner:
             paths_addr = c.cast(parr, c.c_void_p).value
             plen_ptr = plen.ctypes.data
         bin_arr = np.array(binary, dtype=np.uint8) if binary is not None else None
-        batch = _CBatch(n, arena_buf.ctypes.data, offs.ctypes.data,
+        kinds = np.ascontiguousarray(transform, dtype=np.uint8) if transform is not None else None
+        batch = _CBatch(n, arena_buf.ctypes.data if arena_buf is not None else None, offs.ctypes.data,
                         dev_arena, dev_offsets, paths_addr, plen_ptr,
                         bin_arr.ctypes.data if bin_arr is not None else None,
-                        transform.ctypes.data if transform is not None else None,
+                        kinds.ctypes.data if kinds is not None else None,
                         dev_paths, dev_path_offsets)
-        return (arena_buf, offs, parr, plen, bin_arr, transform), batch
+        return (arena_buf, offs, parr, plen, bin_arr, kinds), batch
 
     def scan_arena(self, arena, offsets, paths, binary=None, dev_arena=None, dev_offsets=None, dev_paths=None,
                    dev_path_offsets=None, host_paths=None, host_path_offsets=None, gather_base=None,
                    gather_src=None, transform=None):
-        """One batch (tsg_scan).  dev_arena / dev_offsets: the contents already in HBM;
+        """One batch (tsg_scan).  dev_arena / dev_offsets: the contents already in HBM; with
+        arena None the batch is device-only (host_arena NULL: the candidate files are fetched from
+        HBM for the exact pass, ScanResult.fetch_stats());
         dev_paths / dev_path_offsets: the paths packed in HBM (GPU allow-path prefilter);
         host_paths / host_path_offsets (numpy u8 / u64): the paths packed in host memory, passed
         through the versioned tsg_batch_ext (tsg_scan_ext).  gather_base (a uint8 array registered
@@ -330,7 +346,8 @@ class Scanner:
         if gather_base is not None:
             if arena is not None or transform is None or gather_src is None:
                 raise ValueError("scan_arena(gather): arena None, gather_src and transform required")
-            arena = np.zeros(1, np.uint8)  # (not passed: host_arena is NULL in a gathered batch)
+        elif arena is None and dev_arena is None:
+            raise ValueError("scan_arena: a batch needs arena, dev_arena or both")
         arena_buf = np.frombuffer(arena, dtype=np.uint8) if isinstance(arena, (bytes, bytearray)) else arena
         offs = np.ascontiguousarray(offsets, dtype=np.uint64)
         if isinstance(paths, np.ndarray) and paths.dtype == np.uint64:
@@ -344,7 +361,8 @@ class Scanner:
             plen_ptr = plen.ctypes.data
         bin_arr = np.array(binary, dtype=np.uint8) if binary is not None else None
         kinds = np.ascontiguousarray(transform, dtype=np.uint8) if transform is not None else None
-        batch = _CBatch(n, None if gather_base is not None else arena_buf.ctypes.data, offs.ctypes.data,
+        # host_arena is NULL in a gathered batch and in a device-only one
+        batch = _CBatch(n, arena_buf.ctypes.data if arena_buf is not None else None, offs.ctypes.data,
                         dev_arena, dev_offsets, paths_addr, plen_ptr,
                         bin_arr.ctypes.data if bin_arr is not None else None,
                         kinds.ctypes.data if kinds is not None else None,
@@ -365,6 +383,76 @@ class Scanner:
         if rc != 0:
             raise RuntimeError("tsg_scan failed: %s" % _lib.last_error(self._L))
         return ScanResult(self, h)
+
+    # --- device-only batches (no host copy of the bytes) --------------------
+    def _device_batch(self, dev_arena, offsets, nbytes, dev_offsets):
+        """Checks a resident arena (a torch.uint8 tensor, or an integer device pointer with nbytes)
+        against the contract -- on this scanner's device, contiguous, 16-B aligned, 64 readable
+        bytes past offsets[-1] -- and returns (pointer, dev_offsets pointer, references to keep).
+        Raises ValueError; never pads by copying."""
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if offs.ndim != 1 or len(offs) < 1 or offs[0] != 0 or np.any(offs[1:] < offs[:-1]):
+            raise ValueError("scan_device: offsets must be n_files + 1 ascending values from 0")
+        need = int(offs[-1]) + 64
+        keep = [offs]
+        if isinstance(dev_arena, int):
+            if nbytes is None:
+                raise ValueError("scan_device: an integer device pointer needs nbytes")
+            ptr, have = dev_arena, int(nbytes)
+        else:
+            import torch
+            t = dev_arena
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("scan_device: dev_arena must be a torch.uint8 tensor or an integer device pointer")
+            if t.dtype != torch.uint8:
+                raise ValueError("scan_device: dev_arena must be torch.uint8, not %s" % t.dtype)
+            if t.device.type != "cuda" or (self.device is not None and t.device.index != self.device):
+                raise ValueError("scan_device: dev_arena is on %s, the scanner on device %s" % (t.device, self.device))
+            if not t.is_contiguous():
+                raise ValueError("scan_device: dev_arena must be contiguous")
+            ptr, have = t.data_ptr(), t.numel()
+            keep.append(t)
+        if ptr == 0 or ptr % 16 != 0:
+            raise ValueError("scan_device: dev_arena must be 16-B aligned")
+        if have < need:
+            raise ValueError("scan_device: dev_arena holds %d bytes; offsets[-1] + 64 = %d are read" % (have, need))
+        if dev_offsets is None:  # a device copy of the offsets, kept with the batch
+            import torch
+            d_offs = torch.from_numpy(offs.view(np.int64)).to("cuda:%d" % (self.device or 0))
+            keep.append(d_offs)
+            dev_offsets = d_offs.data_ptr()
+        elif not isinstance(dev_offsets, int):
+            keep.append(dev_offsets)
+            dev_offsets = dev_offsets.data_ptr()
+        return ptr, dev_offsets, offs, keep
+
+    def scan_device_async(self, dev_arena, offsets, paths, binary=None, transform=None, dev_offsets=None,
+                          nbytes=None):
+        """scan_device, pipelined (tsg_scan_submit): returns a PendingScan that keeps the tensor and the
+        arrays referenced until .wait()."""
+        ptr, d_offs, offs, keep_dev = self._device_batch(dev_arena, offsets, nbytes, dev_offsets)
+        keep, batch = self._batch(None, offs, paths, binary, ptr, d_offs, transform=transform)
+        h = c.c_void_p()
+        rc = self._L.tsg_scan_submit(self._h, c.byref(batch), c.byref(h))
+        if rc != 0:
+            raise RuntimeError("tsg_scan_submit failed: %s" % _lib.last_error(self._L))
+        return PendingScan(self, h, (keep, batch, keep_dev))
+
+    def scan_device(self, dev_arena, offsets, paths, binary=None, transform=None, dev_offsets=None, nbytes=None):
+        """One device-only batch: the bytes are resident in HBM and no host copy exists (tsg_batch with
+        host_arena NULL).  dev_arena: a contiguous torch.uint8 tensor on the scanner's device, or an
+        integer device pointer with nbytes; 16-B aligned, at least offsets[-1] + 64 bytes long
+        (ValueError otherwise).  offsets: the n_files + 1 host offsets; dev_offsets: their device copy
+        (a tensor or a pointer; made here when None).  transform (u8 per file): the arena holds the
+        bytes as read and the analyzer's pre-transform runs on the GPU.  The files that got
+        candidates are fetched for the exact pass: ScanResult.fetch_stats()."""
+        return self.scan_device_async(dev_arena, offsets, paths, binary, transform, dev_offsets, nbytes).wait()
+
+    def set_fetch_sizes(self, stage_bytes: int, direct_bytes: int) -> int:
+        """Device-only batches: the device staging size and the length from which a file is copied
+        straight from the arena (tsg_debug_scanner_fetch; tests)."""
+        self._L.tsg_debug_scanner_fetch.argtypes = [c.c_void_p, c.c_uint64, c.c_uint64]
+        return self._L.tsg_debug_scanner_fetch(self._h, int(stage_bytes), int(direct_bytes))
 
     def set_gpu_findings(self, mode) -> int:
         """Findings of HBM-resident batches on the GPU (materialize.h; True / 1), on the host
@@ -427,6 +515,15 @@ class ScanResult:
         s = _CStats()
         self._sc._L.tsg_result_stats(self._h, c.byref(s))
         return {k: getattr(s, k) for k, _ in s._fields_}
+
+    def fetch_stats(self):
+        """What a device-only batch's scan brought back from HBM (tsg_result_fetch_stats): rounds, files,
+        bytes, direct_files, ms_fetch; all zero for a batch with a host arena."""
+        s = _CFetchStats()
+        s.struct_size = FETCH_STATS_SIZE_V1
+        if self._sc._L.tsg_result_fetch_stats(self._h, c.byref(s)) != 0:
+            raise RuntimeError("tsg_result_fetch_stats failed: %s" % _lib.last_error(self._sc._L))
+        return {k: getattr(s, k) for k, _ in s._fields_ if k != "struct_size"}
 
     def raw(self, lo=None, hi=None):
         p = c.c_void_p()

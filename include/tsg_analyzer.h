@@ -133,6 +133,58 @@ int tsg_collector_file(const tsg_collector* c, uint32_t i, const char** path, ui
 int tsg_collector_submit(tsg_collector* c, tsg_pending** out);
 void tsg_collector_reset(tsg_collector* c);
 
+/* Analyze for files whose bytes exist only in HBM (secret.go:103-150): the
+ * caller holds the bytes as read in a resident arena, and the paths and sizes
+ * on the host.  Required (path, size) runs on the host; the binary gate --
+ * utils.IsBinary over each file's first min(size, 300) bytes -- runs on the GPU
+ * over the arena (trivy_amd/csrc/classify.hip), and only the n_files flags
+ * come back.  Versioned like tsg_batch_ext: struct_size first, an unknown size
+ * is refused.  `paths` are AnalysisInput.FilePath (no "/" prefix); the library
+ * adds the prefix for the scan when dir is "" or NULL (a file extracted from an
+ * image, secret.go:130-135).  dev_arena follows the tsg_batch.dev_arena
+ * contract: 16-B aligned, 64 readable bytes past host_offsets[n_files]. */
+typedef struct tsg_device_files {
+  uint32_t struct_size, n_files;
+  const void* dev_arena;         /* the bytes as read, resident */
+  const uint64_t* host_offsets;  /* n_files + 1, ascending from 0 */
+  const void* dev_offsets;       /* optional: device copy of host_offsets */
+  const char* const* paths;      /* AnalysisInput.FilePath per file */
+  const uint64_t* path_lens;     /* optional */
+  const char* dir;               /* AnalysisInput.Dir; "" / NULL = image file */
+} tsg_device_files;
+#define TSG_DEVICE_FILES_SIZE_V1 ((uint32_t)(offsetof(tsg_device_files, dir) + sizeof(const char*)))
+
+/* ms_kernel: classify_heads_kernel alone (HIP events); ms_total: the whole
+ * classify call -- offsets upload, kernel, flags read-back, the host's
+ * Required pass and the gate.  required: files Required accepted;
+ * skipped_binary: of those, binary and not .pyc (dropped); pyc: binary .pyc. */
+typedef struct tsg_device_classify_stats {
+  uint32_t struct_size, reserved;
+  uint64_t files, required, skipped_binary, pyc;
+  double ms_kernel, ms_total;
+} tsg_device_classify_stats;
+#define TSG_DEVICE_CLASSIFY_STATS_SIZE_V1 \
+  ((uint32_t)(offsetof(tsg_device_classify_stats, ms_total) + sizeof(double)))
+
+/* Per file: kind_out = the tsg_batch.transform value -- 3 (dropped) when
+ * Required refuses the file or it is binary and not .pyc, 2 for a binary .pyc
+ * (binary_out 1, ScanArgs.Binary), else 1 (binary_out 0).  st is optional.
+ * Argument errors (unknown struct_size; NULL dev_arena, host_offsets or paths;
+ * dev_arena not 16-B aligned; offsets not ascending from 0) return <0 before
+ * any GPU work.  The classify pass runs on a stream of its own and does not
+ * take the scanner's GPU lock. */
+int tsg_analyzer_classify_device(tsg_analyzer* a, const tsg_device_files* f, uint8_t* kind_out, uint8_t* binary_out,
+                                 tsg_device_classify_stats* st);
+/* Classify, then tsg_scan_submit of the device-only batch (host_arena NULL)
+ * with the computed transform and binary flags and the scan paths.  The same
+ * argument errors, returned here; everything after them runs on the pending's
+ * thread, so several submits may be in flight.  The library owns what it built
+ * (kinds, flags, path strings) until tsg_scan_wait returns; the caller's
+ * buffers -- the struct's arrays, not the struct -- stay borrowed until then.
+ * Result file i is the caller's file i; Analyze's nil is a file whose result
+ * kind is not 2. */
+int tsg_analyzer_submit_device(tsg_analyzer* a, const tsg_device_files* f, tsg_pending** out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,10 +28,18 @@ void tsg_debug_regex_engine(int mode);
 /* The GPU pre-transform (trivy_amd/csrc/xform.hip) on a host batch, on HIP
  * device `device`: out receives the transformed arena (up to out_cap bytes),
  * xoff the n_files + 1 transformed offsets.  kinds per file: 0 as is, 1 CR
- * strip (secret.go:121), 2 ExtractPrintableBytes (utils.go:128-160).  Tests
- * compare it with the oracle's transforms byte for byte. */
+ * strip (secret.go:121), 2 ExtractPrintableBytes (utils.go:128-160), 3 dropped
+ * (no bytes).  Tests compare it with the oracle's transforms byte for byte. */
 int tsg_debug_xform(int device, const uint8_t* raw, uint64_t n_bytes, const uint64_t* offsets, uint32_t n_files,
                     const uint8_t* kinds, uint8_t* out, uint64_t out_cap, uint64_t* xoff);
+/* The analyzer's binary gate on the GPU (trivy_amd/csrc/classify.hip) on a host
+ * batch, on HIP device `device`: the n_bytes of raw are uploaded followed by 64
+ * bytes of 0x00 (the arena's readable tail; NUL is a byte IsBinary rejects, so
+ * a kernel that let the tail reach a flag shows up), the kernel runs, and flags
+ * receives one byte per file: utils.IsBinary (utils.go:85-103) over the file's
+ * first min(size, 300) bytes. */
+int tsg_debug_classify(int device, const uint8_t* raw, uint64_t n_bytes, const uint64_t* offsets, uint32_t n_files,
+                       uint8_t* flags);
 /* regexp.MatchString: 1 = match, 0 = no match, <0 = compile error. */
 int tsg_regex_match(const char* pattern, const uint8_t* text, uint64_t n);
 

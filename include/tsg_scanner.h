@@ -112,7 +112,11 @@ typedef struct tsg_batch {
   const uint8_t* binary;         /* optional ScanArgs.Binary per file */
   /* optional, per file: the analyzer's pre-scan transform, run on the GPU:
    * 0 as is, 1 every '\r' removed (secret.go:121), 2
-   * utils.ExtractPrintableBytes (.pyc, secret.go:112-117, utils.go:128-160).
+   * utils.ExtractPrintableBytes (.pyc, secret.go:112-117, utils.go:128-160),
+   * 3 dropped: a file the analyzer skips (Required false, or binary and not
+   * .pyc, secret.go:108-117) that still lies in the arena -- it contributes no
+   * bytes to the scan, gets no candidates, is never fetched, and its result
+   * is kind 0 (valid for host, gathered and resident batches alike).
    * host_arena / host_offsets then hold the bytes as read.  With dev_arena
    * the bytes as read are resident: dev_arena holds them, host_offsets lays
    * them out as read, and host_arena is NULL or holds the same bytes. */

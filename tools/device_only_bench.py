@@ -13,7 +13,14 @@ fetched from HBM), `--steps` scans of each in all, in one process on one scanner
       ms_gpu_total + ms_fetch - the device-only ms per step, clamped to [0, ms_fetch]
       (0: every fetch extended its step by its whole length; ms_fetch: it was hidden).
 
-Usage: python tools/device_only_bench.py [--gb 4] [--steps 20] [--warmup 5] [--depth 3] [--out FILE]
+--analyze: the analyzer on the same generator's corpus as read (CRLF files not stripped) resident
+in HBM -- blocks of scan_device with caller-supplied kinds and binary flags (computed once, by
+ClassifyDevice) alternate with blocks of AnalyzeDevice, which classifies every step.  Printed:
+ms of classify_heads_kernel (HIP events) and of the whole classify call (offsets, kernel,
+read-back, the host's Required pass), ms per step of both modes, and the kernel's traffic bound
+(320 B per file plus the offsets).
+
+Usage: python tools/device_only_bench.py [--gb 4] [--steps 20] [--warmup 5] [--depth 3] [--analyze] [--out FILE]
 """
 import argparse
 import json
@@ -35,7 +42,10 @@ def main():
     ap.add_argument("--block", type=int, default=5, help="scans of one mode before the other takes its turn")
     ap.add_argument("--depth", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--analyze", action="store_true", help="the AnalyzeDevice leg instead of mirrored / device-only")
     args = ap.parse_args()
+    if args.analyze:
+        return analyze_leg(args)
 
     import torch
     import trivy_amd.secret as secret
@@ -112,6 +122,95 @@ def main():
         "ms_fetch": ms_fetch,
         "fetch_gbps": med([f["bytes"] for f in fetch]) / 1e6 / ms_fetch if ms_fetch > 0 else 0.0,
         "overlap_ms": max(0.0, min(ms_fetch, ms_gpu + ms_fetch - ms_d)),
+        "candidates": int(stats[True][-1]["candidates"]), "findings": int(findings[True]),
+    }
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+
+
+def analyze_leg(args):
+    import torch
+    import trivy_amd.secret as secret
+    from trivy_amd import corpus
+    from trivy_amd.analyzer import SecretAnalyzer
+
+    R = corpus.generate(int(args.gb * 1e9), seed=corpus.SEED, crlf_share=0.05)  # the bytes as read
+    dev = torch.device("cuda", 0)
+    d_arena = torch.from_numpy(R.arena).to(dev)
+    d_offs = torch.from_numpy(R.offsets.view(np.int64)).to(dev)
+    torch.cuda.synchronize()
+    sc = secret.NewScanner(None, device=0, calibration=R.arena[:min(R.n_bytes, 16_000_000)])
+    an = SecretAnalyzer(sc)
+    classify = []
+    for _ in range(args.warmup + 5):
+        st = {}
+        kinds, binary = an.ClassifyDevice(d_arena, R.offsets, R.path_ptrs, "/corpus", dev_offsets=d_offs, stats=st)
+        classify.append(st)
+    classify = classify[args.warmup:]
+
+    def submit(analyze):
+        if analyze:
+            return an.AnalyzeDeviceAsync(d_arena, R.offsets, R.path_ptrs, "/corpus", dev_offsets=d_offs)
+        return sc.scan_device_async(d_arena, R.offsets, R.path_ptrs, binary=binary, transform=kinds, dev_offsets=d_offs)
+
+    def block(analyze, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        inflight, st, fs = [], [], []
+
+        def take(p):
+            r = p.wait(False) if analyze else p.wait()
+            st.append(r.stats())
+            fs.append(r.fetch_stats())
+        for _ in range(n):
+            inflight.append(submit(analyze))
+            if len(inflight) >= args.depth:
+                take(inflight.pop(0))
+        while inflight:
+            take(inflight.pop(0))
+        return time.perf_counter() - t0, st, fs
+
+    for mode in (False, True):
+        block(mode, args.warmup)
+    per = {False: [], True: []}
+    stats = {False: [], True: []}
+    fetch = {False: [], True: []}
+    done = 0
+    while done < args.steps:
+        n = min(args.block, args.steps - done)
+        for mode in (False, True):
+            s, st, fs = block(mode, n)
+            per[mode].append(1e3 * s / n)
+            stats[mode] += st
+            fetch[mode] += fs
+        done += n
+    findings = {m: stats[m][-1]["findings"] for m in (False, True)}
+    assert findings[False] == findings[True], findings
+
+    def med(xs):
+        return float(statistics.median(xs))
+
+    n_files = int(R.n_files)
+    bound = 320 * n_files + 8 * (n_files + 1)
+    ms_k = med([c["ms_kernel"] for c in classify])
+    out = {
+        "tool": "device_only_bench --analyze", "gb": R.n_bytes / 1e9, "files": n_files, "steps": args.steps,
+        "block": args.block, "depth": args.depth,
+        "classify_kernel_ms": ms_k, "classify_call_ms": med([c["ms_total"] for c in classify]),
+        "classify_traffic_bound_bytes": bound, "classify_bound_gbps": bound / 1e6 / ms_k if ms_k > 0 else 0.0,
+        "kinds": [int((kinds == k).sum()) for k in range(4)], "binary": int(binary.sum()),
+        "required": int(classify[-1]["required"]), "skipped_binary": int(classify[-1]["skipped_binary"]),
+        "scan_device_ms_per_step": med(per[False]), "analyze_device_ms_per_step": med(per[True]),
+        "scan_device_blocks_ms": per[False], "analyze_device_blocks_ms": per[True],
+        "ms_gpu_total": med([s["ms_gpu_total"] for s in stats[True]]),
+        "ms_xform_kernel": med([s["ms_xform_kernel"] for s in stats[True]]),
+        "fetch_files_per_step": med([f["files"] for f in fetch[True]]),
+        "fetch_bytes_per_step": med([f["bytes"] for f in fetch[True]]),
+        "ms_fetch": med([f["ms_fetch"] for f in fetch[True]]),
         "candidates": int(stats[True][-1]["candidates"]), "findings": int(findings[True]),
     }
     line = json.dumps(out)

@@ -28,6 +28,8 @@ import time
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
 
+import numpy as np
+
 from .. import _lib
 from ..secret import NewScanner, ParseConfig, Secret
 from ..secret.scanner import ScanResult
@@ -43,9 +45,31 @@ class _CTarStats(c.Structure):
                                           "whiteouts", "opaque_dirs", "input_bytes")]
 
 
+class _CDeviceFiles(c.Structure):  # tsg_device_files (versioned: struct_size first)
+    _fields_ = [("struct_size", c.c_uint32), ("n_files", c.c_uint32), ("dev_arena", c.c_void_p),
+                ("host_offsets", c.c_void_p), ("dev_offsets", c.c_void_p), ("paths", c.c_void_p),
+                ("path_lens", c.c_void_p), ("dir", c.c_char_p)]
+
+
+DEVICE_FILES_SIZE_V1 = _CDeviceFiles.dir.offset + c.sizeof(c.c_char_p)
+
+
+class _CDeviceClassifyStats(c.Structure):  # tsg_device_classify_stats (versioned)
+    _fields_ = [("struct_size", c.c_uint32), ("reserved", c.c_uint32), ("files", c.c_uint64),
+                ("required", c.c_uint64), ("skipped_binary", c.c_uint64), ("pyc", c.c_uint64),
+                ("ms_kernel", c.c_double), ("ms_total", c.c_double)]
+
+
+DEVICE_CLASSIFY_STATS_SIZE_V1 = _CDeviceClassifyStats.ms_total.offset + c.sizeof(c.c_double)
+XFORM_DROP = 3  # tsg_batch.transform: a file the analyzer skips, dropped from the scan
+
+
 def _declare(L):
     if getattr(L, "_tsg_analyzer_declared", False):
         return
+    L.tsg_analyzer_classify_device.argtypes = [c.c_void_p, c.POINTER(_CDeviceFiles), c.c_void_p, c.c_void_p,
+                                               c.POINTER(_CDeviceClassifyStats)]
+    L.tsg_analyzer_submit_device.argtypes = [c.c_void_p, c.POINTER(_CDeviceFiles), c.POINTER(c.c_void_p)]
     L.tsg_is_binary.argtypes = [c.c_char_p, c.c_uint64]
     L.tsg_extract_printable.argtypes = [c.c_char_p, c.c_uint64, c.c_char_p]
     L.tsg_extract_printable.restype = c.c_uint64
@@ -275,6 +299,44 @@ class _ScannerRef:  # what ScanResult needs of its scanner
         self._L = L
 
 
+class PendingDeviceAnalyze:
+    """AnalyzeDeviceAsync in flight (tsg_analyzer_submit_device).  Keeps the arena tensor, the
+    offsets and the paths referenced until wait(): the native thread borrows them."""
+
+    def __init__(self, analyzer, h, paths, image, keep):
+        self._an, self._h, self._paths, self._image, self._keep = analyzer, h, paths, image, keep
+        self.result = None  # the ScanResult, after wait() (fetch_stats(), stats())
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:  # dropped without wait(): join the native thread before the buffers go
+            r = c.c_void_p()
+            self._an._L.tsg_scan_wait(h, c.byref(r))
+            self._h = None
+            if r:
+                self._an._L.tsg_result_free(r)
+
+    def wait(self, materialize: bool = True):
+        """Per file what Analyze returns: an AnalysisResult when it has findings, else None.
+        materialize=False (bench): the ScanResult alone, no per-file objects."""
+        L = self._an._L
+        r = c.c_void_p()
+        rc = L.tsg_scan_wait(self._h, c.byref(r))
+        self._h = None
+        self._keep = None
+        if rc != 0:
+            raise RuntimeError("AnalyzeDevice failed: %s" % _lib.last_error(L))
+        self.result = ScanResult(_ScannerRef(L), r)
+        if not materialize:
+            return self.result
+        paths = self._paths
+        if isinstance(paths, np.ndarray):  # a char* table
+            paths = [c.string_at(int(p)).decode("utf-8", "surrogateescape") for p in paths]
+        if self._image:  # the scan paths: "/" + FilePath for image files (secret.go:130-135)
+            paths = ["/" + p if isinstance(p, str) else b"/" + p for p in paths]
+        return [AnalysisResult(Secrets=[s]) if s.Findings else None for s in self.result.secrets(paths)]
+
+
 def _pipeline(colls, fill, take):
     """Fill the collectors in turn (fill(coll) -> True at the end of the input) and submit
     each batch; with n collectors, n - 1 scans stay in flight while the next batch is
@@ -403,6 +465,66 @@ class SecretAnalyzer:
                 break
         flush()
         return out
+
+    # --- files resident in HBM (no host copy of the bytes) --------------------
+    def _device_files(self, dev_arena, offsets, paths, dir_, dev_offsets, nbytes):
+        """tsg_device_files over a resident arena, checked by Scanner._device_batch (tensor or integer
+        pointer, device, alignment, the 64-byte tail); returns (struct, references to keep)."""
+        if self.scanner is None:
+            raise RuntimeError("the analyzer has no scanner (Init first)")
+        ptr, d_offs, offs, keep = self.scanner._device_batch(dev_arena, offsets, nbytes, dev_offsets)
+        n = len(offs) - 1
+        if len(paths) != n:
+            raise ValueError("AnalyzeDevice: %d paths for %d files" % (len(paths), n))
+        d = _b(dir_ or "")
+        if isinstance(paths, np.ndarray) and paths.dtype == np.uint64:  # a char* table (NUL-terminated strings
+            f = _CDeviceFiles(DEVICE_FILES_SIZE_V1, n, ptr, offs.ctypes.data, d_offs,  # the caller keeps alive)
+                              paths.ctypes.data, None, d)
+            return f, (keep, offs, paths, d)
+        pb = [_b(p) for p in paths]
+        parr = (c.c_char_p * max(1, n))(*pb)
+        plen = np.array([len(p) for p in pb], dtype=np.uint64) if n else np.zeros(1, np.uint64)
+        f = _CDeviceFiles(DEVICE_FILES_SIZE_V1, n, ptr, offs.ctypes.data, d_offs, c.cast(parr, c.c_void_p).value,
+                          plen.ctypes.data, d)
+        return f, (keep, offs, pb, parr, plen, d)
+
+    def ClassifyDevice(self, dev_arena, offsets, paths, dir_="", dev_offsets=None, nbytes=None, stats=None):
+        """What Analyze decides per file before Scan, for files resident in HBM: (kinds, binary) as
+        numpy u8 arrays -- kinds[i] the tsg_batch.transform value (3 dropped: Required false, or binary
+        and not .pyc; 2 a binary .pyc; 1 text), binary[i] ScanArgs.Binary.  The binary gate runs on
+        the GPU over the arena (tsg_analyzer_classify_device); stats (a dict) gets the call's counters."""
+        f, keep = self._device_files(dev_arena, offsets, paths, dir_, dev_offsets, nbytes)
+        kinds = np.zeros(max(1, f.n_files), dtype=np.uint8)
+        binary = np.zeros(max(1, f.n_files), dtype=np.uint8)
+        st = _CDeviceClassifyStats()
+        st.struct_size = DEVICE_CLASSIFY_STATS_SIZE_V1
+        if self._L.tsg_analyzer_classify_device(self._h, c.byref(f), kinds.ctypes.data, binary.ctypes.data,
+                                                c.byref(st)) != 0:
+            raise RuntimeError("tsg_analyzer_classify_device failed: %s" % _lib.last_error(self._L))
+        if stats is not None:
+            stats.update({k: getattr(st, k) for k, _ in st._fields_ if k not in ("struct_size", "reserved")})
+        del keep
+        return kinds[:f.n_files], binary[:f.n_files]
+
+    def AnalyzeDeviceAsync(self, dev_arena, offsets, paths, dir_="", dev_offsets=None,
+                           nbytes=None) -> PendingDeviceAnalyze:
+        """AnalyzeDevice, pipelined (tsg_analyzer_submit_device): several may be in flight; .wait()
+        gives the results.  The pending object keeps the tensors and arrays referenced."""
+        f, keep = self._device_files(dev_arena, offsets, paths, dir_, dev_offsets, nbytes)
+        h = c.c_void_p()
+        if self._L.tsg_analyzer_submit_device(self._h, c.byref(f), c.byref(h)) != 0:
+            raise RuntimeError("tsg_analyzer_submit_device failed: %s" % _lib.last_error(self._L))
+        return PendingDeviceAnalyze(self, h, paths, not dir_, (keep, f, dev_arena, dev_offsets))
+
+    def AnalyzeDevice(self, dev_arena, offsets, paths, dir_="", dev_offsets=None,
+                      nbytes=None) -> List[Optional[AnalysisResult]]:
+        """Analyze (secret.go:103-150) for files whose bytes exist only in HBM: dev_arena holds them as
+        read, back to back (a torch.uint8 tensor on the scanner's device or an integer pointer with
+        nbytes; 16-B aligned, 64 readable bytes past offsets[-1]), offsets / paths are on the host.
+        Required runs on the host, IsBinary over the heads on the GPU; skipped files are dropped from
+        the scan where they lie, .pyc binaries and CRLF text are transformed on the GPU, and only the
+        files that got candidates come back for the exact pass.  Shaped like AnalyzeBatch."""
+        return self.AnalyzeDeviceAsync(dev_arena, offsets, paths, dir_, dev_offsets, nbytes).wait()
 
     def AnalyzeFS(self, root: str, opt=None, arena_bytes: int = 256 << 20, stats: Optional[dict] = None,
                   materialize: bool = True, colls: Optional[List["Collector"]] = None,

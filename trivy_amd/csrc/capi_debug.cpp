@@ -6,6 +6,7 @@
 #include <cstring>
 #include <string>
 
+#include "classify.h"
 #include "goregex.h"
 #include "parallel.h"
 #include "xform.h"
@@ -86,6 +87,43 @@ int tsg_debug_xform(int device, const uint8_t* raw, uint64_t n_bytes, const uint
   if (s) (void)hipStreamDestroy(s);
   if (e != hipSuccess) {
     tsg::SetError(std::string("tsg_debug_xform: ") + hipGetErrorString(e));
+    return -1;
+  }
+  return 0;
+}
+
+int tsg_debug_classify(int device, const uint8_t* raw, uint64_t n_bytes, const uint64_t* offsets, uint32_t n_files,
+                       uint8_t* flags) {
+  if (!offsets || offsets[0] != 0 || offsets[n_files] != n_bytes) {
+    tsg::SetError("offsets must run from 0 to n_bytes");
+    return -2;
+  }
+  for (uint32_t f = 0; f < n_files; f++)
+    if (offsets[f + 1] < offsets[f]) {
+      tsg::SetError("offsets must ascend");
+      return -2;
+    }
+  void *d_raw = nullptr, *d_off = nullptr, *d_flags = nullptr;
+  hipStream_t s = nullptr;
+  hipError_t e = hipSetDevice(device);
+  auto ok = [&](hipError_t r) {
+    if (e == hipSuccess) e = r;
+    return e == hipSuccess;
+  };
+  if (ok(e) && ok(hipStreamCreate(&s)) && ok(hipMalloc(&d_raw, n_bytes + 64)) &&
+      ok(hipMalloc(&d_off, (size_t(n_files) + 1) * 8)) && ok(hipMalloc(&d_flags, size_t(n_files) + 1)) &&
+      ok(hipMemset(d_raw, 0, n_bytes + 64)) && ok(hipMemcpy(d_raw, raw, n_bytes, hipMemcpyHostToDevice)) &&
+      ok(hipMemcpy(d_off, offsets, (size_t(n_files) + 1) * 8, hipMemcpyHostToDevice)) &&
+      ok(hipMemset(d_flags, 0xEE, size_t(n_files) + 1)) &&  // (a flag the kernel leaves unwritten shows up)
+      ok(tsg::ClassifyHeads(static_cast<const uint8_t*>(d_raw), static_cast<const uint64_t*>(d_off), n_files,
+                            static_cast<uint8_t*>(d_flags), s)) &&
+      ok(hipStreamSynchronize(s)))
+    ok(hipMemcpy(flags, d_flags, n_files, hipMemcpyDeviceToHost));
+  for (void* p : {d_raw, d_off, d_flags})
+    if (p) (void)hipFree(p);
+  if (s) (void)hipStreamDestroy(s);
+  if (e != hipSuccess) {
+    tsg::SetError(std::string("tsg_debug_classify: ") + hipGetErrorString(e));
     return -1;
   }
   return 0;

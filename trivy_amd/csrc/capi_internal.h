@@ -2,6 +2,7 @@
 #pragma once
 #include <memory>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "scanner.h"
@@ -19,6 +20,15 @@ struct tsg_result {
   std::string json_range;  // tsg_result_json_range: the last range asked for
   const tsg::SecretScanner* owner;
   std::unique_ptr<tsg::SecretScanner> owned;  // results of scanners made for one call (oracle hooks)
+};
+
+// A scan on its background thread (tsg_scan_submit; tsg_scan_wait joins and frees it).
+struct tsg_pending {
+  std::thread th;
+  tsg_result* r = nullptr;
+  int rc = 0;
+  std::string err;
+  std::shared_ptr<void> owned;  // what the library built for the batch (tsg_analyzer_submit_device): freed with p
 };
 
 namespace tsg {

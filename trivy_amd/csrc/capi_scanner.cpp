@@ -241,13 +241,6 @@ int tsg_scanner_allow_path(const tsg_scanner* s, const char* path, uint64_t len)
   return s->s->AllowPath(reinterpret_cast<const uint8_t*>(path), size_t(len)) ? 1 : 0;
 }
 
-struct tsg_pending {
-  std::thread th;
-  tsg_result* r = nullptr;
-  int rc = 0;
-  std::string err;
-};
-
 namespace {
 
 // tsg_batch_ext sizes this library reads (tsg_scanner.h): the fields past

@@ -19,6 +19,8 @@ namespace tsg {
 struct TarWalkCache;  // analyzer.cpp: evaluated tar entries indexed ahead of the cursor
 void FreeTarWalkCache(TarWalkCache* w);
 void EndTarWalk(TarWalkCache* w);  // joins the background index of the next window
+struct ClassifyPool;  // analyze_device.cpp: streams and buffers of the classify passes in flight
+void FreeClassifyPool(ClassifyPool* p);
 }
 
 struct tsg_analyzer {
@@ -33,7 +35,13 @@ struct tsg_analyzer {
   // background thread (off by default: the layer buffer must then outlive the
   // call that returned 1, the rule in tsg_analyzer.h).
   bool walk_ahead = false;
-  ~tsg_analyzer() { tsg::FreeTarWalkCache(walk); }
+  // tsg_analyzer_classify_device / _submit_device: made on first use
+  std::mutex classify_mu;
+  tsg::ClassifyPool* classify = nullptr;
+  ~tsg_analyzer() {
+    tsg::FreeTarWalkCache(walk);
+    tsg::FreeClassifyPool(classify);
+  }
 };
 
 struct tsg_collector {

@@ -3792,6 +3792,9 @@ bool GpuEngine::FetchNow(const uint8_t* d_arena, const uint64_t* d_offsets, uint
   out->rounds = 0;
   out->ms_fetch = 0;
   if (P.files == 0) return true;  // nothing to bring back
+  // before its members are passed on below: on a scanner whose first fetch is this one
+  // (a resident batch with a transform, FetchFiles) they do not exist yet
+  if (!EnsureFetchStream()) return false;
   size_t cap = 0;
   void* lease = TakeFetchBuf(size_t(P.total) + 64, &cap);
   if (!lease) {

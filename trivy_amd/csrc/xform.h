@@ -9,6 +9,9 @@
 namespace tsg {
 
 constexpr uint8_t kXformNone = 0, kXformStripCR = 1, kXformPrintable = 2;
+// A dropped file: it contributes no bytes to the transformed arena (xoff[f + 1]
+// == xoff[f]), so it gets no candidates and its result is kind 0.
+constexpr uint8_t kXformDrop = 3;
 
 // Flat transform of a batch (n_files + 1 offsets into raw; raw has 64
 // readable bytes past n_bytes).  XformPlan writes xoff (n_files + 1 entries:
@@ -36,7 +39,7 @@ uint32_t XformErrorWord(uint64_t n_bytes, uint32_t n_files, const void* scratch,
 const uint32_t* XformErrorPtr(uint64_t n_bytes, uint32_t n_files, const void* scratch);
 // Upper bound of a batch's transformed size: the strip only drops bytes, the
 // printable extraction replaces a byte by '\n' where it closes a run and adds one
-// '\n' per file at most (a run reaching the file's end).
+// '\n' per file at most (a run reaching the file's end); a dropped file adds nothing.
 inline uint64_t XformMaxOut(uint64_t n_bytes, uint32_t n_files) { return n_bytes + n_files; }
 // dst[dst_off[i] ..) = src[xoff[files[i]] .. xoff[files[i] + 1])
 hipError_t GatherFiles(const uint8_t* src, const uint64_t* xoff, const uint32_t* files, const uint64_t* dst_off,

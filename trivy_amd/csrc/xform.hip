@@ -7,6 +7,8 @@
 //   kind 2  utils.ExtractPrintableBytes (pkg/fanal/utils/utils.go:128-160):
 //           runs of more than 4 unicode.IsPrint bytes, each followed by '\n'
 //           (.pyc binaries, secret.go:112-117)
+//   kind 3  dropped: the file contributes no bytes (a file the analyzer skips:
+//           Required false, or binary and not .pyc, secret.go:108-117)
 // Byte-parallel (see the kernels' comment below): every output byte depends
 // on at most 5 input bytes before it and 4 after it, so a lane per 16-B block
 // computes its block's output with no per-file serial pass; two passes
@@ -89,7 +91,8 @@ __device__ __forceinline__ uint32_t wave_excl(uint32_t v, uint32_t lane) {  // e
 //     bytes of the file cover it; a non-printable byte emits the '\n' that
 //     closes the run before it iff the 5 bytes before it are printable; the
 //     file's last byte emits the closing '\n' of a run reaching the file end
-//     iff the last 5 bytes are printable (utils.go:128-160).
+//     iff the last 5 bytes are printable (utils.go:128-160);
+//   kind 3: no byte is kept.
 // A lane owns one 16-B block, a wave one 1-KiB tile.  Per file segment of the
 // block the rule is evaluated as 16-bit masks (keep, '\n' before, '\n' after);
 // pass 1 counts each tile's output bytes and records where each file starts
@@ -256,8 +259,8 @@ __device__ __forceinline__ void x_stage_files(Pos* so, uint8_t* sk, const XFileR
 }
 
 // An identity tile, decided from the tile's bytes and its staged file table
-// alone (no per-block segment walk): no '\r' in the tile, no kind-2 file
-// starting in it or holding its first byte, at most 64 files starting in it,
+// alone (no per-block segment walk): no '\r' in the tile, no kind-2 or kind-3
+// file starting in it or holding its first byte, at most 64 files starting in it,
 // and no file starting exactly at its first byte (empty files before that one
 // are named by no staged entry).  Its output is its input: the count is its
 // length and a file starting in it starts at the same tile offset.
@@ -277,7 +280,7 @@ __device__ __forceinline__ bool x_fast_identity(const uint4& v, const XFileRegs<
                                                 Pos tend) {
   const uint32_t cr = eq_bytes(v.x, 0x0D0D0D0Du) | eq_bytes(v.y, 0x0D0D0D0Du) | eq_bytes(v.z, 0x0D0D0D0Du) |
                       eq_bytes(v.w, 0x0D0D0D0Du);
-  const bool k2 = fr.o < tend && fr.k == kXformPrintable;  // file tf + lane holds bytes of the tile
+  const bool k2 = fr.o < tend && fr.k >= kXformPrintable;  // file tf + lane (kind 2 or 3) holds bytes of the tile
   const bool many = fr.o64 < tend;                          // file tf + 64 starts in the tile
   const bool edge = x_lane0(fr.o) == t0 && tf > 0;         // lane 0's file: the one holding byte t0
   return !__any(cr != 0u || k2) && !many && !edge;
@@ -312,9 +315,9 @@ __device__ __forceinline__ uint32_t x_lane(Pos n_bytes, const XFiles<Pos>& T, ui
   for (;;) {
     if (fs >= blk && fs < bend) start(f, cnt);
     const uint32_t s = fs > blk ? uint32_t(fs - blk) : 0u, e = uint32_t((fe < bend ? fe : bend) - blk);  // the segment, block bits
-    if (s < e) {
+    const uint32_t k = T.K(f);
+    if (s < e && k != kXformDrop) {  // (a kind-3 file's segment emits nothing)
       const uint32_t seg = ((1u << e) - 1u) & ~((1u << s) - 1u);
-      const uint32_t k = T.K(f);
       if (k == 0) {
         out(seg, 0u, 0u);
         cnt += uint32_t(__popc(seg));
@@ -350,7 +353,7 @@ __global__ __launch_bounds__(kXThreads) void xf_count_kernel(const uint8_t* __re
   const uint32_t n_tiles = uint32_t((n_bytes + kXTile - 1) / kXTile);
   const uint32_t waves = gridDim.x * (kXThreads / 64);
   // The tiles xf_count_fast_kernel left (tile_fast[t] == 0: a '\r', a kind-2
-  // file, an empty file at the tile start, > 64 file starts, the arena's partial
+  // or kind-3 file, an empty file at the tile start, > 64 file starts, the arena's partial
   // last tile).
   __shared__ Pos s_fo[kXThreads / 64][65];
   __shared__ uint8_t s_fk[kXThreads / 64][64];

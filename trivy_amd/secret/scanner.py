@@ -304,8 +304,8 @@ class Scanner:
 
     def _batch(self, arena, offsets, paths, binary, dev_arena, dev_offsets, dev_paths=None, dev_path_offsets=None,
                transform=None):
-        """transform: per-file pre-transform kinds (uint8; 1 = CR strip, 2 = printable runs) run on the
-        GPU over the host arena (the bytes as read)."""
+        """transform: per-file pre-transform kinds (uint8; 1 = CR strip, 2 = printable runs, 3 = the file
+        is dropped from the scan) run on the GPU over the host arena (the bytes as read)."""
         n = len(offsets) - 1
         if arena is None and dev_arena is None:
             raise ValueError("a batch needs arena, dev_arena or both")

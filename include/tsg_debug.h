@@ -114,10 +114,57 @@ int tsg_debug_scanner_gpu_findings(struct tsg_scanner* s, int mode);
  * and the length from which a file is copied straight from the arena instead
  * (defaults: TSG_FETCH_STAGE_MB, 256, and TSG_FETCH_DIRECT_MB, 8, read at scanner
  * creation).  stage_bytes is rounded down to the packing granule (16 KiB, at
- * least one); both take effect with the next scan.  Returns -1 for a scanner
+ * least one; in windows mode 256 B, at least one); both take effect with the next scan.  Returns -1 for a scanner
  * without a GPU engine.  (Tests reach several rounds and the direct route on
  * kilobyte inputs with it.) */
 int tsg_debug_scanner_fetch(struct tsg_scanner* s, uint64_t stage_bytes, uint64_t direct_bytes);
+
+/* ---- the windows fetch of device-only batches (trivy_amd/csrc/fetch_layout.h) ----
+ * FindAll over a piece of a text: the engine is handed bytes [lo, hi) of text
+ * alone (a copy in a block of exactly that size) with the text's true length;
+ * windows and results are relative to the text.  *hit_limit: 1 when the answer
+ * could depend on a byte outside the piece (Regex::FindAllBounded, goregex.h),
+ * the matches written are then not to be used.  Otherwise as tsg_regex_find_all. */
+int tsg_regex_find_all_bounded(const char* pattern, const uint8_t* text, uint64_t true_len, uint64_t lo, uint64_t hi,
+                               int submatch, const int64_t* windows, uint32_t n_windows, int64_t* out,
+                               uint64_t out_cap, uint64_t* out_len, int32_t* num_cap, int32_t* hit_limit);
+/* The host's plan of a windows fetch (fetch_host.h PlanWindowsOnHost) for the
+ * given offsets and candidates (64-B Candidate records, engine.h).  rule_max_len:
+ * one u32 per rule, 0xFFFFFFFF unbounded.  opts: {back, fwd_bytes, fwd_cap,
+ * max_span}, 0 (or opts NULL) the default; back below 4 is refused.  runs:
+ * (first granule, end granule, packed byte offset) triples; views: (file,
+ * lo, hi, packed byte offset) quads, the file-relative pieces of every file in
+ * file order; totals: granules, runs, whole files, packed bytes.  Up to the caps
+ * are written, *n_runs / *n_views receive the full counts. */
+int tsg_debug_fetch_windows_plan(const uint64_t* offsets, uint32_t n_files, const void* cands, uint64_t n_cands,
+                                 const uint32_t* rule_max_len, uint32_t n_rules, const uint32_t* opts, uint64_t* runs,
+                                 uint64_t runs_cap, uint64_t* n_runs, uint64_t* views, uint64_t views_cap,
+                                 uint64_t* n_views, uint64_t totals[4]);
+/* The same marking, ranking and packing on HIP device `device`
+ * (fetch_windows.hip): the batch is uploaded into an allocation of exactly
+ * n_bytes + 64 (the tail 0xEE), the candidate buffer holds min(n_cands,
+ * cand_cap) records while the device count says n_cands (an overflowed list),
+ * and the packed layout comes back through a staging buffer of stage_bytes
+ * (rounded down to 256, at least 256) zeroed before each round.  counters:
+ * granules, runs, whole files, rounds. */
+int tsg_debug_fetch_windows_device(int device, const uint8_t* arena, uint64_t n_bytes, const uint64_t* offsets,
+                                   uint32_t n_files, const void* cands, uint64_t n_cands, uint32_t cand_cap,
+                                   const uint32_t* rule_max_len, uint32_t n_rules, const uint32_t* opts,
+                                   uint64_t stage_bytes, uint8_t* packed, uint64_t packed_cap, uint64_t counters[4]);
+
+/* The windows fetch's host side on a host batch, without a GPU (SecretScanner::SparseTail):
+ * the windows of the given candidates (64-B Candidate records) are planned, each run of marked
+ * granules is copied into a heap block of exactly its size, the sparse exact pass runs on those
+ * blocks alone, the files it cannot answer are rescanned whole from the host arena, and the
+ * findings are made by the host from the whole bytes (the stand-in for the GPU findings pass).
+ * opts as tsg_debug_fetch_windows_plan's.  The result compares with tsg_debug_host_tail_cands
+ * (oracle/native/tsg_oracle.h) on the same candidates. */
+struct tsg_batch;
+struct tsg_result;
+struct tsg_fetch_window_stats;
+int tsg_debug_sparse_tail(const struct tsg_global* g, const struct tsg_batch* batch, const void* cands,
+                          uint64_t n_cands, const uint32_t* opts, struct tsg_result** out,
+                          struct tsg_fetch_window_stats* window_stats);
 
 /* Thread-local text of the last error. */
 const char* tsg_last_error(void);

@@ -90,7 +90,9 @@ int tsg_scanner_allow_path(const tsg_scanner* s, const char* path, uint64_t len)
  *                               of the bytes exists.  The GPU scans dev_arena and the
  *                               files that got candidates -- only those, whole -- are
  *                               copied back to pinned host memory for the exact pass
- *                               (tsg_result_fetch_stats says how much);
+ *                               (tsg_result_fetch_stats says how much); in windows mode
+ *                               (tsg_scanner_set_fetch_options) only the bytes around
+ *                               the candidates are;
  *   gather_base (tsg_batch_ext) host_arena NULL, the files in mapped host memory.
  * host_arena NULL with neither dev_arena nor gather_base is an argument error
  * (status <0 before any GPU work), as is gather_base together with dev_arena.
@@ -250,6 +252,60 @@ typedef struct tsg_fetch_stats {
 } tsg_fetch_stats;
 #define TSG_FETCH_STATS_SIZE_V1 ((uint32_t)(offsetof(tsg_fetch_stats, ms_fetch) + sizeof(double)))
 int tsg_result_fetch_stats(const tsg_result* r, tsg_fetch_stats* out);
+
+/* How a device-only batch's bytes come back for the exact pass (versioned: the
+ * caller sets struct_size, an unknown size is refused).
+ *   TSG_FETCH_FILES (the default)  the files that got candidates, whole;
+ *   TSG_FETCH_WINDOWS              the 256-B granules of the arena around each
+ *     candidate: back_bytes before its window (default 16, at least 4: the regex
+ *     engine looks back one rune), and after it the rule's longest match + 4
+ *     where that is bounded and at most fwd_cap (default 4096), else fwd_bytes
+ *     (default 1024); a window wider than max_span (default 65536), or a span
+ *     that covers its file anyway, brings the whole file.  The exact pass runs
+ *     on those bytes and notices when an answer could depend on a byte it was
+ *     not given; such a file is then fetched whole (the fallback), so results
+ *     never depend on these numbers -- only how much is fetched does.  The
+ *     findings' lines are read from the resident arena by the GPU findings pass.
+ * A field given as 0 means its default.  Windows apply to untransformed
+ * device-only batches (host_arena NULL, dev_arena set, no transform); a batch
+ * with a transform keeps the files fetch whatever the mode (its transformed
+ * bytes are not resident as a whole) and reports mode_used 0.  The options take
+ * effect with the next submitted scan.  TSG_FETCH_MODE=windows at scanner
+ * creation sets the initial mode.  Unknown struct_size, mode > 1 and
+ * back_bytes in 1..3 are argument errors (<0, with a text). */
+#define TSG_FETCH_FILES 0u
+#define TSG_FETCH_WINDOWS 1u
+typedef struct tsg_fetch_options {
+  uint32_t struct_size;
+  uint32_t mode;
+  uint32_t back_bytes;
+  uint32_t fwd_bytes;
+  uint32_t fwd_cap;
+  uint32_t max_span;
+} tsg_fetch_options;
+#define TSG_FETCH_OPTIONS_SIZE_V1 ((uint32_t)(offsetof(tsg_fetch_options, max_span) + sizeof(uint32_t)))
+int tsg_scanner_set_fetch_options(tsg_scanner* s, const tsg_fetch_options* opt);
+/* The effective values (defaults filled in). */
+int tsg_scanner_get_fetch_options(const tsg_scanner* s, tsg_fetch_options* out);
+
+/* What the windows fetch of a scan did.  mode_used: 1 when the batch went the
+ * windows route, 0 otherwise (a host arena, a transform, or the mode off) --
+ * the other fields are then zero.  granules / runs: the 256-B granules fetched
+ * and the contiguous pieces they form; window_bytes = granules * 256;
+ * sparse_files: files answered from their pieces; whole_files: files with
+ * candidates whose every byte came back with the windows; fallback_files / fallback_bytes / ms_fallback: files
+ * fetched whole afterwards because the pieces did not answer them.
+ * tsg_result_fetch_stats then counts, in files, the files of which any byte came
+ * back, in bytes everything copied (window_bytes + fallback_bytes), in rounds the
+ * staging rounds, in direct_files the fallback files that took the direct route. */
+typedef struct tsg_fetch_window_stats {
+  uint32_t struct_size;
+  uint32_t mode_used;
+  uint64_t granules, runs, window_bytes, sparse_files, whole_files, fallback_files, fallback_bytes;
+  double ms_fallback;
+} tsg_fetch_window_stats;
+#define TSG_FETCH_WINDOW_STATS_SIZE_V1 ((uint32_t)(offsetof(tsg_fetch_window_stats, ms_fallback) + sizeof(double)))
+int tsg_result_fetch_window_stats(const tsg_result* r, tsg_fetch_window_stats* out);
 
 /* Page-lock a caller's host buffer (hipHostRegister) so batches in it stream
  * to the GPU asynchronously (the engine's staging ring: copies of this and of

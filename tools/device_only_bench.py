@@ -20,7 +20,14 @@ ms of classify_heads_kernel (HIP events) and of the whole classify call (offsets
 read-back, the host's Required pass), ms per step of both modes, and the kernel's traffic bound
 (320 B per file plus the offsets).
 
-Usage: python tools/device_only_bench.py [--gb 4] [--steps 20] [--warmup 5] [--depth 3] [--analyze] [--out FILE]
+--fetch windows: three modes interleaved in the same way -- mirrored, device-only with the files
+fetch, device-only with the windows fetch (Scanner.set_fetch_mode, --fwd / --fwd-cap / --back) --
+and, for the windows mode, the window stats per step (granules, runs, window bytes, sparse / whole /
+fallback files and the fallback's share of the files with candidates, ms_fallback) beside the fetch
+stats of both device-only modes.
+
+Usage: python tools/device_only_bench.py [--gb 4] [--steps 20] [--warmup 5] [--depth 3] [--analyze]
+                                         [--fetch windows [--fwd N] [--fwd-cap N] [--back N]] [--out FILE]
 """
 import argparse
 import json
@@ -43,9 +50,16 @@ def main():
     ap.add_argument("--depth", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--analyze", action="store_true", help="the AnalyzeDevice leg instead of mirrored / device-only")
+    ap.add_argument("--fetch", choices=["files", "windows"], default="files",
+                    help="windows: the three-mode leg (mirrored / files fetch / windows fetch)")
+    ap.add_argument("--fwd", type=int, default=None)
+    ap.add_argument("--fwd-cap", type=int, default=None)
+    ap.add_argument("--back", type=int, default=None)
     args = ap.parse_args()
     if args.analyze:
         return analyze_leg(args)
+    if args.fetch == "windows":
+        return windows_leg(args)
 
     import torch
     import trivy_amd.secret as secret
@@ -124,6 +138,89 @@ def main():
         "overlap_ms": max(0.0, min(ms_fetch, ms_gpu + ms_fetch - ms_d)),
         "candidates": int(stats[True][-1]["candidates"]), "findings": int(findings[True]),
     }
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+
+
+def windows_leg(args):
+    import torch
+    import trivy_amd.secret as secret
+    from trivy_amd import corpus
+
+    R = corpus.generate(int(args.gb * 1e9), seed=corpus.SEED, crlf_share=0.05)
+    C = R.stripped()
+    del R
+    dev = torch.device("cuda", 0)
+    d_arena = torch.from_numpy(C.arena).to(dev)
+    d_offs = torch.from_numpy(C.offsets.view(np.int64)).to(dev)
+    torch.cuda.synchronize()
+    sc = secret.NewScanner(None, device=0, calibration=C.arena[:min(C.n_bytes, 16_000_000)])
+    MODES = ("mirrored", "files", "windows")
+
+    def submit(mode):
+        if mode == "mirrored":
+            return sc.scan_arena_async(C.arena, C.offsets, C.path_ptrs, dev_arena=d_arena.data_ptr(),
+                                       dev_offsets=d_offs.data_ptr())
+        if mode == "windows":  # (the options hold for the scans submitted from here on)
+            sc.set_fetch_mode("windows", back=args.back, fwd=args.fwd, fwd_cap=args.fwd_cap)
+        else:
+            sc.set_fetch_mode("files")
+        return sc.scan_device_async(d_arena, C.offsets, C.path_ptrs, dev_offsets=d_offs)
+
+    def block(mode, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        inflight, res = [], []
+        for _ in range(n):
+            inflight.append(submit(mode))
+            if len(inflight) >= args.depth:
+                res.append(inflight.pop(0).wait())
+        while inflight:
+            res.append(inflight.pop(0).wait())
+        s = time.perf_counter() - t0
+        return s, [(r.stats(), r.fetch_stats(), r.fetch_window_stats()) for r in res]
+
+    for mode in MODES:
+        block(mode, args.warmup)
+    per = {m: [] for m in MODES}
+    rec = {m: [] for m in MODES}
+    done = 0
+    while done < args.steps:
+        n = min(args.block, args.steps - done)
+        for mode in MODES:
+            s, r = block(mode, n)
+            per[mode].append(1e3 * s / n)
+            rec[mode] += r
+        done += n
+    sc.set_fetch_mode("windows", back=args.back, fwd=args.fwd, fwd_cap=args.fwd_cap)
+    options = sc.fetch_options()  # (the effective values of the windows steps)
+    sc.set_fetch_mode("files")
+    findings = {m: rec[m][-1][0]["findings"] for m in MODES}
+    assert len(set(findings.values())) == 1, findings
+
+    def med(xs):
+        return float(statistics.median(xs))
+
+    out = {"tool": "device_only_bench --fetch windows", "gb": C.n_bytes / 1e9, "files": int(C.n_files),
+           "steps": args.steps, "block": args.block, "depth": args.depth, "options": options,
+           "candidates": int(rec["windows"][-1][0]["candidates"]), "findings": int(findings["windows"])}
+    for m in MODES:
+        out[m + "_ms_per_step"] = med(per[m])
+        out[m + "_blocks_ms"] = per[m]
+        out[m + "_ms_gpu_total"] = med([r[0]["ms_gpu_total"] for r in rec[m]])
+        out[m + "_ms_host_exact"] = med([r[0]["ms_host_exact"] for r in rec[m]])
+    for m in ("files", "windows"):
+        for k in ("files", "bytes", "rounds", "direct_files", "ms_fetch"):
+            out["%s_fetch_%s" % (m, k)] = med([r[1][k] for r in rec[m]])
+    for k in ("granules", "runs", "window_bytes", "sparse_files", "whole_files", "fallback_files", "fallback_bytes",
+              "ms_fallback"):
+        out["windows_" + k] = med([r[2][k] for r in rec["windows"]])
+    with_cands = out["windows_sparse_files"] + out["windows_whole_files"] + out["windows_fallback_files"]
+    out["windows_fallback_share"] = out["windows_fallback_files"] / with_cands if with_cands else 0.0
     line = json.dumps(out)
     print(line)
     if args.out:

@@ -4,9 +4,14 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <vector>
 
+#include "capi_internal.h"
 #include "classify.h"
+#include "fetch_host.h"
+#include "fetch_windows.h"
 #include "goregex.h"
 #include "parallel.h"
 #include "xform.h"
@@ -36,7 +41,7 @@ int tsg_regex_find_all(const char* pattern, const uint8_t* text, uint64_t n, int
   re->FindAll(text, int64_t(n), submatch != 0, windows ? &wins : nullptr, &res);
   *out_len = res.size();
   *num_cap = re->num_cap();
-  std::memcpy(out, res.data(), sizeof(int64_t) * (res.size() < out_cap ? res.size() : out_cap));
+  if (!res.empty()) std::memcpy(out, res.data(), sizeof(int64_t) * (res.size() < out_cap ? res.size() : out_cap));
   return 0;
 }
 
@@ -143,6 +148,230 @@ int64_t tsg_go_bytes_to_lower(const uint8_t* s, uint64_t n, uint8_t* out, uint64
   std::string l = tsg::GoBytesToLower(s, n);
   std::memcpy(out, l.data(), l.size() < out_cap ? l.size() : out_cap);
   return int64_t(l.size());
+}
+
+int tsg_regex_find_all_bounded(const char* pattern, const uint8_t* text, uint64_t true_len, uint64_t lo, uint64_t hi,
+                               int submatch, const int64_t* windows, uint32_t n_windows, int64_t* out,
+                               uint64_t out_cap, uint64_t* out_len, int32_t* num_cap, int32_t* hit_limit) {
+  if (lo > hi || hi > true_len) {
+    tsg::SetError("tsg_regex_find_all_bounded: need lo <= hi <= true_len");
+    return -2;
+  }
+  std::string err;
+  auto re = tsg::Regex::Compile(pattern, &err);
+  if (!re) {
+    tsg::SetError(err);
+    return -1;
+  }
+  std::vector<tsg::Window> wins;
+  for (uint32_t i = 0; i < n_windows; i++) wins.push_back({windows[2 * i], windows[2 * i + 1]});
+  // the engine gets the piece alone, in a block of exactly its size
+  std::unique_ptr<uint8_t[]> piece(new uint8_t[size_t(hi - lo)]);
+  if (hi > lo) std::memcpy(piece.get(), text + lo, size_t(hi - lo));
+  std::vector<int64_t> res;
+  bool hit = false;
+  re->FindAllBounded(piece.get(), int64_t(lo), int64_t(hi), int64_t(true_len), submatch != 0,
+                     windows ? &wins : nullptr, &res, &hit);
+  *out_len = res.size();
+  *num_cap = re->num_cap();
+  *hit_limit = hit ? 1 : 0;
+  if (!res.empty()) std::memcpy(out, res.data(), sizeof(int64_t) * (res.size() < out_cap ? res.size() : out_cap));
+  return 0;
+}
+
+static tsg::FetchWinParams WinParamsOf(const uint32_t* opts) {
+  tsg::FetchWinParams p;
+  if (opts) {
+    if (opts[0]) p.back = opts[0];
+    if (opts[1]) p.fwd_bytes = opts[1];
+    if (opts[2]) p.fwd_cap = opts[2];
+    if (opts[3]) p.max_span = opts[3];
+  }
+  return p;
+}
+
+static bool WinArgsOk(const char* who, const uint64_t* offsets, uint32_t n_files, const uint32_t* opts) {
+  if (!offsets || offsets[0] != 0) {
+    tsg::SetError(std::string(who) + ": offsets must start at 0");
+    return false;
+  }
+  for (uint32_t f = 0; f < n_files; f++)
+    if (offsets[f + 1] < offsets[f]) {
+      tsg::SetError(std::string(who) + ": offsets must ascend");
+      return false;
+    }
+  if (opts && opts[0] && opts[0] < tsg::kFetchBackMin) {
+    tsg::SetError(std::string(who) + ": back_bytes below 4 (the engine looks back one rune)");
+    return false;
+  }
+  return true;
+}
+
+int tsg_debug_fetch_windows_plan(const uint64_t* offsets, uint32_t n_files, const void* cands, uint64_t n_cands,
+                                 const uint32_t* rule_max_len, uint32_t n_rules, const uint32_t* opts, uint64_t* runs,
+                                 uint64_t runs_cap, uint64_t* n_runs, uint64_t* views, uint64_t views_cap,
+                                 uint64_t* n_views, uint64_t totals[4]) {
+  if (!WinArgsOk("tsg_debug_fetch_windows_plan", offsets, n_files, opts)) return -2;
+  tsg::HostWindowPlan P;
+  tsg::PlanWindowsOnHost(static_cast<const tsg::Candidate*>(cands), size_t(n_cands), offsets, n_files, rule_max_len,
+                         n_rules, WinParamsOf(opts), &P);
+  *n_runs = P.runs.size();
+  for (size_t k = 0; k < P.runs.size() && k < runs_cap; k++) {
+    runs[3 * k] = P.runs[k].g0;
+    runs[3 * k + 1] = P.runs[k].g1;
+    runs[3 * k + 2] = P.runs[k].packed;
+  }
+  uint64_t nv = 0;
+  size_t from = 0;
+  std::vector<tsg::FilePiece> v;
+  for (uint32_t f = 0; f < n_files; f++) {
+    v.clear();
+    from = tsg::FileViewOf(P, offsets[f], offsets[f + 1], from, &v);
+    for (const tsg::FilePiece& p : v) {
+      if (nv < views_cap) {
+        views[4 * nv] = f;
+        views[4 * nv + 1] = p.lo;
+        views[4 * nv + 2] = p.hi;
+        views[4 * nv + 3] = p.packed;
+      }
+      nv++;
+    }
+  }
+  *n_views = nv;
+  totals[0] = P.granules;
+  totals[1] = P.runs.size();
+  totals[2] = P.whole_files;
+  totals[3] = P.packed_bytes();
+  return 0;
+}
+
+int tsg_debug_fetch_windows_device(int device, const uint8_t* arena, uint64_t n_bytes, const uint64_t* offsets,
+                                   uint32_t n_files, const void* cands, uint64_t n_cands, uint32_t cand_cap,
+                                   const uint32_t* rule_max_len, uint32_t n_rules, const uint32_t* opts,
+                                   uint64_t stage_bytes, uint8_t* packed, uint64_t packed_cap, uint64_t counters[4]) {
+  if (!WinArgsOk("tsg_debug_fetch_windows_device", offsets, n_files, opts)) return -2;
+  if (offsets[n_files] != n_bytes || n_cands > 0xFFFFFFFFull) {
+    tsg::SetError("tsg_debug_fetch_windows_device: offsets must end at n_bytes");
+    return -2;
+  }
+  stage_bytes = std::max<uint64_t>(stage_bytes / tsg::kFetchGranule, 1) * tsg::kFetchGranule;
+  const uint32_t count = uint32_t(n_cands);
+  const size_t held = size_t(std::min<uint64_t>(n_cands, cand_cap));
+  void *d_arena = nullptr, *d_off = nullptr, *d_cands = nullptr, *d_count = nullptr, *d_ml = nullptr, *d_sc = nullptr,
+       *d_ctr = nullptr, *d_stage = nullptr;
+  hipStream_t s = nullptr;
+  hipError_t e = hipSetDevice(device);
+  auto ok = [&](hipError_t r) {
+    if (e == hipSuccess) e = r;
+    return e == hipSuccess;
+  };
+  tsg::FetchWinCounters ctr = {};
+  const size_t sc_bytes = tsg::FetchWinScratchBytes(n_bytes, n_files);
+  // the arena as the library's callers give it: n_bytes + 64 readable bytes and no more (0xEE: not file bytes)
+  if (ok(e) && ok(hipStreamCreate(&s)) && ok(hipMalloc(&d_arena, n_bytes + 64)) &&
+      ok(hipMalloc(&d_off, (size_t(n_files) + 1) * 8)) && ok(hipMalloc(&d_cands, (held + 1) * sizeof(tsg::Candidate))) &&
+      ok(hipMalloc(&d_count, 4)) && ok(hipMalloc(&d_ml, (size_t(n_rules) + 1) * 4)) && ok(hipMalloc(&d_sc, sc_bytes)) &&
+      ok(hipMalloc(&d_ctr, sizeof ctr)) && ok(hipMalloc(&d_stage, stage_bytes)) &&
+      ok(hipMemset(d_arena, 0xEE, n_bytes + 64)) && ok(hipMemcpy(d_arena, arena, n_bytes, hipMemcpyHostToDevice)) &&
+      ok(hipMemcpy(d_off, offsets, (size_t(n_files) + 1) * 8, hipMemcpyHostToDevice)) &&
+      ok(hipMemcpy(d_cands, cands, held * sizeof(tsg::Candidate), hipMemcpyHostToDevice)) &&
+      ok(hipMemcpy(d_count, &count, 4, hipMemcpyHostToDevice)) &&
+      ok(hipMemcpy(d_ml, rule_max_len, size_t(n_rules) * 4, hipMemcpyHostToDevice)) &&
+      ok(tsg::FetchWinPlan(static_cast<const tsg::Candidate*>(d_cands), static_cast<const uint32_t*>(d_count), cand_cap,
+                           static_cast<const uint64_t*>(d_off), n_files, n_bytes, static_cast<const uint32_t*>(d_ml),
+                           n_rules, WinParamsOf(opts), d_sc, static_cast<tsg::FetchWinCounters*>(d_ctr), s)) &&
+      ok(hipMemcpyAsync(&ctr, d_ctr, sizeof ctr, hipMemcpyDeviceToHost, s)) && ok(hipStreamSynchronize(s))) {
+    const uint64_t total = ctr.granules * tsg::kFetchGranule;
+    uint64_t rounds = 0;
+    for (uint64_t w0 = 0; w0 < total && e == hipSuccess; w0 += stage_bytes, rounds++) {
+      const uint64_t w1 = std::min(w0 + stage_bytes, total);
+      // (the bytes the pack leaves alone -- the last granule's blocks past the arena -- read as 0)
+      if (ok(hipMemsetAsync(d_stage, 0, stage_bytes, s)) &&
+          ok(tsg::FetchWinPack(static_cast<const uint8_t*>(d_arena), n_bytes, d_sc, n_files,
+                               static_cast<const tsg::FetchWinCounters*>(d_ctr), w0, w1, static_cast<uint8_t*>(d_stage),
+                               s)) &&
+          ok(hipStreamSynchronize(s)) && w0 < packed_cap)
+        ok(hipMemcpy(packed + w0, d_stage, std::min(w1, packed_cap) - w0, hipMemcpyDeviceToHost));
+    }
+    counters[0] = ctr.granules;
+    counters[1] = ctr.runs;
+    counters[2] = ctr.whole_files;
+    counters[3] = rounds;
+  }
+  for (void* p : {d_arena, d_off, d_cands, d_count, d_ml, d_sc, d_ctr, d_stage})
+    if (p) (void)hipFree(p);
+  if (s) (void)hipStreamDestroy(s);
+  if (e != hipSuccess) {
+    tsg::SetError(std::string("tsg_debug_fetch_windows_device: ") + hipGetErrorString(e));
+    return -1;
+  }
+  return 0;
+}
+
+int tsg_debug_sparse_tail(const tsg_global* g, const tsg_batch* b, const void* cands, uint64_t n_cands,
+                          const uint32_t* opts, tsg_result** out, tsg_fetch_window_stats* window_stats) {
+  if (!g || !b || !out || !window_stats || !b->host_arena || !b->host_offsets) {
+    tsg::SetError("tsg_debug_sparse_tail: NULL argument (a host batch is required)");
+    return -2;
+  }
+  if (window_stats->struct_size != TSG_FETCH_WINDOW_STATS_SIZE_V1) {
+    tsg::SetError("tsg_debug_sparse_tail: unknown tsg_fetch_window_stats.struct_size");
+    return -2;
+  }
+  if (!WinArgsOk("tsg_debug_sparse_tail", b->host_offsets, b->n_files, opts)) return -2;
+  std::string err;
+  std::vector<tsg::RuleSpec> rules;
+  std::vector<tsg::AllowRuleSpec> allow;
+  std::vector<std::unique_ptr<tsg::Regex>> exclude;
+  if (!tsg::MakeRules(g, &rules, &err) || !tsg::MakeAllow(g->allow_rules, g->n_allow_rules, &allow, &err) ||
+      !tsg::MakeExclude(g->exclude_regexes, g->n_exclude_regexes, &exclude, &err)) {
+    tsg::SetError(err);
+    return -1;
+  }
+  std::unique_ptr<tsg::SecretScanner> sc(
+      new tsg::SecretScanner(std::move(rules), std::move(allow), std::move(exclude), -1, &err));
+  if (!sc->ok()) {
+    tsg::SetError(err.empty() ? sc->error() : err);
+    return -1;
+  }
+  std::vector<tsg::Candidate> cv(n_cands);
+  if (n_cands) std::memcpy(cv.data(), cands, n_cands * sizeof(tsg::Candidate));
+  for (const auto& c : cv)
+    if (c.file >= b->n_files || c.rule >= sc->compiled().rules.size()) {
+      tsg::SetError("candidate out of range");
+      return -3;
+    }
+  tsg::BatchInput in;
+  in.n_files = b->n_files;
+  in.host_arena = b->host_arena;
+  in.host_offsets = b->host_offsets;
+  in.paths = b->paths;
+  in.path_lens = b->path_lens;
+  in.binary = b->binary;
+  std::unique_ptr<tsg_result> r(new tsg_result());
+  tsg::HostStats hs;
+  if (!sc->SparseTail(in, &cv, WinParamsOf(opts), &r->files, &hs, &r->win, &err)) {
+    tsg::SetError(err);
+    return -1;
+  }
+  std::memset(&r->stats, 0, sizeof(r->stats));
+  r->stats.bytes = in.n_files ? in.host_offsets[in.n_files] : 0;
+  r->stats.files = in.n_files;
+  r->stats.findings = hs.findings;
+  r->stats.candidates = hs.candidates;
+  r->owner = sc.get();
+  r->owned = std::move(sc);
+  window_stats->mode_used = r->win.mode_used;
+  window_stats->granules = r->win.granules;
+  window_stats->runs = r->win.runs;
+  window_stats->window_bytes = r->win.window_bytes;
+  window_stats->sparse_files = r->win.sparse_files;
+  window_stats->whole_files = r->win.whole_files;
+  window_stats->fallback_files = r->win.fallback_files;
+  window_stats->fallback_bytes = r->win.fallback_bytes;
+  window_stats->ms_fallback = r->win.ms_fallback;
+  *out = r.release();
+  return 0;
 }
 
 int tsg_debug_pool_budget(void) { return tsg::PoolBudget(); }

@@ -16,6 +16,7 @@ struct tsg_result {
   tsg::BatchResult files;
   tsg_stats stats;
   tsg::FetchStats fetch;  // tsg_result_fetch_stats (device-only batches; zero otherwise)
+  tsg::FetchWindowStats win;  // tsg_result_fetch_window_stats (the windows fetch; zero otherwise)
   std::string json;        // tsg_result_json: every file (built once)
   std::string json_range;  // tsg_result_json_range: the last range asked for
   const tsg::SecretScanner* owner;

@@ -264,6 +264,9 @@ struct ExtFields {  // the fields past tsg_batch that a caller's struct_size cov
   const uint64_t* host_path_off = nullptr;
   const uint8_t* gather_base = nullptr;
   const uint64_t* gather_src = nullptr;
+  // (not a batch field) the scanner's fetch options as they were when the scan was submitted
+  int fetch_windows = -1;
+  tsg::FetchWinParams fetch_prm;
 };
 
 ExtFields ExtOf(const tsg_batch_ext* b) {
@@ -305,8 +308,9 @@ bool CheckBatch(const tsg_batch* b, const ExtFields& x) {
 int tsg_scan_submit_ext(tsg_scanner* s, const tsg_batch_ext* b, tsg_pending** out) {
   if (!CheckExtSize(b)) return -1;
   const tsg_batch bc = b->base;
-  const ExtFields x = ExtOf(b);
+  ExtFields x = ExtOf(b);
   if (!CheckBatch(&bc, x)) return -1;
+  if (s && s->s) x.fetch_windows = s->s->GetFetchOptions(&x.fetch_prm) ? 1 : 0;  // (a later set is for later scans)
   std::unique_ptr<tsg_pending> p(new tsg_pending());
   tsg_pending* pp = p.get();
   pp->th = std::thread([s, bc, x, pp] {
@@ -362,12 +366,14 @@ int ScanImpl(tsg_scanner* s, const tsg_batch* b, const ExtFields& x, tsg_result*
   in.host_path_off = x.host_path_off;
   in.gather_base = x.gather_base;
   in.gather_src = x.gather_src;
+  in.fetch_windows = x.fetch_windows;
+  in.fetch_prm = x.fetch_prm;
   std::unique_ptr<tsg_result> r(new tsg_result());
   r->owner = s->s.get();
   tsg::BatchStats gs;
   tsg::HostStats hs;
   std::string err;
-  if (!s->s->Scan(in, &r->files, &gs, &hs, &err, &r->fetch)) {
+  if (!s->s->Scan(in, &r->files, &gs, &hs, &err, &r->fetch, &r->win)) {
     tsg::SetError(err);
     return -1;
   }
@@ -707,6 +713,77 @@ int tsg_debug_scanner_engine(tsg_scanner* s, uint64_t out[4]) {
     out[2] = std::max<uint64_t>(out[2], m.cand_cap);
     out[3] += m.slot_bytes;
   }
+  return 0;
+}
+
+int tsg_scanner_set_fetch_options(tsg_scanner* s, const tsg_fetch_options* opt) {
+  if (!s || !s->s || !opt) {
+    tsg::SetError("tsg_scanner_set_fetch_options: NULL argument");
+    return -1;
+  }
+  if (opt->struct_size != TSG_FETCH_OPTIONS_SIZE_V1) {
+    tsg::SetError("tsg_scanner_set_fetch_options: tsg_fetch_options.struct_size " + std::to_string(opt->struct_size) +
+                  " is not a size this library knows (v1 = " + std::to_string(TSG_FETCH_OPTIONS_SIZE_V1) + ")");
+    return -1;
+  }
+  if (opt->mode > TSG_FETCH_WINDOWS) {
+    tsg::SetError("tsg_scanner_set_fetch_options: mode " + std::to_string(opt->mode) +
+                  " (0 = files, 1 = windows are the modes)");
+    return -1;
+  }
+  if (opt->back_bytes != 0 && opt->back_bytes < tsg::kFetchBackMin) {
+    tsg::SetError("tsg_scanner_set_fetch_options: back_bytes " + std::to_string(opt->back_bytes) +
+                  " is below 4 (the regex engine looks back one rune)");
+    return -1;
+  }
+  tsg::FetchWinParams p;
+  if (opt->back_bytes) p.back = opt->back_bytes;
+  if (opt->fwd_bytes) p.fwd_bytes = opt->fwd_bytes;
+  if (opt->fwd_cap) p.fwd_cap = opt->fwd_cap;
+  if (opt->max_span) p.max_span = opt->max_span;
+  s->s->SetFetchOptions(opt->mode == TSG_FETCH_WINDOWS, p);
+  return 0;
+}
+
+int tsg_scanner_get_fetch_options(const tsg_scanner* s, tsg_fetch_options* out) {
+  if (!s || !s->s || !out) {
+    tsg::SetError("tsg_scanner_get_fetch_options: NULL argument");
+    return -1;
+  }
+  if (out->struct_size != TSG_FETCH_OPTIONS_SIZE_V1) {
+    tsg::SetError("tsg_scanner_get_fetch_options: tsg_fetch_options.struct_size " + std::to_string(out->struct_size) +
+                  " is not a size this library knows (v1 = " + std::to_string(TSG_FETCH_OPTIONS_SIZE_V1) + ")");
+    return -1;
+  }
+  tsg::FetchWinParams p;
+  out->mode = s->s->GetFetchOptions(&p) ? TSG_FETCH_WINDOWS : TSG_FETCH_FILES;
+  out->back_bytes = p.back;
+  out->fwd_bytes = p.fwd_bytes;
+  out->fwd_cap = p.fwd_cap;
+  out->max_span = p.max_span;
+  return 0;
+}
+
+int tsg_result_fetch_window_stats(const tsg_result* r, tsg_fetch_window_stats* out) {
+  if (!r || !out) {
+    tsg::SetError("tsg_result_fetch_window_stats: NULL argument");
+    return -1;
+  }
+  if (out->struct_size != TSG_FETCH_WINDOW_STATS_SIZE_V1) {
+    tsg::SetError("tsg_result_fetch_window_stats: tsg_fetch_window_stats.struct_size " +
+                  std::to_string(out->struct_size) + " is not a size this library knows (v1 = " +
+                  std::to_string(TSG_FETCH_WINDOW_STATS_SIZE_V1) + ")");
+    return -1;
+  }
+  out->mode_used = r->win.mode_used;
+  out->granules = r->win.granules;
+  out->runs = r->win.runs;
+  out->window_bytes = r->win.window_bytes;
+  out->sparse_files = r->win.sparse_files;
+  out->whole_files = r->win.whole_files;
+  out->fallback_files = r->win.fallback_files;
+  out->fallback_bytes = r->win.fallback_bytes;
+  out->ms_fallback = r->win.ms_fallback;
   return 0;
 }
 

@@ -12,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "fetch_layout.h"
 #include "rules.h"
 
 namespace tsg {
@@ -85,6 +86,14 @@ struct FetchOut {
   uint64_t files = 0, bytes = 0, direct_files = 0;
   uint32_t rounds = 0;   // staging rounds that carried packed bytes
   double ms_fetch = 0;   // plan + pack + copies (HIP events; direct copies by the host clock)
+  // Windows mode (fetch_layout.h): the caller sets want_windows and prm; on return `windows`
+  // says the fetch went that way, and buf then holds the packed granules instead of files:
+  // run k's bytes start at buf + runs[k].packed (off / fetched are unused; fetch_host.h
+  // FileViewOf gives a file's pieces).  whole_marked: files a candidate marked whole.
+  bool want_windows = false, windows = false;
+  FetchWinParams prm;
+  std::vector<GranuleRun> runs;
+  uint64_t granules = 0, whole_marked = 0;
   FetchOut() = default;
   FetchOut(const FetchOut&) = delete;
   FetchOut& operator=(const FetchOut&) = delete;
@@ -222,6 +231,8 @@ class GpuEngine {
     size_t lease_cap = 0;
     uint64_t fetch_copy = 0;          // packed bytes copied back
     uint64_t stage = 0, direct = 0;   // the sizes the fetch was enqueued with
+    bool win = false;                 // a windows fetch (h_fctr then holds FetchWinCounters)
+    FetchWinParams prm;
     const uint8_t* d_arena = nullptr; // (direct copies are issued by Collect)
   };
   static constexpr int kSlots = 4;
@@ -251,6 +262,17 @@ class GpuEngine {
   bool FetchNow(const uint8_t* d_arena, const uint64_t* d_offsets, uint32_t n_files, std::vector<uint8_t> want,
                 bool upload_flags, FetchOut* out);
   void NoteFetch(uint64_t packed, uint64_t total);
+  // windows mode (fetch_windows.h): the same rounds, events, staging buffer and fetch stream
+  bool IssueFetchWin(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
+                     const FetchWinParams& prm, uint64_t stage, uint64_t copy_bytes, uint8_t* h_dst, void* h_ctr,
+                     hipEvent_t ev0);
+  bool FetchNowWin(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
+                   const std::vector<Candidate>& cands, FetchOut* out);
+  std::atomic<uint64_t> fetchw_stage_bytes_{uint64_t(256) << 20};  // SetFetchSizes' stage, rounded to granules
+  std::atomic<uint64_t> fetchw_recent_packed_{0};  // the recent windows fetches' packed bytes (as fetch_recent_packed_)
+  void* d_wscratch_ = nullptr; size_t cap_wscratch_ = 0;
+  uint32_t* d_rule_max_len_ = nullptr;   // RuleGpu::max_len per rule, compact (the marking kernel's fwd reach)
+  std::vector<uint32_t> h_rule_max_len_;
   bool EnsureFetchStream();
   std::atomic<uint64_t> fetch_stage_bytes_{uint64_t(256) << 20}, fetch_direct_bytes_{uint64_t(8) << 20};
   std::atomic<uint64_t> fetch_recent_packed_{0}, fetch_recent_total_{0};

@@ -35,6 +35,7 @@
 #include "engine.h"
 #include "fetch.h"
 #include "fetch_host.h"
+#include "fetch_windows.h"
 #include "xform.h"
 #include "filter.h"
 
@@ -2340,7 +2341,10 @@ GpuEngine::GpuEngine(const CompiledRules& cr, int device) : device_(device) {
     err_ = "too many anchors for the hit records (>= 2^24)";
     return;
   }
+  h_rule_max_len_.resize(cr.rules.size());
+  for (size_t r = 0; r < cr.rules.size(); r++) h_rule_max_len_[r] = cr.rules[r].max_len;
   if (!Upload(&err_, &d_anchors_, cr.anchors.data(), cr.anchors.size()) ||
+      !Upload(&err_, &d_rule_max_len_, h_rule_max_len_.data(), h_rule_max_len_.size()) ||
       !Upload(&err_, &d_rules_, cr.rules.data(), cr.rules.size()) ||
       !Upload(&err_, &d_rule_kw_, cr.rule_kw.data(), cr.rule_kw.size()) ||
       !Upload(&err_, &d_nfa_, cr.nfa.data(), cr.nfa.size()) ||
@@ -2677,7 +2681,7 @@ GpuEngine::~GpuEngine() {
     if (S.h_fctr) hipHostFree(S.h_fctr);
     if (S.lease) hipHostFree(S.lease);
   }
-  for (void* p : {d_fscratch_, d_fstage_, d_fctr_})
+  for (void* p : {d_fscratch_, d_fstage_, d_fctr_, d_wscratch_, static_cast<void*>(d_rule_max_len_)})
     if (p) hipFree(p);
   for (void* h : {h_run_fctr_, h_fflags_})
     if (h) hipHostFree(h);
@@ -3312,7 +3316,18 @@ bool GpuEngine::Enqueue(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t
     if (ok && !S.h_fctr)
       ok = hipHostMalloc(&S.h_fctr, sizeof(FetchCounters), hipHostMallocDefault) == hipSuccess &&
            hipEventCreate(&S.ev_f[0]) == hipSuccess && hipEventCreate(&S.ev_f[1]) == hipSuccess;
-    if (ok) {
+    S.win = fetch->want_windows;
+    S.prm = fetch->prm;
+    if (ok && S.win) {  // pre-sized from the recent windows fetches' packed bytes, kept apart from the files mode's
+      S.stage = fetchw_stage_bytes_.load();
+      S.direct = 0;
+      const uint64_t rp = fetchw_recent_packed_.load();
+      const uint64_t all = FetchGranules(n_bytes) * kFetchGranule;
+      const uint64_t copy = std::min(rp + rp / 8 + std::min<uint64_t>(uint64_t(1) << 20, S.stage), all);
+      S.fetch_copy = (copy + kFetchGranule - 1) / kFetchGranule * kFetchGranule;
+      S.lease = TakeFetchBuf(size_t(S.fetch_copy) + 64, &S.lease_cap);
+      ok = S.lease != nullptr;
+    } else if (ok) {
       S.stage = fetch_stage_bytes_.load();
       S.direct = fetch_direct_bytes_.load();
       // The packed bytes copied back follow the recent scans' (as the candidate
@@ -3334,8 +3349,10 @@ bool GpuEngine::Enqueue(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t
       hipMemcpyAsync(S.h_cands, d_cands_, size_t(n_copy) * sizeof(Candidate), hipMemcpyDeviceToHost, stream_) !=
           hipSuccess ||
       // the fetch right behind: no host round trip between the candidates and its launch
-      (fetch && (!IssueFetch(d_arena, d_offsets, n_files, nullptr, S.direct, S.stage, S.fetch_copy,
-                             static_cast<uint8_t*>(S.lease), S.h_fctr, S.ev_f[0]) ||
+      (fetch && (!(S.win ? IssueFetchWin(d_arena, n_bytes, d_offsets, n_files, S.prm, S.stage, S.fetch_copy,
+                                         static_cast<uint8_t*>(S.lease), S.h_fctr, S.ev_f[0])
+                         : IssueFetch(d_arena, d_offsets, n_files, nullptr, S.direct, S.stage, S.fetch_copy,
+                                      static_cast<uint8_t*>(S.lease), S.h_fctr, S.ev_f[0])) ||
                  hipEventRecord(S.ev_f[1], fetch_stream_) != hipSuccess)) ||
       hipEventRecord(S.done, fetch ? fetch_stream_ : stream_) != hipSuccess) {
     if (err_.empty()) err_ = "Enqueue: HIP call failed";
@@ -3398,7 +3415,46 @@ bool GpuEngine::Collect(Ticket* t, std::vector<Candidate>* cands, BatchStats* st
   for (uint32_t i = 0; i < cnt[1]; i++)  // closed keyword gates (finalize_kernel) never reach the host
     if (!(S.h_cands[i].flags & kCandDrop)) cands->push_back(S.h_cands[i]);
   st->candidates = cands->size();
-  if (S.has_fetch) {
+  if (S.has_fetch && S.win) {  // the windows fetch: the plan restated from the candidates, checked, handed over
+    bool ok = fetch != nullptr && fetch->h_offsets != nullptr;
+    if (!ok) *err = "Collect: the ticket's scan was enqueued with a fetch";
+    if (ok) {
+      HostWindowPlan P;
+      PlanWindowsOnHost(cands->data(), cands->size(), fetch->h_offsets, S.n_files, h_rule_max_len_.data(),
+                        uint32_t(h_rule_max_len_.size()), S.prm, &P);
+      const FetchWinCounters& C = *static_cast<const FetchWinCounters*>(S.h_fctr);
+      ok = SameWindowPlan(C.granules, C.runs, C.whole_files, P, err);
+      if (ok) {
+        const uint64_t packed = P.packed_bytes();
+        const uint64_t rp = fetchw_recent_packed_.load();
+        fetchw_recent_packed_.store(std::max(packed, rp - rp / 8));
+        if (packed > S.fetch_copy || packed + 64 > S.lease_cap) {  // more marked than pre-sized: Run fetches it all
+          *rerun = true;
+          release();
+          return true;
+        }
+        float ms = 0;
+        if (P.granules) hipEventElapsedTime(&ms, S.ev_f[0], S.ev_f[1]);  // (nothing marked: nothing was fetched)
+        fetch->Release();
+        fetch->windows = true;
+        fetch->runs = std::move(P.runs);
+        fetch->granules = P.granules;
+        fetch->whole_marked = P.whole_files;
+        fetch->rounds = uint32_t((packed + S.stage - 1) / S.stage);
+        fetch->ms_fetch = ms;
+        fetch->buf = static_cast<const uint8_t*>(S.lease);
+        fetch->owner = this;
+        fetch->lease = S.lease;
+        fetch->lease_cap = S.lease_cap;
+        S.lease = nullptr;
+        S.lease_cap = 0;
+      }
+    }
+    if (!ok) {
+      release();
+      return false;
+    }
+  } else if (S.has_fetch) {
     bool ok = fetch != nullptr && fetch->h_offsets != nullptr;
     if (!ok) *err = "Collect: the ticket's scan was enqueued with a fetch";
     HostFetchPlan P;
@@ -3711,6 +3767,8 @@ void FetchOut::Release() {
 void GpuEngine::SetFetchSizes(uint64_t stage_bytes, uint64_t direct_bytes) {
   fetch_stage_bytes_.store(std::max<uint64_t>(kFetchSeg, stage_bytes / kFetchSeg * kFetchSeg));
   fetch_direct_bytes_.store(std::max<uint64_t>(1, direct_bytes));
+  // (the windows fetch packs granules: its rounds may be as small as one)
+  fetchw_stage_bytes_.store(std::max<uint64_t>(kFetchGranule, stage_bytes / kFetchGranule * kFetchGranule));
 }
 
 // Pinned fetch buffers (fetch_host.h FetchPool): allocated here, retired through RetireHost.
@@ -3832,6 +3890,96 @@ bool GpuEngine::FetchNow(const uint8_t* d_arena, const uint64_t* d_offsets, uint
   return true;
 }
 
+// Windows mode: marking + ranking + the rounds of packing on the scan stream, the copies of the
+// rounds on the fetch stream -- IssueFetch with fetch_windows.h in the place of fetch.h.  The
+// staging buffer, its two events and the device counter record are the files mode's (one fetch
+// at a time uses them, in stream order).  copy_bytes: a multiple of 256.
+bool GpuEngine::IssueFetchWin(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
+                              const FetchWinParams& prm, uint64_t stage, uint64_t copy_bytes, uint8_t* h_dst,
+                              void* h_ctr, hipEvent_t ev0) {
+  static_assert(sizeof(FetchWinCounters) == sizeof(FetchCounters), "one device record serves both modes");
+  if (!EnsureFetchStream()) return false;
+  const size_t stage_need = size_t(std::max<uint64_t>(std::min(stage, copy_bytes), kFetchGranule));
+  if (d_fstage_ && cap_fstage_ < stage_need) HIP_OK(hipStreamSynchronize(fetch_stream_));  // a copy may read it still
+  if (!Ensure(&d_wscratch_, &cap_wscratch_, FetchWinScratchBytes(n_bytes, n_files)) ||
+      !Ensure(&d_fstage_, &cap_fstage_, stage_need))
+    return false;
+  FetchWinCounters* ctr = static_cast<FetchWinCounters*>(d_fctr_);
+  HIP_OK(hipEventRecord(ev0, stream_));
+  HIP_OK(FetchWinPlan(static_cast<const Candidate*>(d_cands_), d_counters_ + 1, cand_cap_, d_offsets, n_files, n_bytes,
+                      d_rule_max_len_, uint32_t(h_rule_max_len_.size()), prm, d_wscratch_, ctr, stream_));
+  HIP_OK(hipMemcpyAsync(h_ctr, ctr, sizeof(FetchWinCounters), hipMemcpyDeviceToHost, stream_));
+  uint8_t* st = static_cast<uint8_t*>(d_fstage_);
+  for (uint64_t w0 = 0; w0 < copy_bytes; w0 += stage) {
+    const uint64_t w1 = std::min(w0 + stage, copy_bytes);
+    HIP_OK(hipStreamWaitEvent(stream_, ev_drained_, 0));  // the staging buffer's last copy is done
+    HIP_OK(FetchWinPack(d_arena, n_bytes, d_wscratch_, n_files, ctr, w0, w1, st, stream_));
+    HIP_OK(hipEventRecord(ev_packed_, stream_));
+    HIP_OK(hipStreamWaitEvent(fetch_stream_, ev_packed_, 0));
+    HIP_OK(hipMemcpyAsync(h_dst + w0, st, size_t(w1 - w0), hipMemcpyDeviceToHost, fetch_stream_));
+    HIP_OK(hipEventRecord(ev_drained_, fetch_stream_));
+  }
+  if (copy_bytes == 0) {  // the fetch stream's events still follow the plan
+    HIP_OK(hipEventRecord(ev_packed_, stream_));
+    HIP_OK(hipStreamWaitEvent(fetch_stream_, ev_packed_, 0));
+  }
+  return true;
+}
+
+// A windows fetch sized exactly, waited for (Run's): the candidates are on the host already.
+bool GpuEngine::FetchNowWin(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
+                            const std::vector<Candidate>& cands, FetchOut* out) {
+  if (!out->h_offsets) {
+    err_ = "fetch: the batch's host offsets are missing";
+    return false;
+  }
+  const uint64_t stage = fetchw_stage_bytes_.load();
+  HostWindowPlan P;
+  PlanWindowsOnHost(cands.data(), cands.size(), out->h_offsets, n_files, h_rule_max_len_.data(),
+                    uint32_t(h_rule_max_len_.size()), out->prm, &P);
+  const uint64_t packed = P.packed_bytes();
+  const uint64_t rp = fetchw_recent_packed_.load();
+  fetchw_recent_packed_.store(std::max(packed, rp - rp / 8));
+  out->Release();
+  out->windows = true;
+  out->runs.clear();
+  out->granules = out->whole_marked = 0;
+  out->files = out->bytes = out->direct_files = 0;
+  out->rounds = 0;
+  out->ms_fetch = 0;
+  if (packed == 0) return true;  // nothing to bring back
+  if (!EnsureFetchStream()) return false;
+  size_t cap = 0;
+  void* lease = TakeFetchBuf(size_t(packed) + 64, &cap);
+  if (!lease) {
+    err_ = "fetch: hipHostMalloc failed for " + std::to_string(packed) + " bytes";
+    return false;
+  }
+  out->owner = this;  // (from here on a failure's lease goes back with *out)
+  out->lease = lease;
+  out->lease_cap = cap;
+  out->buf = static_cast<const uint8_t*>(lease);
+  if (!IssueFetchWin(d_arena, n_bytes, d_offsets, n_files, out->prm, stage, packed, static_cast<uint8_t*>(lease),
+                     h_run_fctr_, ev_run_f_[0]))
+    return false;
+  HIP_OK(hipEventRecord(ev_run_f_[1], fetch_stream_));
+  HIP_OK(WaitEvent(ev_run_f_[1]));
+  const FetchWinCounters& C = *static_cast<const FetchWinCounters*>(h_run_fctr_);
+  std::string why;
+  if (!SameWindowPlan(C.granules, C.runs, C.whole_files, P, &why)) {
+    err_ = why;
+    return false;
+  }
+  float ms = 0;
+  hipEventElapsedTime(&ms, ev_run_f_[0], ev_run_f_[1]);
+  out->runs = std::move(P.runs);
+  out->granules = P.granules;
+  out->whole_marked = P.whole_files;
+  out->rounds = uint32_t((packed + stage - 1) / stage);
+  out->ms_fetch = ms;
+  return true;
+}
+
 bool GpuEngine::FetchFiles(const uint8_t* d_arena, const uint64_t* d_offsets, uint32_t n_files,
                            const std::vector<uint8_t>& want, FetchOut* out) {
   HIP_OK(hipSetDevice(device_));
@@ -3932,7 +4080,11 @@ bool GpuEngine::Run(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_
       std::vector<uint8_t> want(n_files, 0);
       for (const Candidate& c : *cands)
         if (c.file < n_files) want[c.file] = 1;
-      if (!FetchNow(d_arena, d_offsets, n_files, std::move(want), false, fetch)) return false;
+      if (fetch->want_windows) {
+        if (!FetchNowWin(d_arena, n_bytes, d_offsets, n_files, *cands, fetch)) return false;
+      } else if (!FetchNow(d_arena, d_offsets, n_files, std::move(want), false, fetch)) {
+        return false;
+      }
     }
     return true;
   }

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "fetch_layout.h"
 
 namespace tsg {
 
@@ -67,6 +68,77 @@ inline void FinishFetch(const HostFetchPlan& P, uint64_t stage, double ms, Fetch
   out->direct_files = P.direct.size();
   out->rounds = uint32_t((P.packed + stage - 1) / stage);
   out->ms_fetch = ms;
+}
+
+// ---- the windows fetch (fetch_layout.h), restated on the host ----
+//
+// From the candidates the host holds: the maximal runs of marked granules in
+// arena order (sorted, merged spans -- no bitmap), each with its place in the
+// packed layout, and the totals the device counted (fetch_windows.h
+// FetchWinCounters).  A file's view is the runs that meet its bytes, clipped
+// to the file.
+struct FilePiece {  // file-relative bytes [lo, hi), where they lie in the packed layout, and the run they are of
+  uint64_t lo, hi, packed;
+  size_t run;
+};
+struct HostWindowPlan {
+  std::vector<GranuleRun> runs;
+  std::vector<uint8_t> whole;  // per file: marked whole
+  uint64_t granules = 0, whole_files = 0;
+  uint64_t packed_bytes() const { return granules * kFetchGranule; }
+};
+
+inline void PlanWindowsOnHost(const Candidate* c, size_t nc, const uint64_t* h_off, uint32_t n_files,
+                              const uint32_t* rule_max_len, uint32_t n_rules, const FetchWinParams& prm,
+                              HostWindowPlan* P) {
+  *P = HostWindowPlan();
+  P->whole.assign(n_files, 0);
+  std::vector<std::pair<uint64_t, uint64_t>> spans;
+  spans.reserve(nc);
+  for (size_t i = 0; i < nc; i++) {
+    const uint32_t f = c[i].file;
+    if (f >= n_files || (c[i].flags & kCandDrop)) continue;  // as mark_files_kernel
+    uint64_t g0, g1;
+    bool whole;
+    const uint32_t ml = c[i].rule < n_rules ? rule_max_len[c[i].rule] : kFetchNoMaxLen;
+    if (!CandidateGranules(c[i].wlo, c[i].whi, ml, h_off[f], h_off[f + 1], prm, &g0, &g1, &whole)) continue;
+    if (whole && !P->whole[f]) {
+      P->whole[f] = 1;
+      P->whole_files++;
+    }
+    spans.push_back({g0, g1});
+  }
+  std::sort(spans.begin(), spans.end());
+  for (const auto& s : spans) {
+    if (!P->runs.empty() && s.first <= P->runs.back().g1) P->runs.back().g1 = std::max(P->runs.back().g1, s.second);
+    else P->runs.push_back(GranuleRun{s.first, s.second, 0});
+  }
+  for (GranuleRun& r : P->runs) {
+    r.packed = P->granules * kFetchGranule;
+    P->granules += r.g1 - r.g0;
+  }
+}
+
+// File [fs, fe)'s view: appended to *out in file order; `from`: a run index at
+// or before the file's first (views taken in file order pass the last result).
+inline size_t FileViewOf(const HostWindowPlan& P, uint64_t fs, uint64_t fe, size_t from, std::vector<FilePiece>* out) {
+  size_t k = from;
+  while (k < P.runs.size() && P.runs[k].g1 * kFetchGranule <= fs) k++;
+  const size_t first = k;
+  for (; k < P.runs.size() && P.runs[k].g0 * kFetchGranule < fe; k++) {
+    const uint64_t a = std::max(fs, P.runs[k].g0 * kFetchGranule), b = std::min(fe, P.runs[k].g1 * kFetchGranule);
+    if (a < b) out->push_back(FilePiece{a - fs, b - fs, P.runs[k].packed + (a - P.runs[k].g0 * kFetchGranule), k});
+  }
+  return first;
+}
+
+inline bool SameWindowPlan(uint64_t dev_granules, uint64_t dev_runs, uint64_t dev_whole, const HostWindowPlan& P,
+                           std::string* err) {
+  if (dev_granules == P.granules && dev_runs == P.runs.size() && dev_whole == P.whole_files) return true;
+  *err = "fetch windows: the device marked " + std::to_string(dev_granules) + " granules / " +
+         std::to_string(dev_runs) + " runs / " + std::to_string(dev_whole) + " whole files, the host " +
+         std::to_string(P.granules) + " / " + std::to_string(P.runs.size()) + " / " + std::to_string(P.whole_files);
+  return false;
 }
 
 // Pinned fetch buffers: on loan to the scans' FetchOut, back to a small free

@@ -978,11 +978,30 @@ void Regex::ComputeFirstBytes() {
 }
 
 // ---------------------------------------------------------------------------
+// Cut texts (Regex::FindAllBounded): the engines are given bytes [0, n) that
+// are a piece of a longer text.  Every read site below tells the Cut when its
+// answer could depend on a byte beyond a cut edge; the search goes on as if
+// the piece were the whole text, and the caller discards the result.
+// ---------------------------------------------------------------------------
+struct Cut {
+  bool lo, hi;  // bytes exist before 0 / at and after n that were not given
+  bool hit;
+};
+// a rune decoded (or a byte read) at pos: beyond the piece, or a multi-byte rune that may run past it
+static inline void CutRune(Cut* c, const uint8_t* s, int64_t n, int64_t pos) {
+  if (c && c->hi && (pos >= n || (s[pos] >= 0x80 && pos + 4 > n))) c->hit = true;
+}
+// the bytes on both sides of pos (an assertion's context)
+static inline void CutContext(Cut* c, int64_t n, int64_t pos) {
+  if (c && ((c->lo && pos <= 0) || (c->hi && pos >= n))) c->hit = true;
+}
+
+// ---------------------------------------------------------------------------
 // Pike VM (regexp/exec.go)
 // ---------------------------------------------------------------------------
 class Machine {
  public:
-  Machine(const Regex* re, int ncap) : re_(re), ncap_(ncap) {
+  Machine(const Regex* re, int ncap, Cut* cut = nullptr) : re_(re), ncap_(ncap), cut_(cut) {
     size_t n = re->prog_.size();
     for (int k = 0; k < 2; k++) {
       q_[k].sparse.assign(n, 0);
@@ -1008,10 +1027,17 @@ class Machine {
     size_t wi = 0;
     if (wins) {
       while (wi < wins->size() && (*wins)[wi].hi < pos) wi++;
+      if (cut_) {  // a cut text: nothing is read before the first allowed start (the loop's jump, made first)
+        if (wi >= wins->size() || (re_->anchored_begin_ && pos != 0)) return false;
+        if ((*wins)[wi].lo > pos) {
+          const int64_t t = Align(s, n, (*wins)[wi].lo, cut_);
+          if (t > pos) pos = t;
+        }
+      }
     }
-    Rune r = DecodeRune(s, n, pos);
-    Rune r1 = r.r >= 0 ? DecodeRune(s, n, pos + r.width) : Rune{-1, 0};
-    uint8_t flag = Context(s, n, pos);
+    Rune r = Decode(s, n, pos);
+    Rune r1 = r.r >= 0 ? Decode(s, n, pos + r.width) : Rune{-1, 0};
+    uint8_t flag = Context(s, n, pos, cut_);
     for (;;) {
       if (runq->dense.empty()) {
         if (re_->anchored_begin_ && pos != 0) break;
@@ -1021,12 +1047,12 @@ class Machine {
           while (wi < wins->size() && (*wins)[wi].hi < pos) wi++;
           if (wi >= wins->size()) break;
           if ((*wins)[wi].lo > pos) {
-            int64_t t = Align(s, n, (*wins)[wi].lo);
+            int64_t t = Align(s, n, (*wins)[wi].lo, cut_);
             if (t > pos) {
               pos = t;
-              r = DecodeRune(s, n, pos);
-              r1 = r.r >= 0 ? DecodeRune(s, n, pos + r.width) : Rune{-1, 0};
-              flag = Context(s, n, pos);
+              r = Decode(s, n, pos);
+              r1 = r.r >= 0 ? Decode(s, n, pos + r.width) : Rune{-1, 0};
+              flag = Context(s, n, pos, cut_);
             }
           }
         }
@@ -1046,7 +1072,7 @@ class Machine {
       if (ncap_ == 0 && matched_) break;
       pos += r.width;
       r = r1;
-      if (r.r >= 0) r1 = DecodeRune(s, n, pos + r.width);
+      if (r.r >= 0) r1 = Decode(s, n, pos + r.width);
       flag = nextflag;
       std::swap(runq, nextq);
     }
@@ -1059,12 +1085,15 @@ class Machine {
 
   // Largest Go rune-chain position <= t (see goregex.h): only a continuation
   // byte inside a valid multi-byte sequence is not a rune boundary.
-  static int64_t Align(const uint8_t* s, int64_t n, int64_t t) {
+  static int64_t Align(const uint8_t* s, int64_t n, int64_t t, Cut* cut = nullptr) {
+    if (cut && t < n && t <= 3 && cut->lo && (s[t < 0 ? 0 : t] & 0xC0) == 0x80)
+      cut->hit = true;  // the rune this byte continues may begin before the piece
     if (t >= n || t <= 0) return t;
     if ((s[t] & 0xC0) != 0x80) return t;
     for (int k = 1; k <= 3 && t - k >= 0; k++) {
       uint8_t b = s[t - k];
       if ((b & 0xC0) == 0x80) continue;
+      CutRune(cut, s, n, t - k);
       Rune r = DecodeRune(s, n, t - k);
       if (r.width > k) return t - k;
       return t;
@@ -1083,6 +1112,11 @@ class Machine {
   };
   const Regex* re_;
   int ncap_;
+  Cut* cut_;
+  Rune Decode(const uint8_t* s, int64_t n, int64_t pos) const {
+    CutRune(cut_, s, n, pos);
+    return DecodeRune(s, n, pos);
+  }
   Queue q_[2];
   bool matched_ = false;
   std::vector<int64_t> matchcap_;
@@ -1114,7 +1148,8 @@ class Machine {
   }
 
   friend class Backtracker;
-  static uint8_t Context(const uint8_t* s, int64_t n, int64_t pos) {
+  static uint8_t Context(const uint8_t* s, int64_t n, int64_t pos, Cut* cut = nullptr) {
+    CutContext(cut, n, pos);
     int32_t r1 = -1, r2 = -1;
     if (pos > 0 && pos <= n) {
       uint8_t b = s[pos - 1];
@@ -1231,7 +1266,8 @@ class Backtracker {
   // Same contract as Machine::Search (returns the match in cap()).  *overflow:
   // the search needed more than kMaxRows positions; the result is invalid.
   bool Search(const Regex* re, const uint8_t* s, int64_t n, int64_t pos, const std::vector<Window>* wins, int ncap,
-              bool* overflow) {
+              bool* overflow, Cut* cut = nullptr) {
+    cut_ = cut;
     re_ = re;
     s_ = s;
     n_ = n;
@@ -1248,12 +1284,15 @@ class Backtracker {
         while (wi < wins->size() && (*wins)[wi].hi < pos) wi++;
         if (wi >= wins->size()) break;
         if ((*wins)[wi].lo > pos) {
-          const int64_t t = Machine::Align(s, n, (*wins)[wi].lo);
+          const int64_t t = Machine::Align(s, n, (*wins)[wi].lo, cut);
           if (t > pos) pos = t;
         }
       }
       const bool allowed = !wins || (*wins)[wi].lo <= pos;
       if (anchored && pos != 0) break;
+      if (cut && allowed) {  // a start at a cut edge: what lies beyond decides (\A, the first byte at n)
+        CutContext(cut, n, pos);
+      }
       if (allowed && re->FirstOk(s, n, pos)) {
         if (top_ < pos) Rebase(pos);  // states before pos are unreachable from here on
         if (ncap_ > 0) cap_[0] = pos;
@@ -1264,6 +1303,7 @@ class Backtracker {
         }
       }
       if (pos >= n) break;
+      CutRune(cut, s, n, pos);
       pos += DecodeRune(s, n, pos).width;
     }
     return false;
@@ -1271,6 +1311,7 @@ class Backtracker {
   const std::vector<int64_t>& cap() const { return matchcap_; }
 
  private:
+  Cut* cut_ = nullptr;
   struct Job {
     uint32_t pc;
     bool arg;
@@ -1356,6 +1397,7 @@ class Backtracker {
             if (!ok) continue;
             pos += 1;
           } else {
+            CutRune(cut_, s_, n_, pos);
             const Rune r = DecodeRune(s_, n_, pos);
             if (!re_->RuneMatch(in, r.r)) continue;
             pos += r.width;
@@ -1378,7 +1420,7 @@ class Backtracker {
           pc = in.out;
           goto check;
         case kIEmpty:
-          if ((in.empty & ~Machine::Context(s_, n_, pos)) != 0) continue;
+          if ((in.empty & ~Machine::Context(s_, n_, pos, cut_)) != 0) continue;
           pc = in.out;
           goto check;
         case kINop:
@@ -1506,7 +1548,7 @@ void Regex::DetectRun() {
 // the run can match either (their runs are shorter), so the search resumes
 // after it.  Windows restrict the starts as in Backtracker::Search.
 void Regex::FindAllRun(const uint8_t* s, int64_t n, bool submatch, const std::vector<Window>* wins,
-                       std::vector<int64_t>* out) const {
+                       std::vector<int64_t>* out, Cut* cut) const {
   const int groups = submatch ? num_cap_ + 1 : 1;
   const int64_t lim = run_max_ < 0 ? INT64_MAX : int64_t(run_max_);
   int64_t pos = 0;
@@ -1516,15 +1558,17 @@ void Regex::FindAllRun(const uint8_t* s, int64_t n, bool submatch, const std::ve
       while (wi < wins->size() && (*wins)[wi].hi < pos) wi++;
       if (wi >= wins->size()) break;
       if ((*wins)[wi].lo > pos) {
-        const int64_t t = Machine::Align(s, n, (*wins)[wi].lo);
+        const int64_t t = Machine::Align(s, n, (*wins)[wi].lo, cut);
         if (t > pos) pos = t;
       }
       if (pos >= n) break;
       if ((*wins)[wi].lo > pos) {  // not a start the windows allow: the next rune
+        CutRune(cut, s, n, pos);
         pos += DecodeRune(s, n, pos).width;
         continue;
       }
     }
+    if (cut && cut->lo && pos == 0) cut->hit = true;  // (whether the piece begins at a rune boundary is not known)
     int64_t q = pos, k = 0;
     int w = 1;
     while (q < n && k < lim) {
@@ -1539,6 +1583,7 @@ void Regex::FindAllRun(const uint8_t* s, int64_t n, bool submatch, const std::ve
         w = 1;
         in = false;
       } else {
+        CutRune(cut, s, n, q);
         const Rune r = DecodeRune(s, n, q);
         w = r.width;
         in = InRanges(run_cls_, uint32_t(r.r));
@@ -1547,6 +1592,7 @@ void Regex::FindAllRun(const uint8_t* s, int64_t n, bool submatch, const std::ve
       q += w;
       k++;
     }
+    if (cut && q >= n && k < lim) CutRune(cut, s, n, q);  // the run reached the end of the piece
     if (k >= run_min_) {
       for (int g = 0; g < groups; g++) {
         out->push_back(pos);
@@ -1561,25 +1607,59 @@ void Regex::FindAllRun(const uint8_t* s, int64_t n, bool submatch, const std::ve
 
 void Regex::FindAll(const uint8_t* s, int64_t n, bool submatch, const std::vector<Window>* wins,
                     std::vector<int64_t>* out) const {
+  FindAllImpl(s, n, submatch, wins, out, nullptr);
+}
+
+void Regex::FindAllBounded(const uint8_t* bytes, int64_t lo, int64_t hi, int64_t true_len, bool submatch,
+                           const std::vector<Window>* wins, std::vector<int64_t>* out, bool* hit_limit) const {
+  const int64_t n = hi - lo;
+  Cut cut{lo > 0, hi < true_len, false};
+  // the allowed starts, relative to the piece; a start outside it cannot be examined
+  const int64_t last = cut.hi ? n - 1 : n;  // (the end of the text is a start: an empty match there)
+  std::vector<Window> w;
+  if (wins) {
+    for (const Window& x : *wins) {
+      Window y{x.lo - lo, x.hi - lo};
+      if (y.lo < 0 || y.hi > last) {
+        if (y.lo < 0 && cut.lo) cut.hit = true;
+        if (y.hi > last && cut.hi) cut.hit = true;
+        y.lo = std::max<int64_t>(y.lo, 0);
+        y.hi = std::min(y.hi, last);
+      }
+      if (y.lo <= y.hi) w.push_back(y);
+    }
+  } else {
+    if (cut.lo || cut.hi) cut.hit = cut.hit || n <= 0;
+    if (last >= 0) w.push_back({0, last});
+  }
+  const size_t at = out->size();
+  if (n >= 0 && !(wins && w.empty())) FindAllImpl(bytes, n, submatch, (cut.lo || cut.hi || wins) ? &w : nullptr, out, &cut);
+  for (size_t k = at; k < out->size(); k++)
+    if ((*out)[k] >= 0) (*out)[k] += lo;
+  *hit_limit = cut.hit;
+}
+
+void Regex::FindAllImpl(const uint8_t* s, int64_t n, bool submatch, const std::vector<Window>* wins,
+                        std::vector<int64_t>* out, Cut* cut) const {
   int ncap = submatch ? 2 * (num_cap_ + 1) : 2;
   Backtracker& bt = t_bt;
   const int mode = g_regex_engine.load(std::memory_order_relaxed);
   if (run_ok_ && mode == 0) {  // modes 1-3: the general engines (tests compare them)
-    FindAllRun(s, n, submatch, wins, out);
+    FindAllRun(s, n, submatch, wins, out, cut);
     return;
   }
   bt.max_rows_ = mode == 2 ? 8 : Backtracker::kMaxRows;
   std::unique_ptr<Machine> m;  // only when the backtracker's row budget runs out
-  if (mode == 1) m.reset(new Machine(this, ncap));
+  if (mode == 1) m.reset(new Machine(this, ncap, cut));
   int64_t pos = 0, prev_end = -1;
   while (pos <= n) {
     bool overflow = false;
     const std::vector<int64_t>* cp;
-    if (!m && bt.Search(this, s, n, pos, wins, ncap, &overflow)) {
+    if (!m && bt.Search(this, s, n, pos, wins, ncap, &overflow, cut)) {
       cp = &bt.cap();
     } else {
       if (!overflow && !m) break;
-      if (!m) m.reset(new Machine(this, ncap));
+      if (!m) m.reset(new Machine(this, ncap, cut));
       if (!m->Search(s, n, pos, wins)) break;
       cp = &m->cap();
     }
@@ -1587,6 +1667,7 @@ void Regex::FindAll(const uint8_t* s, int64_t n, bool submatch, const std::vecto
     bool accept = true;
     if (c[1] == pos) {  // empty match
       if (c[0] == prev_end) accept = false;
+      CutRune(cut, s, n, pos);
       Rune r = DecodeRune(s, n, pos);
       pos += r.width > 0 ? r.width : 1;
     } else {

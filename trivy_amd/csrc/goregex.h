@@ -67,6 +67,8 @@ struct Rune {
 };
 Rune DecodeRune(const uint8_t* s, int64_t n, int64_t pos);
 
+struct Cut;  // goregex.cpp: the cut edges of a piece of text and whether a read met one (FindAllBounded)
+
 class Regex {
  public:
   static std::unique_ptr<Regex> Compile(const std::string& pattern, std::string* err);
@@ -83,6 +85,19 @@ class Regex {
   // (or 2 when !submatch).  `wins` (sorted, merged) restricts match starts.
   void FindAll(const uint8_t* s, int64_t n, bool submatch, const std::vector<Window>* wins,
                std::vector<int64_t>* out) const;
+  // FindAll over a piece of a text: `bytes` holds the text's bytes [lo, hi)
+  // and nothing else (bytes[0] is the text's byte lo); the text's true extent
+  // is [0, true_len).  `wins` and the offsets appended are relative to the
+  // text, not the piece.  *hit_limit is set whenever the answer could depend
+  // on a byte that was not given -- a rune or an assertion that needs a byte
+  // >= hi while hi < true_len, or one < lo while lo > 0 (it may also be set by
+  // a read within 4 bytes of such an edge that turned out not to matter); the
+  // matches appended are then not to be used.  lo == 0 and hi == true_len are
+  // the text's real ends and never set it.  Where it stays clear, the result
+  // is FindAll's over the whole text, restricted to the starts in `wins` (all
+  // of [lo, hi) -- [lo, hi] at the text's end -- without windows).
+  void FindAllBounded(const uint8_t* bytes, int64_t lo, int64_t hi, int64_t true_len, bool submatch,
+                      const std::vector<Window>* wins, std::vector<int64_t>* out, bool* hit_limit) const;
 
  private:
   friend class Parser;
@@ -126,7 +141,9 @@ class Regex {
   void DetectLiteral();
   bool MatchLiteral(const uint8_t* s, int64_t n) const;
   void FindAllRun(const uint8_t* s, int64_t n, bool submatch, const std::vector<Window>* wins,
-                  std::vector<int64_t>* out) const;
+                  std::vector<int64_t>* out, struct Cut* cut) const;
+  void FindAllImpl(const uint8_t* s, int64_t n, bool submatch, const std::vector<Window>* wins,
+                   std::vector<int64_t>* out, struct Cut* cut) const;
   void ComputeFirstBytes();
   bool FirstOk(const uint8_t* s, int64_t n, int64_t pos) const {
     return first_all_ || (pos < n && ((first_[s[pos] >> 6] >> (s[pos] & 63)) & 1));

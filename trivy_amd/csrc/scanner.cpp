@@ -1,6 +1,7 @@
 // Exact host tail of the drop-in Scanner (see scanner.h for the line map).
 #include "scanner.h"
 
+#include "fetch_host.h"
 #include "parallel.h"
 
 #include <pthread.h>
@@ -475,6 +476,7 @@ SecretScanner::SecretScanner(std::vector<RuleSpec> rules, std::vector<AllowRuleS
                              const CompileOptions* opt)
     : rules_(std::move(rules)), allow_(std::move(allow)), exclude_(std::move(exclude)) {
   rule_rank_ = RuleRanks(rules_);
+  if (const char* fm = std::getenv("TSG_FETCH_MODE")) fetch_windows_ = std::strcmp(fm, "windows") == 0;
   std::vector<RuleSrc> src;
   for (auto& r : rules_) src.push_back({r.id, r.regex_src, r.keywords, r.has_regex});
   for (size_t g = 0; g < exclude_.size(); g++) {
@@ -793,7 +795,7 @@ thread_local ScanScratch t_scan;
 void SecretScanner::ScanFile(const uint8_t* content, int64_t len, std::string_view path, bool binary,
                              const Candidate* c, size_t nc, FileResult* out, bool gpu_windows) const {
   PhaseTimer pt_all(7);
-  MatchFile(content, len, path, c, nc, gpu_windows);
+  (void)MatchFile(content, len, path, c, nc, gpu_windows);
   if (t_scan.matched.empty()) {
     out->kind = kNoFindings;
     return;
@@ -801,8 +803,54 @@ void SecretScanner::ScanFile(const uint8_t* content, int64_t len, std::string_vi
   FindingsHost(content, len, path, binary, c, nc, out);
 }
 
-void SecretScanner::MatchFile(const uint8_t* content, int64_t len, std::string_view path, const Candidate* c,
-                              size_t nc, bool gpu_windows) const {
+namespace {
+// The piece of a sparse file that holds its bytes [s, e) (e == s: the byte position s), or nullptr.
+const SparsePiece* PieceOf(const SparseFile& sp, int64_t s, int64_t e) {
+  size_t a = 0, b = sp.n;  // the last piece with lo <= s
+  while (a < b) {
+    const size_t mid = (a + b) / 2;
+    if (sp.pieces[mid].lo <= s) a = mid + 1;
+    else b = mid;
+  }
+  if (a == 0) return nullptr;
+  const SparsePiece& pc = sp.pieces[a - 1];
+  return e <= pc.hi ? &pc : nullptr;
+}
+}  // namespace
+
+bool SecretScanner::MatchFile(const uint8_t* content, int64_t len, std::string_view path, const Candidate* c,
+                              size_t nc, bool gpu_windows, const SparseFile* sp) const {
+  // A sparse file (the windows fetch): only pieces of it are here.  Each FindAll
+  // runs piece by piece on the windows inside the piece (FindAllBounded); the
+  // pieces are separated by bytes that were not fetched, and a match that would
+  // reach them reports it.  Whatever needs a byte outside the pieces -- such a
+  // report, a window outside every piece, a keyword gate that has to read the
+  // whole content -- ends the sparse pass: false, the caller scans the whole file.
+  auto find_all = [&](const Regex* re, bool sub, const std::vector<Window>& wins, std::vector<int64_t>* m) {
+    if (!sp) {
+      re->FindAll(content, len, sub, &wins, m);
+      return true;
+    }
+    size_t pi = 0, wi = 0;
+    std::vector<Window> pw;
+    while (wi < wins.size()) {
+      const int64_t w_lo = wins[wi].lo;
+      while (pi < sp->n && sp->pieces[pi].hi <= w_lo && !(w_lo == len && sp->pieces[pi].hi == len)) pi++;
+      if (pi == sp->n || sp->pieces[pi].lo > w_lo) return false;
+      const SparsePiece& pc = sp->pieces[pi];
+      const int64_t last = pc.hi == len ? pc.hi : pc.hi - 1;  // the last start the piece can answer for
+      pw.clear();
+      for (; wi < wins.size() && wins[wi].lo <= last; wi++) {
+        const Window w{wins[wi].lo, std::min(wins[wi].hi, len)};
+        if (w.hi > last) return false;
+        pw.push_back(w);
+      }
+      bool hit = false;
+      re->FindAllBounded(pc.p, pc.lo, pc.hi, len, sub, &pw, m, &hit);
+      if (hit) return false;
+    }
+    return true;
+  };
   const uint8_t* P = reinterpret_cast<const uint8_t*>(path.data());
   ScanScratch& S = t_scan;
   std::vector<std::pair<uint32_t, Loc>>& matched = S.matched;
@@ -827,6 +875,7 @@ void SecretScanner::MatchFile(const uint8_t* content, int64_t len, std::string_v
       else wins->push_back(w);
     }
   };
+  bool need_whole = false;  // (sparse) a block regex ran off its pieces
   auto blocks_match = [&](const std::vector<std::unique_ptr<Regex>>& rx, const std::vector<uint32_t>& rx_rule,
                           std::vector<Loc>* cache, bool* done, Loc loc) {
     if (!*done) {
@@ -837,8 +886,12 @@ void SecretScanner::MatchFile(const uint8_t* content, int64_t len, std::string_v
           std::vector<Window> wins;
           block_windows(rx_rule[q], &wins);
           if (wins.empty()) continue;
-          rx[q]->FindAll(content, len, false, &wins, &m);
+          if (!find_all(rx[q].get(), false, wins, &m)) need_whole = true;
         } else {
+          if (sp) {  // (a sweep of the whole file: not from pieces)
+            need_whole = true;
+            continue;
+          }
           rx[q]->FindAll(content, len, false, nullptr, &m);
         }
         for (size_t k = 0; k + 1 < m.size(); k += 2) cache->push_back({m[k], m[k + 1]});
@@ -875,7 +928,7 @@ void SecretScanner::MatchFile(const uint8_t* content, int64_t len, std::string_v
     {
       PhaseTimer pt(0);
       const auto fa0 = g_tail_debug ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
-      re->FindAll(content, len, sub, &wins, &m);
+      if (!find_all(re, sub, wins, &m)) return false;
       if (g_tail_debug && r < kRuleProf) {  // per-rule FindAll time (TSG_TAIL_DEBUG)
         g_rule_ns[r] += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - fa0).count();
         g_rule_calls[r] += 1;
@@ -896,6 +949,11 @@ void SecretScanner::MatchFile(const uint8_t* content, int64_t len, std::string_v
                  !cr_.rules[r].kw_match_implied && (group_flags & kCandGateOpen);
       for (size_t k = 0; k + stride <= m.size() && !hit; k += stride) {
         const uint8_t* ms = content + m[k];
+        if (sp) {  // (a match lies inside one piece: nothing beyond it was read)
+          const SparsePiece* pc = PieceOf(*sp, m[k], m[k + 1]);
+          if (!pc) return false;
+          ms = pc->p + (m[k] - pc->lo);
+        }
         const size_t mn = size_t(m[k + 1] - m[k]);
         // ASCII keywords in a match without U+0130 / U+212A: the ASCII
         // case-insensitive search is exact (see the whole-content case below)
@@ -927,6 +985,15 @@ void SecretScanner::MatchFile(const uint8_t* content, int64_t len, std::string_v
         hit = (group_flags & kCandGateOpen) != 0;
         fold_done = true;
         fold_runes = (group_flags & kCandFoldFile) != 0;
+      }
+      if (!hit && sp) {
+        // a closed gate is exact only from the GPU's bits over a file without fold runes and
+        // for ASCII keywords; every other case reads the whole content
+        bool need_go = false;
+        for (auto& kw : R.kw_lower_host)
+          if (!IsAsciiStr(kw)) need_go = true;
+        if (!gpu_bits || fold_runes || need_go) return false;
+        continue;
       }
       if (!hit) {
         // ASCII keywords: an occurrence in the ASCII-lowered bytes is one in
@@ -980,8 +1047,14 @@ void SecretScanner::MatchFile(const uint8_t* content, int64_t len, std::string_v
     PhaseTimer pt5(5);
     for (size_t k = 0; k + stride <= m.size(); k += stride) {
       int64_t s = m[k], e = m[k + 1];
-      if (AllowRulesAllow(allow_, content + s, size_t(e - s)) ||
-          AllowRulesAllow(R.allow_rules, content + s, size_t(e - s)))  // AllowLocation :150-153
+      const uint8_t* mp = content + s;
+      if (sp) {
+        const SparsePiece* pc = PieceOf(*sp, s, e);
+        if (!pc) return false;
+        mp = pc->p + (s - pc->lo);
+      }
+      if (AllowRulesAllow(allow_, mp, size_t(e - s)) ||
+          AllowRulesAllow(R.allow_rules, mp, size_t(e - s)))  // AllowLocation :150-153
         continue;
       if (sub) {
         for (int g : R.group_idx) locs.push_back({m[k + 2 * g], m[k + 2 * g + 1]});
@@ -1001,7 +1074,9 @@ void SecretScanner::MatchFile(const uint8_t* content, int64_t len, std::string_v
       matched.push_back({r, loc});
       censor.push_back(loc);
     }
+    if (need_whole) return false;
   }
+  return true;
 }
 
 void SecretScanner::FindingsHost(const uint8_t* content, int64_t len, std::string_view path, bool binary,
@@ -1399,8 +1474,29 @@ void SecretScanner::FindingsHost(const uint8_t* content, int64_t len, std::strin
   SortFindings(&out->findings, rule_rank_);
 }
 
-void SecretScanner::GpuFindingsInput(const uint8_t* content, const Candidate* c, size_t nc, FileResult* out) const {
+bool SecretScanner::GpuFindingsInput(const uint8_t* content, const Candidate* c, size_t nc, FileResult* out,
+                                     const SparseFile* sp) const {
   ScanScratch& S = t_scan;
+  bool inside = true;  // (sparse) every span lies in a piece
+  auto count_nl = [&](int64_t a, int64_t b) {  // '\n' in [a, b): inside a censor span, hence inside a piece
+    const uint8_t* p = content + a;
+    if (sp) {
+      const SparsePiece* pc = PieceOf(*sp, a, b);
+      if (!pc) {
+        inside = false;
+        return int64_t(0);
+      }
+      p = pc->p + (a - pc->lo);
+    }
+    int64_t n = 0;
+    for (const uint8_t* e = p + (b - a); p < e;) {
+      const void* q = std::memchr(p, '\n', size_t(e - p));
+      if (!q) break;
+      n++;
+      p = static_cast<const uint8_t*>(q) + 1;
+    }
+    return n;
+  };
   // the anchors: (wlo, raw '\n' before wlo) of every candidate window of the file
   std::vector<std::pair<int64_t, int64_t>>& nla = S.nla;
   nla.clear();
@@ -1418,24 +1514,15 @@ void SecretScanner::GpuFindingsInput(const uint8_t* content, const Candidate* c,
     if (!out->gs.empty() && z.s <= out->gs.back().e) {
       MatSpan& b = out->gs.back();
       if (z.e > b.e) {  // (the '\n' of the grown part)
-        for (const uint8_t *p = content + b.e, *e = content + z.e; p < e;) {
-          const void* q = std::memchr(p, '\n', size_t(e - p));
-          if (!q) break;
-          nl++;
-          p = static_cast<const uint8_t*>(q) + 1;
-        }
+        nl += count_nl(b.e, z.e);
         b.e = z.e;
       }
       continue;
     }
     out->gs.push_back({z.s, z.e, nl});
-    for (const uint8_t *p = content + z.s, *e = content + z.e; p < e;) {
-      const void* q = std::memchr(p, '\n', size_t(e - p));
-      if (!q) break;
-      nl++;
-      p = static_cast<const uint8_t*>(q) + 1;
-    }
+    nl += count_nl(z.s, z.e);
   }
+  if (!inside) return false;
   out->gs.push_back({INT64_MAX, INT64_MAX, nl});
   out->gm.clear();
   uint64_t tb = 0;
@@ -1453,12 +1540,20 @@ void SecretScanner::GpuFindingsInput(const uint8_t* content, const Candidate* c,
   }
   out->text_bound = tb;
   out->gpu = true;
+  return true;
 }
 
+static uint64_t BuildSparse(const HostWindowPlan& P, const std::vector<const uint8_t*>& run_base, const uint64_t* off,
+                            uint32_t n_files, SparseBatch* sb, std::vector<const uint8_t*>* fdata,
+                            std::vector<uint64_t>* flen);
+
 bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst, HostStats* hst, std::string* err,
-                         FetchStats* fst) {
+                         FetchStats* fst, FetchWindowStats* wst) {
   double t0 = NowMs();
   if (fst) *fst = FetchStats();
+  FetchWindowStats wlocal;
+  if (!wst) wst = &wlocal;
+  *wst = FetchWindowStats();
   struct Active {
     std::atomic<int>& n;
     explicit Active(std::atomic<int>& c) : n(c) { n.fetch_add(1); }
@@ -1493,6 +1588,16 @@ bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst
   FetchOut fetch;
   fetch.h_offsets = in.host_offsets;
   FetchOut* fp = dev_only && !in.transform ? &fetch : nullptr;
+  // the windows fetch (fetch_layout.h): untransformed device-only batches, where the mode is on and the
+  // GPU findings pass exists (the sparse files' lines are read from the resident arena)
+  if (fp && mat_) {
+    if (in.fetch_windows >= 0) {
+      fetch.want_windows = in.fetch_windows != 0;
+      fetch.prm = in.fetch_prm;
+    } else {
+      fetch.want_windows = GetFetchOptions(&fetch.prm);
+    }
+  }
   // dev_offsets is optional: without it the offsets are uploaded for this scan
   struct DevOffsets {
     void* p = nullptr;
@@ -1559,6 +1664,10 @@ bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst
   tin.dev_offsets = dev_offsets;
   std::vector<const uint8_t*> fdata;
   std::vector<uint64_t> flen;
+  SparseBatch sparse;
+  uint64_t n_touched = 0;
+  uint32_t fallback_rounds = 0;
+  double fallback_ms = 0;
   if (in.transform) {  // gathered files from tail.buf, identity-transformed ones in place
     fdata.assign(in.n_files, nullptr);
     flen.assign(in.n_files, 0);
@@ -1576,6 +1685,41 @@ bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst
     }
     tin.file_data = fdata.data();
     tin.file_len = flen.data();
+  } else if (dev_only && fetch.windows) {  // the fetched granules: whole files through file_data, the others sparse
+    HostWindowPlan P;
+    P.runs = fetch.runs;
+    std::vector<const uint8_t*> run_base(P.runs.size());
+    for (size_t k = 0; k < P.runs.size(); k++) run_base[k] = fetch.buf + P.runs[k].packed;
+    n_touched = BuildSparse(P, run_base, in.host_offsets, in.n_files, &sparse, &fdata, &flen);
+    sparse.fetch_whole = [&](const std::vector<uint8_t>& want, std::vector<const uint8_t*>* data,
+                             std::shared_ptr<void>* keep, uint64_t* direct, std::string* e) {
+      auto fo = std::make_shared<FetchOut>();
+      fo->h_offsets = in.host_offsets;
+      {
+        std::lock_guard<std::mutex> g(gpu_mu_[slot]);
+        if (!engine->FetchFiles(in.dev_arena, dev_offsets, in.n_files, want, fo.get())) {
+          *e = engine->error();
+          return false;
+        }
+      }
+      data->assign(in.n_files, nullptr);
+      for (uint32_t f = 0; f < in.n_files; f++)
+        if (want[f]) (*data)[f] = fo->buf + fo->off[f];
+      *direct = fo->direct_files;
+      fallback_rounds = fo->rounds;
+      fallback_ms = fo->ms_fetch;
+      *keep = fo;
+      return true;
+    };
+    tin.file_data = fdata.data();
+    tin.file_len = flen.data();
+    tin.file_data_is_arena = true;
+    tin.sparse = &sparse;
+    tin.window_stats = wst;
+    wst->mode_used = 1;
+    wst->granules = fetch.granules;
+    wst->runs = fetch.runs.size();
+    wst->window_bytes = fetch.granules * kFetchGranule;
   } else if (dev_only) {  // the fetched files, where the fetch put them
     fdata.assign(in.n_files, nullptr);
     flen.assign(in.n_files, 0);
@@ -1604,6 +1748,13 @@ bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst
   }
   const double t_tail = NowMs();
   if (!HostTail(tin, &cands, out, &hs, &allowed, true, err)) return false;
+  if (fst && fetch.windows) {  // what came back in all: the granules, then the whole files of the fallback
+    fst->files = n_touched;
+    fst->bytes = wst->window_bytes + wst->fallback_bytes;
+    fst->rounds = fetch.rounds + fallback_rounds;
+    fst->direct_files = wst->fallback_direct;
+    fst->ms_fetch = fetch.ms_fetch + fallback_ms;
+  }
   if (gst && gst->ms_total > 0) host_bound_.store(hs.ms_exact > 1.5 * double(gst->ms_total));
   static const bool times = std::getenv("TSG_TAIL_TIMES") != nullptr;
   if (times)
@@ -1614,6 +1765,92 @@ bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst
   hs.ms_total = NowMs() - t0;
   if (hst) *hst = hs;
   return true;
+}
+
+std::vector<uint32_t> SecretScanner::RuleMaxLens() const {
+  std::vector<uint32_t> ml(cr_.rules.size());
+  for (size_t r = 0; r < ml.size(); r++) ml[r] = cr_.rules[r].max_len;
+  return ml;
+}
+
+// The exact pass's view of a windows fetch: the files whose pieces are the whole file read them
+// through file_data, the others are sparse.  run_base[k]: where run k's bytes are.
+static uint64_t BuildSparse(const HostWindowPlan& P, const std::vector<const uint8_t*>& run_base, const uint64_t* off,
+                        uint32_t n_files, SparseBatch* sb, std::vector<const uint8_t*>* fdata,
+                        std::vector<uint64_t>* flen) {
+  static const uint8_t kNothing = 0;
+  sb->pieces.clear();
+  sb->first.assign(size_t(n_files) + 1, 0);
+  sb->sparse.assign(n_files, 0);
+  fdata->assign(n_files, nullptr);
+  flen->assign(n_files, 0);
+  std::vector<FilePiece> v;
+  size_t from = 0;
+  uint64_t touched = 0;  // files of which any byte is here
+  for (uint32_t f = 0; f < n_files; f++) {
+    sb->first[f] = uint32_t(sb->pieces.size());
+    const uint64_t fs = off[f], fe = off[f + 1];
+    (*flen)[f] = fe - fs;
+    if (fe == fs) {  // (an empty file is whole)
+      (*fdata)[f] = &kNothing;
+      continue;
+    }
+    if (from >= P.runs.size()) continue;  // (no run left: no candidates from here on)
+    v.clear();
+    from = FileViewOf(P, fs, fe, from, &v);
+    if (v.empty()) continue;
+    touched++;
+    if (v.size() == 1 && v[0].lo == 0 && v[0].hi == fe - fs) {
+      (*fdata)[f] = run_base[v[0].run] + (fs - P.runs[v[0].run].g0 * kFetchGranule);
+      continue;
+    }
+    sb->sparse[f] = 1;
+    for (const FilePiece& x : v)
+      sb->pieces.push_back(SparsePiece{int64_t(x.lo), int64_t(x.hi),
+                                       run_base[x.run] + (fs + x.lo - P.runs[x.run].g0 * kFetchGranule)});
+  }
+  sb->first[n_files] = uint32_t(sb->pieces.size());
+  return touched;
+}
+
+bool SecretScanner::SparseTail(const BatchInput& in, std::vector<Candidate>* cands, const FetchWinParams& prm,
+                               BatchResult* out, HostStats* hs, FetchWindowStats* ws, std::string* err) const {
+  const std::vector<uint32_t> ml = RuleMaxLens();
+  HostWindowPlan P;
+  PlanWindowsOnHost(cands->data(), cands->size(), in.host_offsets, in.n_files, ml.data(), uint32_t(ml.size()), prm, &P);
+  const uint64_t n_bytes = in.n_files ? in.host_offsets[in.n_files] : 0;
+  std::vector<std::unique_ptr<uint8_t[]>> blocks;
+  std::vector<const uint8_t*> run_base;
+  for (const GranuleRun& r : P.runs) {
+    const uint64_t a = r.g0 * kFetchGranule, b = std::min(r.g1 * kFetchGranule, n_bytes);
+    blocks.emplace_back(new uint8_t[size_t(b - a)]);
+    std::memcpy(blocks.back().get(), in.host_arena + a, size_t(b - a));
+    run_base.push_back(blocks.back().get());
+  }
+  SparseBatch sb;
+  std::vector<const uint8_t*> fdata;
+  std::vector<uint64_t> flen;
+  BuildSparse(P, run_base, in.host_offsets, in.n_files, &sb, &fdata, &flen);
+  sb.findings_arena = in.host_arena;
+  sb.fetch_whole = [&](const std::vector<uint8_t>& want, std::vector<const uint8_t*>* data, std::shared_ptr<void>*,
+                       uint64_t*, std::string*) {
+    data->assign(in.n_files, nullptr);
+    for (uint32_t f = 0; f < in.n_files; f++)
+      if (want[f]) (*data)[f] = in.host_arena + in.host_offsets[f];
+    return true;
+  };
+  *ws = FetchWindowStats();
+  ws->mode_used = 1;
+  ws->granules = P.granules;
+  ws->runs = P.runs.size();
+  ws->window_bytes = P.packed_bytes();
+  BatchInput tin = in;
+  tin.host_arena = nullptr;  // the exact pass has the blocks only
+  tin.file_data = fdata.data();
+  tin.file_len = flen.data();
+  tin.sparse = &sb;
+  tin.window_stats = ws;
+  return HostTail(tin, cands, out, hs, nullptr, true, err);
 }
 
 std::vector<uint8_t> SecretScanner::AllowedPaths(const BatchInput& in) const {
@@ -1792,6 +2029,7 @@ bool SecretScanner::HostTail(const BatchInput& in, std::vector<Candidate>* cands
     const uint32_t f = group_file(k);
     if (allowed[f]) return;
     __builtin_prefetch(in.paths[f]);
+    if (in.sparse && in.sparse->sparse[f]) return;  // (only its pieces exist: no address to prefetch by offset)
     const uint8_t* data = in.file_data ? in.file_data[f] : in.host_arena + in.host_offsets[f];
     const int64_t len = int64_t(in.file_data ? in.file_len[f] : in.host_offsets[f + 1] - in.host_offsets[f]);
     for (size_t q = a; q < b && q < a + 4; q++) {
@@ -1823,6 +2061,18 @@ bool SecretScanner::HostTail(const BatchInput& in, std::vector<Candidate>* cands
   const int gf_mode = gpu_findings_.load();
   const bool gpu_mat = mat_ && gpu_windows && (gf_mode == 1 || (gf_mode == 2 && host_bound_.load())) &&
                        in.dev_arena && in.dev_offsets && (!in.file_data || in.file_data_is_arena);
+  // Sparse files (the windows fetch): matched from their pieces, their findings made from the
+  // resident arena whatever the findings mode; the ones the pieces cannot answer are fetched
+  // whole after the pass and scanned as every other file (whole_data).
+  const SparseBatch* SB = in.sparse;
+  std::vector<uint8_t> need_whole(SB ? nf : 0, 0);
+  std::atomic<uint64_t> n_sparse{0};
+  if (SB && !SB->findings_arena && !(mat_ && in.dev_arena && in.dev_offsets)) {
+    *err = "windows fetch: the findings of sparse files need the GPU findings pass over a resident arena";
+    GiveScratch(std::move(scr));
+    return false;
+  }
+  const std::vector<const uint8_t*>* whole_data = nullptr;
   auto scan_group = [&](size_t k) {
     const size_t a = starts[k], b = starts[k + 1];
     const uint32_t f = group_file(k);
@@ -1849,18 +2099,47 @@ bool SecretScanner::HostTail(const BatchInput& in, std::vector<Candidate>* cands
     const uint8_t* data = in.file_data ? in.file_data[f] : in.host_arena + in.host_offsets[f];
     const int64_t len = int64_t(in.file_data ? in.file_len[f] : in.host_offsets[f + 1] - in.host_offsets[f]);
     const bool bin = in.binary && in.binary[f];
+    if (SB && SB->sparse[f]) {
+      if (whole_data) {
+        data = (*whole_data)[f];  // fetched whole after all: the usual path below
+      } else {
+        const SparseFile sf{SB->pieces.data() + SB->first[f], size_t(SB->first[f + 1] - SB->first[f])};
+        const std::string_view path(p, pn);
+        if (!MatchFile(nullptr, len, path, t_group.data(), t_group.size(), gpu_windows, &sf)) {
+          need_whole[k] = 1;
+          return;
+        }
+        if (t_scan.matched.empty()) {
+          n_sparse++;
+          return;
+        }
+        if (bin) {  // (Match from the path and title, Code{}: the host makes it, from the whole file)
+          need_whole[k] = 1;
+          return;
+        }
+        if (SB->findings_arena)
+          FindingsHost(SB->findings_arena + in.host_offsets[f], len, path, bin, t_group.data(), t_group.size(), &tmp[k]);
+        else if (!GpuFindingsInput(nullptr, t_group.data(), t_group.size(), &tmp[k], &sf)) {
+          tmp[k].gpu = false;
+          need_whole[k] = 1;
+          return;
+        }
+        n_sparse++;
+        return;
+      }
+    }
     if (!gpu_mat) {
       ScanFile(data, len, std::string_view(p, pn), bin, t_group.data(), t_group.size(), &tmp[k], gpu_windows);
       return;
     }
     PhaseTimer pt_all(7);
-    MatchFile(data, len, std::string_view(p, pn), t_group.data(), t_group.size(), gpu_windows);
+    (void)MatchFile(data, len, std::string_view(p, pn), t_group.data(), t_group.size(), gpu_windows);
     if (t_scan.matched.empty()) return;
     if (bin) {  // (Code{}, Match from the path and title: nothing for the GPU)
       FindingsHost(data, len, std::string_view(p, pn), bin, t_group.data(), t_group.size(), &tmp[k]);
       return;
     }
-    GpuFindingsInput(data, t_group.data(), t_group.size(), &tmp[k]);
+    (void)GpuFindingsInput(data, t_group.data(), t_group.size(), &tmp[k]);
   };
   // no other scan in flight (the end of a run): the pool's spare workers join in,
   // the last scan's exact pass being all that is left (TSG_DRAIN_WIDE=0: never;
@@ -1883,9 +2162,46 @@ bool SecretScanner::HostTail(const BatchInput& in, std::vector<Candidate>* cands
       scan_group(order[kk]);
     }
   }, wide);
+  if (SB) {  // the files the sparse pass could not answer: whole, through the usual path
+    std::vector<uint32_t> again;
+    std::vector<uint8_t> want(in.n_files, 0);
+    uint64_t fb_bytes = 0;
+    for (size_t k = 0; k < nf; k++)
+      if (need_whole[k]) {
+        const uint32_t f = group_file(k);
+        again.push_back(uint32_t(k));
+        want[f] = 1;
+        fb_bytes += in.host_offsets[f + 1] - in.host_offsets[f];
+      }
+    std::vector<const uint8_t*> data;
+    std::shared_ptr<void> keep;
+    uint64_t direct = 0;
+    const double f0 = NowMs();
+    if (!again.empty()) {
+      if (!SB->fetch_whole || !SB->fetch_whole(want, &data, &keep, &direct, err)) {
+        if (err->empty()) *err = "windows fetch: the whole-file fallback failed";
+        GiveScratch(std::move(scr));
+        return false;
+      }
+      whole_data = &data;
+      ParallelFor(again.size(), host_threads_, [&](size_t i) { scan_group(again[i]); }, wide);
+      whole_data = nullptr;
+    }
+    if (in.window_stats) {
+      uint64_t n_whole = 0;  // files with candidates whose bytes all came back with the windows
+      for (size_t k = 0; k < nf; k++) n_whole += !SB->sparse[group_file(k)] && !allowed[group_file(k)];
+      in.window_stats->whole_files = n_whole;
+      in.window_stats->sparse_files = n_sparse.load();
+      in.window_stats->fallback_files = again.size();
+      in.window_stats->fallback_bytes = fb_bytes;
+      in.window_stats->ms_fallback = again.empty() ? 0 : NowMs() - f0;
+      in.window_stats->fallback_direct = direct;
+    }
+    if (SB->findings_arena) SB = nullptr;  // (no GPU pass: the findings are made)
+  }
   const double t_par0 = NowMs();
   double ms_mat_gpu = 0;
-  if (gpu_mat && !GpuFindings(in, scr.get(), nf, [&](size_t k) { return group_file(k); }, thread_arena, wide,
+  if ((gpu_mat || SB) && !GpuFindings(in, scr.get(), nf, [&](size_t k) { return group_file(k); }, thread_arena, wide,
                               &ms_mat_gpu, err)) {
     GiveScratch(std::move(scr));
     return false;

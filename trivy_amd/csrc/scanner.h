@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -20,6 +21,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "fetch_layout.h"
 #include "materialize.h"
 #include "pathfilter.h"
 #include "goregex.h"
@@ -217,6 +219,40 @@ struct BatchResult {
   }
 };
 
+// A file of which only pieces are in host memory (the windows fetch of a
+// device-only batch, fetch_layout.h): file-relative bytes [lo, hi) at p, the
+// pieces ascending and apart.
+struct SparsePiece {
+  int64_t lo, hi;
+  const uint8_t* p;
+};
+struct SparseFile {
+  const SparsePiece* pieces;
+  size_t n;
+};
+// What the windows fetch did (tsg_fetch_window_stats).
+struct FetchWindowStats {
+  uint32_t mode_used = 0;
+  uint64_t granules = 0, runs = 0, window_bytes = 0, sparse_files = 0, whole_files = 0, fallback_files = 0,
+           fallback_bytes = 0;
+  uint64_t fallback_direct = 0;  // fallback files that took the direct route (tsg_fetch_stats.direct_files)
+  double ms_fallback = 0;
+};
+// The sparse files of a batch and what the exact pass needs beside them.
+struct SparseBatch {
+  std::vector<SparsePiece> pieces;  // every sparse file's pieces, in file order
+  std::vector<uint32_t> first;      // n_files + 1: file f's pieces are [first[f], first[f + 1])
+  std::vector<uint8_t> sparse;      // per file: served from its pieces (else whole, through file_data)
+  // The files want[f] != 0 whole, for the ones the sparse pass could not answer: (*data)[f]
+  // points at file f's bytes, valid until `keep` is destroyed.
+  std::function<bool(const std::vector<uint8_t>& want, std::vector<const uint8_t*>* data,
+                     std::shared_ptr<void>* keep, uint64_t* direct_files, std::string* err)>
+      fetch_whole;
+  // tests (tsg_debug_sparse_tail): the whole bytes, for FindingsHost to stand in for the GPU
+  // findings pass -- the sparse files' findings are otherwise made from the resident arena
+  const uint8_t* findings_arena = nullptr;
+};
+
 struct BatchInput {
   uint32_t n_files = 0;
   const uint8_t* host_arena = nullptr;  // the exact pass reads it; NULL with dev_arena: a device-only batch
@@ -244,6 +280,12 @@ struct BatchInput {
   // in page-locked, device-mapped memory; the engine gathers them on the GPU (GpuEngine::RunHost)
   const uint8_t* gather_base = nullptr;
   const uint64_t* gather_src = nullptr;
+  // optional: the windows fetch's sparse files (their file_data is unused) and where HostTail counts
+  const SparseBatch* sparse = nullptr;
+  FetchWindowStats* window_stats = nullptr;
+  // the fetch options this scan was submitted under (-1: the scanner's, as Scan finds them)
+  int fetch_windows = -1;
+  FetchWinParams fetch_prm;
 };
 
 struct HostStats {
@@ -276,7 +318,20 @@ class SecretScanner {
 
   // Thread-safe: concurrent scans report failures through *err only (no shared state).
   bool Scan(const BatchInput& in, BatchResult* out, BatchStats* gst, HostStats* hst, std::string* err,
-            FetchStats* fst = nullptr);
+            FetchStats* fst = nullptr, FetchWindowStats* wst = nullptr);
+  // How device-only batches' bytes come back (tsg_fetch_options): windows != 0 the windows fetch
+  // (fetch_layout.h); takes effect with the next scan submitted.  TSG_FETCH_MODE=windows at
+  // creation sets the initial mode.
+  void SetFetchOptions(bool windows, const FetchWinParams& prm) {
+    std::lock_guard<std::mutex> g(fetch_opt_mu_);
+    fetch_windows_ = windows;
+    fetch_prm_ = prm;
+  }
+  bool GetFetchOptions(FetchWinParams* prm) const {
+    std::lock_guard<std::mutex> g(fetch_opt_mu_);
+    *prm = fetch_prm_;
+    return fetch_windows_;
+  }
   // The exact host tail over a given candidate list (what Scan runs after the GPU).
   // The exact host pass over the GPU's candidates.  `allowed` (per-file
   // global AllowPath results) is computed here when not supplied.
@@ -287,6 +342,15 @@ class SecretScanner {
   bool HostTail(const BatchInput& in, std::vector<Candidate>* cands, BatchResult* out, HostStats* hs,
                 const std::vector<uint8_t>* allowed = nullptr, bool gpu_windows = false,
                 std::string* err = nullptr) const;
+  // The windows fetch's host side without a GPU (tsg_debug_sparse_tail): the windows of the
+  // given candidates planned on a host batch, each run of marked granules copied into a block
+  // of its own size (the pack kernel's stand-in; a read outside a run is outside an
+  // allocation), the sparse exact pass on those blocks alone, the fallback from the host
+  // arena, the findings by FindingsHost on the whole bytes (the GPU findings pass's stand-in).
+  bool SparseTail(const BatchInput& in, std::vector<Candidate>* cands, const FetchWinParams& prm, BatchResult* out,
+                  HostStats* hs, FetchWindowStats* ws, std::string* err) const;
+  // RuleGpu::max_len per compiled rule (the exclude-block rules included)
+  std::vector<uint32_t> RuleMaxLens() const;
   std::vector<uint8_t> AllowedPaths(const BatchInput& in) const;
   // Global.AllowPath (scanner.go:57-59)
   bool AllowPath(const uint8_t* p, size_t n) const;
@@ -305,12 +369,14 @@ class SecretScanner {
   // ScanFile in two parts: the surviving locations of the rules (scanner.go:394-436)
   // into the calling thread's scratch (matched, censor), then toFinding /
   // findLocation / sort on the host (:438-457) from them
-  void MatchFile(const uint8_t* content, int64_t len, std::string_view path, const Candidate* c, size_t nc,
-                 bool gpu_windows) const;
+  // sp: the file is sparse (content unused); false: the pieces do not answer it, scan the whole file
+  bool MatchFile(const uint8_t* content, int64_t len, std::string_view path, const Candidate* c, size_t nc,
+                 bool gpu_windows, const SparseFile* sp = nullptr) const;
   void FindingsHost(const uint8_t* content, int64_t len, std::string_view path, bool binary, const Candidate* c,
                     size_t nc, FileResult* out) const;
   // the GPU materialisation's uploads of one file (materialize.h), from the scratch of MatchFile
-  void GpuFindingsInput(const uint8_t* content, const Candidate* c, size_t nc, FileResult* out) const;
+  bool GpuFindingsInput(const uint8_t* content, const Candidate* c, size_t nc, FileResult* out,
+                        const SparseFile* sp = nullptr) const;
   // HostTail's serial set-up buffers (the per-file counts, the grouped
   // candidates, the dispatch order), kept across calls: allocated per call,
   // their first touch (page faults on ~10 MB) was most of the set-up's time.
@@ -374,6 +440,9 @@ class SecretScanner {
   std::unique_ptr<PathFilter> path_filter_;
   std::unique_ptr<FindingMaterializer> mat_;  // GPU findings of HBM-resident batches
   std::atomic<int> gpu_findings_{0};
+  mutable std::mutex fetch_opt_mu_;
+  bool fetch_windows_ = false;
+  FetchWinParams fetch_prm_;
 
  public:
   // 1 / 0 / 2: GPU / host / auto (GPU while host-bound) findings for HBM-resident

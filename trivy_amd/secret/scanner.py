@@ -91,6 +91,22 @@ class _CFetchStats(c.Structure):  # tsg_fetch_stats (versioned: struct_size firs
 FETCH_STATS_SIZE_V1 = c.sizeof(_CFetchStats)  # TSG_FETCH_STATS_SIZE_V1
 
 
+class _CFetchOptions(c.Structure):  # tsg_fetch_options (versioned: struct_size first)
+    _fields_ = [("struct_size", c.c_uint32), ("mode", c.c_uint32), ("back_bytes", c.c_uint32),
+                ("fwd_bytes", c.c_uint32), ("fwd_cap", c.c_uint32), ("max_span", c.c_uint32)]
+
+
+class _CFetchWindowStats(c.Structure):  # tsg_fetch_window_stats (versioned: struct_size first)
+    _fields_ = [("struct_size", c.c_uint32), ("mode_used", c.c_uint32)] + \
+               [(n, c.c_uint64) for n in ("granules", "runs", "window_bytes", "sparse_files", "whole_files",
+                                          "fallback_files", "fallback_bytes")] + [("ms_fallback", c.c_double)]
+
+
+FETCH_OPTIONS_SIZE_V1 = c.sizeof(_CFetchOptions)            # TSG_FETCH_OPTIONS_SIZE_V1
+FETCH_WINDOW_STATS_SIZE_V1 = c.sizeof(_CFetchWindowStats)   # TSG_FETCH_WINDOW_STATS_SIZE_V1
+FETCH_MODES = ("files", "windows")                          # TSG_FETCH_FILES, TSG_FETCH_WINDOWS
+
+
 class _CTableInfo(c.Structure):
     _fields_ = [(n, c.c_uint32) for n in ("n_rules", "n_keywords", "n_anchors", "n_filter_items",
                                           "n_filter_buckets", "filter_window", "n_fullscan_rules",
@@ -117,6 +133,10 @@ def _declare(L):
     L.tsg_result_stats.argtypes = [c.c_void_p, c.POINTER(_CStats)]
     if hasattr(L, "tsg_result_fetch_stats"):
         L.tsg_result_fetch_stats.argtypes = [c.c_void_p, c.POINTER(_CFetchStats)]
+    if hasattr(L, "tsg_scanner_set_fetch_options"):
+        L.tsg_scanner_set_fetch_options.argtypes = [c.c_void_p, c.POINTER(_CFetchOptions)]
+        L.tsg_scanner_get_fetch_options.argtypes = [c.c_void_p, c.POINTER(_CFetchOptions)]
+        L.tsg_result_fetch_window_stats.argtypes = [c.c_void_p, c.POINTER(_CFetchWindowStats)]
     if hasattr(L, "tsg_result_records"):
         L.tsg_result_records.argtypes = [c.c_void_p, c.c_void_p, c.c_uint64]
         L.tsg_result_records.restype = c.c_uint64
@@ -454,6 +474,29 @@ class Scanner:
         self._L.tsg_debug_scanner_fetch.argtypes = [c.c_void_p, c.c_uint64, c.c_uint64]
         return self._L.tsg_debug_scanner_fetch(self._h, int(stage_bytes), int(direct_bytes))
 
+    def set_fetch_mode(self, mode, back=None, fwd=None, fwd_cap=None, max_span=None):
+        """How device-only batches' bytes come back for the exact pass (tsg_scanner_set_fetch_options):
+        "files" (the default: the candidate files, whole) or "windows" (the 256-B granules around the
+        candidates; `back` bytes before a candidate's window, after it the rule's longest match + 4
+        where that is at most `fwd_cap`, else `fwd`; a window wider than `max_span` brings the whole
+        file).  None: the default.  Takes effect with the next scan submitted; results never depend
+        on it (ScanResult.fetch_window_stats() says what it did)."""
+        if mode not in FETCH_MODES:
+            raise ValueError("set_fetch_mode: mode must be one of %s" % (FETCH_MODES,))
+        o = _CFetchOptions(FETCH_OPTIONS_SIZE_V1, FETCH_MODES.index(mode), int(back or 0), int(fwd or 0),
+                           int(fwd_cap or 0), int(max_span or 0))
+        if self._L.tsg_scanner_set_fetch_options(self._h, c.byref(o)) != 0:
+            raise ValueError("tsg_scanner_set_fetch_options failed: %s" % _lib.last_error(self._L))
+
+    def fetch_options(self):
+        """The effective fetch options: mode ("files" / "windows"), back, fwd, fwd_cap, max_span."""
+        o = _CFetchOptions()
+        o.struct_size = FETCH_OPTIONS_SIZE_V1
+        if self._L.tsg_scanner_get_fetch_options(self._h, c.byref(o)) != 0:
+            raise RuntimeError("tsg_scanner_get_fetch_options failed: %s" % _lib.last_error(self._L))
+        return {"mode": FETCH_MODES[o.mode], "back": o.back_bytes, "fwd": o.fwd_bytes, "fwd_cap": o.fwd_cap,
+                "max_span": o.max_span}
+
     def set_gpu_findings(self, mode) -> int:
         """Findings of HBM-resident batches on the GPU (materialize.h; True / 1), on the host
         (False / 0, the default) or on the GPU while the exact pass is the bound (2)
@@ -523,6 +566,17 @@ class ScanResult:
         s.struct_size = FETCH_STATS_SIZE_V1
         if self._sc._L.tsg_result_fetch_stats(self._h, c.byref(s)) != 0:
             raise RuntimeError("tsg_result_fetch_stats failed: %s" % _lib.last_error(self._sc._L))
+        return {k: getattr(s, k) for k, _ in s._fields_ if k != "struct_size"}
+
+    def fetch_window_stats(self):
+        """What the windows fetch of this scan did (tsg_result_fetch_window_stats): mode_used (0: the
+        batch went the files route -- a host arena, a transform, or the mode off -- and the rest is
+        zero), granules, runs, window_bytes, sparse_files, whole_files, fallback_files, fallback_bytes,
+        ms_fallback."""
+        s = _CFetchWindowStats()
+        s.struct_size = FETCH_WINDOW_STATS_SIZE_V1
+        if self._sc._L.tsg_result_fetch_window_stats(self._h, c.byref(s)) != 0:
+            raise RuntimeError("tsg_result_fetch_window_stats failed: %s" % _lib.last_error(self._sc._L))
         return {k: getattr(s, k) for k, _ in s._fields_ if k != "struct_size"}
 
     def raw(self, lo=None, hi=None):

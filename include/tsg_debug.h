@@ -166,6 +166,23 @@ int tsg_debug_sparse_tail(const struct tsg_global* g, const struct tsg_batch* ba
                           uint64_t n_cands, const uint32_t* opts, struct tsg_result** out,
                           struct tsg_fetch_window_stats* window_stats);
 
+/* ---- scans that skip allow-listed files (trivy_amd/csrc/pathfilter.h) ----
+ * The GPU's "surely allowed" decision on the host: the table is built from the
+ * exact literal forms of the given path regexes (the same builder the scanner
+ * uses for its global allow rules) and run over the n_paths paths packed in
+ * `paths` (path i is bytes off[i] .. off[i + 1]).  sure[i]: 1 when path i is
+ * surely allowed.  has_form[r] (optional): 1 when pattern r has an exact
+ * literal form.  <0: a pattern does not compile. */
+int tsg_debug_sure_allow(const char* const* patterns, uint32_t n_patterns, const uint8_t* paths, const uint64_t* off,
+                         uint32_t n_paths, uint8_t* sure, uint8_t* has_form);
+/* What a scan's skip list did: out = {files marked, bytes in them, 4-KiB tiles
+ * the streaming filter left out, runs of kept tiles, the most runs one of its
+ * waves walked, the arena's tiles}.  All zero for a scan without one (no packed
+ * paths, no rule with an exact form, TSG_GPU_SKIP_ALLOWED=0, a host arena or a
+ * transform).  TSG_DIAG_K1_GRID=<n> at scanner creation caps the filter's grid
+ * at n workgroups, so a small arena still gives a wave many tiles. */
+int tsg_debug_result_skip(const struct tsg_result* r, uint64_t out[6]);
+
 /* Thread-local text of the last error. */
 const char* tsg_last_error(void);
 

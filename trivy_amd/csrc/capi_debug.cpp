@@ -375,4 +375,31 @@ int tsg_debug_sparse_tail(const tsg_global* g, const tsg_batch* b, const void* c
 }
 
 int tsg_debug_pool_budget(void) { return tsg::PoolBudget(); }
+
+int tsg_debug_sure_allow(const char* const* patterns, uint32_t n_patterns, const uint8_t* paths, const uint64_t* off,
+                         uint32_t n_paths, uint8_t* sure, uint8_t* has_form) {
+  std::vector<std::unique_ptr<tsg::Regex>> own;
+  std::vector<const tsg::Regex*> res;
+  for (uint32_t i = 0; i < n_patterns; i++) {
+    std::string err;
+    own.push_back(tsg::Regex::Compile(patterns[i], &err));
+    if (!own.back()) {
+      tsg::SetError(err);
+      return -1;
+    }
+    res.push_back(own.back().get());
+  }
+  tsg::SureTable t;
+  std::vector<uint8_t> form;
+  tsg::SureTableOf(res, &t, &form);  // (none / no fit: words = 0, nothing is surely allowed)
+  if (has_form && n_patterns) std::memcpy(has_form, form.data(), n_patterns);
+  for (uint32_t i = 0; i < n_paths; i++) sure[i] = tsg::SureAllowHost(t, paths + off[i], off[i + 1] - off[i]) ? 1 : 0;
+  return 0;
+}
+
+int tsg_debug_result_skip(const struct tsg_result* r, uint64_t out[6]) {
+  if (!r) return -1;
+  std::memcpy(out, r->skip, sizeof(r->skip));
+  return 0;
+}
 }

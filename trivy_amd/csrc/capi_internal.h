@@ -17,6 +17,8 @@ struct tsg_result {
   tsg_stats stats;
   tsg::FetchStats fetch;  // tsg_result_fetch_stats (device-only batches; zero otherwise)
   tsg::FetchWindowStats win;  // tsg_result_fetch_window_stats (the windows fetch; zero otherwise)
+  // tsg_debug_result_skip: files marked, their bytes, tiles dropped, runs, most runs per K1 wave, tiles
+  uint64_t skip[6] = {0, 0, 0, 0, 0, 0};
   std::string json;        // tsg_result_json: every file (built once)
   std::string json_range;  // tsg_result_json_range: the last range asked for
   const tsg::SecretScanner* owner;

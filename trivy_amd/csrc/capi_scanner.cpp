@@ -405,6 +405,8 @@ int ScanImpl(tsg_scanner* s, const tsg_batch* b, const ExtFields& x, tsg_result*
   st.fullscan_pairs = gs.fullscan_tasks;
   st.fold_sites = gs.fold_sites;
   st.ms_xform_kernel = gs.ms_xform;
+  const uint64_t sk[6] = {gs.skip_files, gs.skip_bytes, gs.skip_tiles, gs.skip_runs, gs.skip_wave_runs, gs.tiles};
+  std::memcpy(r->skip, sk, sizeof(sk));
   *out = r.release();
   return 0;
 }

@@ -115,6 +115,19 @@ struct BatchStats {
   float ms_xform = 0;     // RunHost with kinds: pre-transform kernels (part of ms_total)
   uint64_t h2d_chunks = 0;
   bool hit_overflow = false, cand_overflow = false;
+  // a scan with a skip list (SkipIn): the files marked and their bytes, the 4-KiB tiles K1 left out,
+  // the runs of kept tiles, the most runs one K1 wave walked, the arena's tiles
+  uint64_t skip_files = 0, skip_bytes = 0, skip_tiles = 0, skip_runs = 0, skip_wave_runs = 0, tiles = 0;
+};
+
+// Files whose bytes the result does not need: d_skip[f] != 0
+// for a file whose path is surely allow-listed (pathfilter.h).  The engine's
+// stream waits for `ready` before K0; the bytes stay readable until the scan's
+// GPU phase is over.  K1 then streams only the 4-KiB tiles that hold a byte of
+// some other file, and the full scan makes no pair for a marked file.
+struct SkipIn {
+  const uint8_t* d_skip = nullptr;
+  hipEvent_t ready = nullptr;
 };
 
 class GpuEngine {
@@ -132,7 +145,7 @@ class GpuEngine {
   // With fetch (a device-only batch): the candidate files' bytes are brought
   // back too, sized exactly (the candidates are known before the fetch is issued).
   bool Run(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
-           std::vector<Candidate>* cands, BatchStats* st, FetchOut* fetch = nullptr);
+           std::vector<Candidate>* cands, BatchStats* st, FetchOut* fetch = nullptr, const SkipIn* skip = nullptr);
   // The files want[f] != 0 of a device-resident arena into *out (synchronous;
   // the caller holds the engine's lock).  For the files a GPU pre-transform of
   // resident bytes left as they were read.
@@ -192,7 +205,7 @@ class GpuEngine {
     uint32_t cand_copy = 0;  // candidates copied back
   };
   bool Enqueue(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files, Ticket* t,
-               std::string* err, FetchOut* fetch = nullptr);
+               std::string* err, FetchOut* fetch = nullptr, const SkipIn* skip = nullptr);
   bool Collect(Ticket* t, std::vector<Candidate>* cands, BatchStats* st, bool* rerun, std::string* err,
                FetchOut* fetch = nullptr);
 
@@ -212,12 +225,14 @@ class GpuEngine {
  private:
   bool Ensure(void** p, size_t* cap, size_t need);
   bool EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
-                    uint64_t n_chunks, hipEvent_t* ev, hipEvent_t ev_fs);
+                    uint64_t n_chunks, hipEvent_t* ev, hipEvent_t ev_fs, const SkipIn* skip = nullptr);
   void InitCaps(uint64_t n_bytes);
   struct Slot {  // one in-flight Enqueue: its phase events and pinned read-back buffers
     hipEvent_t ev[7] = {};
     hipEvent_t ev_fs = nullptr, done = nullptr;
     uint32_t* h_cnt = nullptr;
+    uint32_t* h_skip = nullptr;  // pinned copy of the skip counters (d_skip_info_), scans with a skip list
+    bool has_skip = false;
     Candidate* h_cands = nullptr;
     size_t h_cap = 0;
     bool busy = false, has_fs = false;
@@ -351,6 +366,15 @@ class GpuEngine {
   // per-batch buffers
   void* d_chunk_file_ = nullptr; size_t cap_chunk_file_ = 0;
   void* d_nl_ = nullptr; size_t cap_nl_ = 0;
+  // scans with a skip list: the kept-tile bitmap, the runs of kept tiles (begin tile, kept tiles before),
+  // and 16 counters: [0] runs [1] kept tiles [2] last tile kept [3] files marked [4,5] their bytes (u64)
+  // [6] most runs walked by a K1 wave [7] tiles
+  void* d_keep_bits_ = nullptr; size_t cap_keep_bits_ = 0;
+  void* d_runs_ = nullptr; size_t cap_runs_ = 0;
+  uint32_t* d_skip_info_ = nullptr;
+  uint32_t* h_run_skip_ = nullptr;  // pinned (Run)
+  uint32_t k1_grid_cap_ = 0;        // TSG_DIAG_K1_GRID: at most this many K1 workgroups (tests; 0: no cap)
+  void NoteSkip(const uint32_t* info, BatchStats* st) const;
   void* d_kw_ = nullptr; size_t cap_kw_ = 0;
   void* d_flags_ = nullptr; size_t cap_flags_ = 0;
   void* d_hits_ = nullptr; size_t cap_hits_ = 0;

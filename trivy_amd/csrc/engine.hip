@@ -1,6 +1,9 @@
 // gfx950 kernels of the secret-scanning hot path.
 //
 //  K0 chunk_map   : 1-KiB chunk -> file index (one thread per file)
+//  tile_keep/runs : scans with a skip list (allow-listed files, §4.9) only: the
+//                   4-KiB tiles that hold a byte of a file that is not skipped,
+//                   as runs of kept tiles; K1 then streams those alone.
 //  K1 filter      : streams every arena byte once (64 B per lane per tile);
 //                   bucketed shift-or over 15 item buckets + a newline bucket
 //                   (reach table replicated 16x in LDS); records the flagged
@@ -74,6 +77,7 @@ struct ClearParams {
   uint64_t n_kw;       // words of kw
   uint32_t* counters;  // 16
   uint32_t* fs_ctr;    // 16, or null
+  uint32_t* skip_info; // 16, or null (scans with a skip list)
 };
 __device__ __forceinline__ void clear_words(uint32_t* p, uint64_t n, uint64_t tid, uint64_t nthr) {
   // hipMalloc'd buffers are 256-B aligned: 16-B stores, the last n % 4 words singly
@@ -91,6 +95,7 @@ __global__ __launch_bounds__(256) void chunk_map_kernel(const uint64_t* __restri
     if (tid < 16) {
       Z.counters[tid] = 0;
       if (Z.fs_ctr) Z.fs_ctr[tid] = 0;
+      if (Z.skip_info) Z.skip_info[tid] = 0;
     }
   }
   const uint64_t n_runs = (n_chunks + kK0Run - 1) / kK0Run;
@@ -165,9 +170,167 @@ constexpr uint32_t kNlBits = 0x8888u;        // newline bucket (15 = register 3,
 static_assert(kChunk % kFLane == 0 && kChunk / kFLane <= 64, "a newline chunk must be whole lane chunks");
 static_assert(kFChunks * kChunk == kFTile && kFChunks == 4, "a tile's newline counts are one u64");
 
+// ---------------------------------------------------------------------------
+// Scans with a skip list: the tiles K1 streams
+// ---------------------------------------------------------------------------
+// Counters of such a scan (engine.h d_skip_info_), cleared by K0.
+constexpr uint32_t kSkRuns = 0, kSkKept = 1, kSkTailKept = 2, kSkFiles = 3, kSkBytes = 4 /* u64: 4, 5 */,
+                   kSkWaveRuns = 6, kSkTiles = 7;
+
+// The bitmap's words, rounded up to whole 64-B groups (tile_runs_kernel reads a group per step).
+constexpr uint32_t kRunWords = 8;
+__host__ __device__ inline uint64_t KeepWords(uint64_t n_tiles) {
+  return ((n_tiles + 63) / 64 + kRunWords - 1) / kRunWords * kRunWords;
+}
+
+// One lane per tile: the tile is kept when a byte of it belongs to a file that
+// is not marked -- dropped only when every byte of it lies in marked files
+// (several adjacent ones may cover it together; empty files hold no byte).
+// A wave's ballot is one word of the bitmap.  Also counts the marked files and
+// their bytes.
+__global__ __launch_bounds__(256) void tile_keep_kernel(const uint64_t* __restrict__ off, uint32_t n_files,
+                                                        const uint32_t* __restrict__ chunk_file,
+                                                        const uint8_t* __restrict__ skip, uint64_t n_bytes,
+                                                        uint64_t n_tiles, uint64_t* __restrict__ keep_bits,
+                                                        uint32_t* __restrict__ info) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
+  // (the bitmap is written up to a multiple of kRunWords words: zeros past the last tile)
+  const uint64_t n_padded = KeepWords(n_tiles) * 64;
+  for (uint64_t base = uint64_t(blockIdx.x) * blockDim.x + (threadIdx.x & ~63u); base < n_padded; base += stride) {
+    const uint64_t t = base + lane;
+    bool keep = false;
+    if (t < n_tiles) {
+      const uint64_t ts = t * kFTile, te = ts + kFTile < n_bytes ? ts + kFTile : n_bytes;
+      uint32_t f = chunk_file[t * kFChunks];  // the file holding byte ts (never an empty one)
+      for (;;) {                              // the files with a byte in [ts, te)
+        const uint64_t fb = off[f], fe = off[f + 1];
+        if (fe > fb && !skip[f]) {
+          keep = true;
+          break;
+        }
+        if (fe >= te || f + 1 >= n_files) break;
+        f++;
+      }
+    }
+    const uint64_t m = __ballot(keep);
+    if (lane == 0) keep_bits[base / 64] = m;
+  }
+  // the marked files and their bytes (diagnostics): the first kStatBlocks workgroups only, one
+  // atomic pair per wave -- a pair per wave of the whole grid, 32 K atomics on two addresses,
+  // took 0.2 ms of this kernel's 0.3 on C2
+  constexpr uint32_t kStatBlocks = 64;
+  if (blockIdx.x >= kStatBlocks) return;
+  const uint64_t fstride = uint64_t(gridDim.x < kStatBlocks ? gridDim.x : kStatBlocks) * blockDim.x;
+  uint32_t nf = 0;
+  uint64_t nb = 0;
+  for (uint64_t f = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; f < n_files; f += fstride)
+    if (skip[f]) {
+      nf++;
+      nb += off[f + 1] - off[f];
+    }
+#pragma unroll
+  for (int x = 1; x < 64; x <<= 1) {
+    nf += __shfl_xor(nf, x);
+    nb += __shfl_xor(nb, x);
+  }
+  if (lane == 0 && nf) {
+    atomicAdd(&info[kSkFiles], nf);
+    atomicAdd(reinterpret_cast<unsigned long long*>(&info[kSkBytes]), static_cast<unsigned long long>(nb));
+  }
+}
+
+// One workgroup: the bitmap -> the list of runs of kept tiles, runs[i] =
+// (first tile, kept tiles before it), closed by (n_tiles, kept tiles).  Each
+// thread owns a contiguous slice of the words: counts, a workgroup prefix sum,
+// then the slice's runs written at their places.  (78 K words for a 20-GB
+// arena: two passes over 0.6 MB.)
+constexpr int kRunThreads = 1024;
+__global__ __launch_bounds__(kRunThreads) void tile_runs_kernel(const uint64_t* __restrict__ keep_bits,
+                                                                uint64_t n_tiles, uint2* __restrict__ runs,
+                                                                uint32_t* __restrict__ info) {
+  __shared__ uint32_t s_k[kRunThreads / 64], s_r[kRunThreads / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+  // a slice is whole 64-B groups of words, each read with four 16-B loads issued together (a
+  // load per word, 600 B apart across the lanes, made the kernel a chain of 150 exposed L2
+  // latencies: 0.15 ms on C2); the words past the last tile are zero (tile_keep_kernel)
+  const uint64_t n_words = KeepWords(n_tiles);
+  const uint64_t per = ((n_words / kRunWords + kRunThreads - 1) / kRunThreads) * kRunWords;
+  const uint64_t w0 = per * tid < n_words ? per * tid : n_words;
+  const uint64_t w1 = w0 + per < n_words ? w0 + per : n_words;
+  const uint64_t carry0 = w0 > 0 && w0 < n_words ? keep_bits[w0 - 1] >> 63 : 0;
+  auto load_group = [&](uint64_t w, uint64_t* b) {
+    const uint4* g = reinterpret_cast<const uint4*>(keep_bits + w);
+#pragma unroll
+    for (uint32_t q = 0; q < kRunWords / 2; q++) {
+      const uint4 v = g[q];
+      b[2 * q] = uint64_t(v.x) | (uint64_t(v.y) << 32);
+      b[2 * q + 1] = uint64_t(v.z) | (uint64_t(v.w) << 32);
+    }
+  };
+  uint32_t kept = 0, starts = 0;
+  uint64_t carry = carry0;
+  for (uint64_t w = w0; w < w1; w += kRunWords) {
+    uint64_t g[kRunWords];
+    load_group(w, g);
+#pragma unroll
+    for (uint32_t q = 0; q < kRunWords; q++) {
+      const uint64_t b = g[q];
+      kept += uint32_t(__popcll(b));
+      starts += uint32_t(__popcll(b & ~((b << 1) | carry)));
+      carry = b >> 63;
+    }
+  }
+  // exclusive prefix over the threads: a shuffle scan per wave, the waves' totals through LDS
+  uint32_t ik = kept, ir = starts;
+#pragma unroll
+  for (int x = 1; x < 64; x <<= 1) {
+    const uint32_t a = __shfl_up(ik, x), b = __shfl_up(ir, x);
+    if (lane >= uint32_t(x)) {
+      ik += a;
+      ir += b;
+    }
+  }
+  if (lane == 63) {
+    s_k[wv] = ik;
+    s_r[wv] = ir;
+  }
+  __syncthreads();
+  uint32_t bk = 0, br = 0;
+  for (uint32_t q = 0; q < wv; q++) {
+    bk += s_k[q];
+    br += s_r[q];
+  }
+  uint32_t k = bk + ik - kept, r = br + ir - starts;
+  carry = carry0;
+  for (uint64_t w = w0; w < w1; w += kRunWords) {
+    uint64_t g[kRunWords];
+    load_group(w, g);
+#pragma unroll
+    for (uint32_t q = 0; q < kRunWords; q++) {
+      const uint64_t b = g[q];
+      for (uint64_t s = b & ~((b << 1) | carry); s; s &= s - 1) {
+        const uint32_t bit = uint32_t(__builtin_ctzll(s));
+        runs[r++] = make_uint2(uint32_t((w + q) * 64 + bit), k + uint32_t(__popcll(b & ((uint64_t(1) << bit) - 1))));
+      }
+      k += uint32_t(__popcll(b));
+      carry = b >> 63;
+    }
+  }
+  if (tid == kRunThreads - 1) {  // (k, r: the totals)
+    runs[r] = make_uint2(uint32_t(n_tiles), k);
+    info[kSkRuns] = r;
+    info[kSkKept] = k;
+    info[kSkTailKept] = n_tiles ? uint32_t((keep_bits[(n_tiles - 1) / 64] >> ((n_tiles - 1) & 63)) & 1) : 0u;
+    info[kSkTiles] = uint32_t(n_tiles);
+  }
+}
+
 struct FilterParams {
   const uint8_t* arena;
   uint64_t n_bytes;
+  const uint2* runs;      // scans with a skip list: the runs of kept tiles (tile_runs_kernel); else null
+  uint32_t* run_info;     // ... and their counters (kSk*)
   const uint32_t* reach;  // 256 x 4 u32 (filter.h layout)
   uint32_t diag_mode;     // TSG_DIAG_SCAN: 2 skips the filter (loads + newline count only)
   uint16_t* nl;           // '\n' per 1-KiB chunk
@@ -223,6 +386,10 @@ __device__ __forceinline__ void load_reach_lds(uint8_t* s_reach, const uint32_t*
 // the confirm kernel (K2) checks them exactly.
 // (<= 64 VGPRs in both shapes: with one workgroup per CU the other half of the
 // VGPRs and LDS go to a concurrent scan's confirm kernel)
+// kRuns: the scan has a skip list (P.runs).  Without one the kernel is the
+// instantiation with the plain loop over a contiguous tile range: the run walk's
+// scalar bookkeeping cost that loop 3 % (5.35 -> 5.5 ms on C2) when both shared one.
+template <bool kRuns>
 __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P) {
   __shared__ __attribute__((aligned(16))) uint8_t s_reach[65536];
   __shared__ uint32_t s_queue[kScanWaves * kFQueue];
@@ -240,19 +407,58 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
   // Each wave streams one contiguous range of tiles, so lane 0's 8-byte
   // prefix is lane 63's last 8 bytes of the wave's previous tile (carried in
   // scalar registers) -- only the range's first tile loads it.
+  // With a skip list (P.runs) the tiles are the kept ones only, numbered
+  // through the runs of kept tiles: each wave takes an equal share of the kept
+  // tiles, finds its first run by binary search and walks the runs.  Without
+  // one the arena is a single run and the walk never leaves it.
   const uint64_t n_tiles = (P.n_bytes + kFTile - 1) / kFTile;
   const uint64_t n_waves = uint64_t(gridDim.x) * kScanWaves;
   const uint64_t wid = uint64_t(blockIdx.x) * kScanWaves + wave;
-  const uint64_t per = n_tiles / n_waves, extra = n_tiles % n_waves;
-  const uint64_t t_begin = wid * per + (wid < extra ? wid : extra);
-  const uint64_t t_end = t_begin + per + (wid < extra ? 1 : 0);
+  const uint2* __restrict__ RUNS = kRuns ? P.runs : nullptr;
+  // (what is loaded is the same in every lane: readfirstlane keeps the walk's state in scalar registers)
+  auto uni = [](uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(v)); };
+  const uint64_t n_kept = RUNS ? uint64_t(uni(P.run_info[kSkKept])) : n_tiles;
+  const bool tail_kept = RUNS ? uni(P.run_info[kSkTailKept]) != 0 : true;
+  const uint64_t per = n_kept / n_waves, extra = n_kept % n_waves;
+  const uint64_t k_begin = wid * per + (wid < extra ? wid : extra);
+  const uint64_t k_end = k_begin + per + (wid < extra ? 1 : 0);
+  uint32_t run = 0;             // wave-uniform: the run of the tile in hand
+  uint64_t run_k1 = n_kept;     // kept tiles before the next run
+  uint64_t t_begin = k_begin;   // the tile of kept index k_begin
+  uint32_t runs_walked = 1;
+  if (RUNS && k_begin < k_end) {
+    uint32_t lo = 0, hi = uni(P.run_info[kSkRuns]);  // the last run with kept-before <= k_begin
+    while (hi - lo > 1) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (uni(RUNS[mid].y) <= k_begin) lo = mid;
+      else hi = mid;
+    }
+    run = lo;
+    const uint2 r0 = RUNS[lo];
+    t_begin = uint64_t(uni(r0.x)) + (k_begin - uni(r0.y));
+    run_k1 = uni(RUNS[lo + 1].y);
+  }
   uint4 bufA[kFBlocks], bufB[kFBlocks];
   uint32_t pre_x = 0, pre_y = 0;  // wave-uniform: the 8 bytes before the current tile
-  if (t_begin < t_end && t_begin > 0) {
-    const uint2 pv = *reinterpret_cast<const uint2*>(P.arena + t_begin * kFTile - 8);
+  auto load_pre = [&](uint64_t tt) {  // tt > 0
+    const uint2 pv = *reinterpret_cast<const uint2*>(P.arena + tt * kFTile - 8);
     pre_x = __builtin_amdgcn_readfirstlane(pv.x);
     pre_y = __builtin_amdgcn_readfirstlane(pv.y);
-  }
+  };
+  if (k_begin < k_end && t_begin > 0) load_pre(t_begin);
+  // The tile after tile tcur, kept index k1: the next one of the run, or the
+  // first of the next run (*nr).  Scalar code; the loads it feeds stay unconditional.
+  auto next_tile = [&](uint64_t k1, uint64_t tcur, bool* nr) -> uint64_t {
+    if (k1 < run_k1) {
+      *nr = false;
+      return tcur + 1;
+    }
+    run++;
+    runs_walked++;
+    run_k1 = uni(RUNS[run + 1].y);
+    *nr = true;
+    return uni(RUNS[run].x);
+  };
   auto load_tile = [&](uint4* dst, uint64_t tt) {
     // One clamp per lane, no branch (a wave-uniform full-tile branch around
     // the loads cost 1.4 ms on C2): a lane chunk starting inside the arena is
@@ -446,33 +652,93 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
     if (qn >= kFFlushAt) flush();
   };
   using Full = std::false_type;
-  // whole tiles; the arena's partial last tile (if any) is the last of its wave's range
-  const uint64_t t_full = t_end < P.n_bytes / kFTile ? t_end : P.n_bytes / kFTile;
-  uint64_t t = t_begin;
-  // two register buffers alternate roles (no copies): tile t in A while t + 1 loads into B
-  if (t < t_full) load_tile(bufA, t);
-  while (t < t_full) {
-    flush_due();
-    load_tile(bufB, t + 1 < t_full ? t + 1 : t);  // past the range: a harmless reload
-    tile(bufA, t, Full());
-    t++;
-    if (t >= t_full) break;
-    flush_due();
-    load_tile(bufA, t + 1 < t_full ? t + 1 : t);
-    tile(bufB, t, Full());
-    t++;
+  if constexpr (!kRuns) {
+    // whole tiles; the arena's partial last tile (if any) is the last of its wave's range
+    const uint64_t t_end = k_end;
+    const uint64_t t_full = t_end < P.n_bytes / kFTile ? t_end : P.n_bytes / kFTile;
+    uint64_t t = t_begin;
+    // two register buffers alternate roles (no copies): tile t in A while t + 1 loads into B
+    if (t < t_full) load_tile(bufA, t);
+    while (t < t_full) {
+      flush_due();
+      load_tile(bufB, t + 1 < t_full ? t + 1 : t);  // past the range: a harmless reload
+      tile(bufA, t, Full());
+      t++;
+      if (t >= t_full) break;
+      flush_due();
+      load_tile(bufA, t + 1 < t_full ? t + 1 : t);
+      tile(bufB, t, Full());
+      t++;
+    }
+    if (t < t_end) {  // the partial last tile
+      flush_due();
+      load_tile(bufA, t);
+      tile(bufA, t, std::true_type());
+      t++;
+    }
+#if TSG_K1_GROUPQ
+    if (grp_n) compact();
+#endif
+    if (qn) flush();
+    if (nl_slots) flush_nl(t - 1);
+    return;
   }
-  if (t < t_end) {  // the partial last tile
+  // whole tiles; the arena's partial last tile (if any, and kept) is the last kept tile: the last of its wave's range
+  const bool partial = (P.n_bytes % kFTile) != 0 && tail_kept;
+  const uint64_t k_full = (partial && k_end == n_kept && k_end > k_begin) ? k_end - 1 : k_end;
+  uint64_t k = k_begin, t = t_begin, t_prev = t_begin;
+  bool nr_cur = false;  // wave-uniform: tile t starts a run (the range's first tile loaded its prefix above)
+  // A run ends before tile t: the staged newline counts and the flag group
+  // assume consecutive tiles, so they go out first (a store and maybe a
+  // flush's wait per run boundary, none inside a run).
+  auto run_boundary = [&]() {
+#if TSG_K1_GROUPQ
+    if (grp_n) compact();
+#endif
+    if (nl_slots) flush_nl(t_prev);
+  };
+  // tile t from `cur` while the next kept tile loads into `nxt`
+  auto step = [&](uint4* cur, uint4* nxt) {
+    if (nr_cur) run_boundary();
     flush_due();
+    uint64_t tn = t;
+    bool nr_n = false;
+    if (k + 1 < k_end) tn = next_tile(k + 1, t, &nr_n);
+    // A run's first tile takes the 8 bytes before it, not the last tile's:
+    // read here, ahead of the next tile's prefetch, so the wait is for this
+    // load alone (the tile in hand arrived a tile ago).  Loaded a tile
+    // earlier, with this tile's own prefetch, the pair would stay live across
+    // a whole tile body -- two more VGPRs spilled at the kernel's 64.
+    if (nr_cur) load_pre(t);
+    load_tile(nxt, k + 1 < k_full ? tn : t);  // past the range: a harmless reload
+    tile(cur, t, Full());
+    t_prev = t;
+    t = tn;
+    nr_cur = nr_n;
+    k++;
+  };
+  // two register buffers alternate roles (no copies): tile t in A while the next loads into B
+  if (k < k_full) load_tile(bufA, t);
+  while (k < k_full) {
+    step(bufA, bufB);
+    if (k >= k_full) break;
+    step(bufB, bufA);
+  }
+  if (k < k_end) {  // the partial last tile
+    if (nr_cur) run_boundary();
+    flush_due();
+    if (nr_cur) load_pre(t);
     load_tile(bufA, t);
     tile(bufA, t, std::true_type());
-    t++;
+    t_prev = t;
+    k++;
   }
 #if TSG_K1_GROUPQ
   if (grp_n) compact();
 #endif
   if (qn) flush();
-  if (nl_slots) flush_nl(t - 1);
+  if (nl_slots) flush_nl(t_prev);
+  if (RUNS && lane == 0 && k_begin < k_end) atomicMax(&P.run_info[kSkWaveRuns], runs_walked);
 }
 
 // ---------------------------------------------------------------------------
@@ -500,6 +766,7 @@ struct NfaParams {
   uint32_t fs_chunk;       // full-scan chunk bytes per lane (min; files of > 64 chunks use larger ones)
   uint32_t kw_fold;        // kwfold_kernel ran: with no fold-site overflow the keyword bits are exact in every file
   uint32_t diag;           // TSG_DIAG_VERIFY (timing only): 1 verifies only 1-word NFAs' hits, 2 only the wider ones
+  const uint8_t* skip;     // scans with a skip list: per file, 1 = its bytes are not needed (or null)
 };
 
 // The keyword bits of file f may miss occurrences through U+0130 / U+212A
@@ -1947,6 +2214,7 @@ __global__ __launch_bounds__(256) void fs_pairs_kernel(NfaParams P, FsLists Q) {
   for (uint64_t t = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; t < total; t += stride) {
     // one (file, rule) pair per lane: can its keyword gate be open?
     const uint32_t f = uint32_t(t / P.n_fullscan_rules);
+    if (P.skip && P.skip[f]) continue;  // an allow-listed file: no pair, whatever its gate says
     const uint32_t r = P.fullscan_rules[t % P.n_fullscan_rules];
     const RuleGpu rg = P.rules[r];
     bool open = rg.gate != kGateKeywords || rg.kw_match_implied || kw_bits_inexact(P, f) ||
@@ -2321,6 +2589,7 @@ GpuEngine::GpuEngine(const CompiledRules& cr, int device) : device_(device) {
   for (auto& e : ev_) hipEventCreate(&e);
   if (const char* dm = std::getenv("TSG_DIAG_SCAN")) diag_mode_ = uint32_t(std::atoi(dm));
   if (const char* dc = std::getenv("TSG_DIAG_CONFIRM")) diag_confirm_ = uint32_t(std::atoi(dc));
+  if (const char* kg = std::getenv("TSG_DIAG_K1_GRID")) k1_grid_cap_ = uint32_t(std::max(0, std::atoi(kg)));
   if (const char* di = std::getenv("TSG_DIAG_ITEMS")) item_diag_path_ = di;
   if (const char* fc = std::getenv("TSG_FULLSCAN_CHUNK")) fs_chunk_ = uint32_t(std::atoi(fc));
   if (fs_chunk_ < 64) fs_chunk_ = 64;
@@ -2654,7 +2923,7 @@ GpuEngine::~GpuEngine() {
   void* ps[] = {d_item_diag_, d_fold_pairs_, d_kwfold_pairs_, d_fold_idx_off_, d_fold_idx_items_, d_fold_first_, d_reach_, d_core_, d_group_items_, d_bucket_groups_, d_ftabs_, d_folds_, d_recs_, d_anchors_,
                 d_rules_, d_rule_kw_, d_nfa_, d_fullscan_rules_, d_counters_, d_chunk_file_, d_nl_, d_kw_,
                 d_flags_, d_hits_, d_cands_, d_fs_pairs_, d_fs_tasks_, d_fs_wave_, d_fs_ctr_, d_xlen_, d_xoff_, d_xscan_,
-                d_xf_, d_gfiles_, d_gdst_, d_gbuf_, d_wins_};
+                d_xf_, d_gfiles_, d_gdst_, d_gbuf_, d_wins_, d_keep_bits_, d_runs_, d_skip_info_};
   for (void* p : ps)
     if (p) hipFree(p);
   for (int b = 0; b < kNStage; b++)
@@ -2675,6 +2944,7 @@ GpuEngine::~GpuEngine() {
     if (S.ev_fs) hipEventDestroy(S.ev_fs);
     if (S.done) hipEventDestroy(S.done);
     if (S.h_cnt) hipHostFree(S.h_cnt);
+    if (S.h_skip) hipHostFree(S.h_skip);
     if (S.h_cands) hipHostFree(S.h_cands);
     for (auto& e : S.ev_f)
       if (e) hipEventDestroy(e);
@@ -2697,7 +2967,7 @@ GpuEngine::~GpuEngine() {
   for (auto* h : h_off_)
     if (h) hipHostFree(h);
   if (h_xoff_) hipHostFree(h_xoff_);
-  for (void* h : {static_cast<void*>(h_run_cnt_), h_run_cands_, h_gup_, h_gbuf_})
+  for (void* h : {static_cast<void*>(h_run_cnt_), static_cast<void*>(h_run_skip_), h_run_cands_, h_gup_, h_gbuf_})
     if (h) hipHostFree(h);
   if (copy_stream_) hipStreamDestroy(copy_stream_);
   if (stream_) hipStreamDestroy(stream_);
@@ -3243,7 +3513,7 @@ void GpuEngine::InitCaps(uint64_t n_bytes) {
 }
 
 bool GpuEngine::Enqueue(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
-                        Ticket* t, std::string* err, FetchOut* fetch) {
+                        Ticket* t, std::string* err, FetchOut* fetch, const SkipIn* skip) {
   t->slot = -1;
   if (n_files == 0 || n_bytes >= (uint64_t(1) << 36) - 64 || d_item_diag_ || diag_mode_ != 0) return false;
   int k = -1;
@@ -3344,8 +3614,15 @@ bool GpuEngine::Enqueue(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t
       return fail();
     }
   }
-  if (!EnqueuePhase(d_arena, n_bytes, d_offsets, n_files, n_chunks, S.ev, S.ev_fs) ||
+  S.has_skip = skip && skip->d_skip && n_bytes > 0;
+  if (S.has_skip && !S.h_skip &&
+      hipHostMalloc(reinterpret_cast<void**>(&S.h_skip), 64, hipHostMallocDefault) != hipSuccess) {
+    err_ = "pinned skip counters";
+    return fail();
+  }
+  if (!EnqueuePhase(d_arena, n_bytes, d_offsets, n_files, n_chunks, S.ev, S.ev_fs, skip) ||
       hipMemcpyAsync(S.h_cnt, d_counters_, 64, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
+      (S.has_skip && hipMemcpyAsync(S.h_skip, d_skip_info_, 64, hipMemcpyDeviceToHost, stream_) != hipSuccess) ||
       hipMemcpyAsync(S.h_cands, d_cands_, size_t(n_copy) * sizeof(Candidate), hipMemcpyDeviceToHost, stream_) !=
           hipSuccess ||
       // the fetch right behind: no host round trip between the candidates and its launch
@@ -3410,6 +3687,7 @@ bool GpuEngine::Collect(Ticket* t, std::vector<Candidate>* cands, BatchStats* st
   st->flagged_blocks = cnt[7];
   st->fullscan_tasks = cnt[13];
   st->fold_sites = cnt[9];
+  if (S.has_skip) NoteSkip(S.h_skip, st);
   cands->clear();
   cands->reserve(cnt[1]);
   for (uint32_t i = 0; i < cnt[1]; i++)  // closed keyword gates (finalize_kernel) never reach the host
@@ -3525,7 +3803,20 @@ bool GpuEngine::Collect(Ticket* t, std::vector<Candidate>* cands, BatchStats* st
 // The GPU phase of one scan, enqueued on stream_: clears, K0 .. finalize,
 // with the phase events recorded into ev[0..6] (ev_fs before the full scan).
 bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
-                             uint64_t n_chunks, hipEvent_t* ev, hipEvent_t ev_fs) {
+                             uint64_t n_chunks, hipEvent_t* ev, hipEvent_t ev_fs, const SkipIn* skip) {
+  const uint64_t f_tiles = (n_bytes + kFTile - 1) / kFTile;
+  if (skip && (!skip->d_skip || f_tiles == 0)) skip = nullptr;
+  if (skip) {
+    if (!Ensure(&d_keep_bits_, &cap_keep_bits_, KeepWords(f_tiles) * 8) ||
+        !Ensure(&d_runs_, &cap_runs_, (f_tiles / 2 + 2) * sizeof(uint2)))
+      return false;
+    if (!d_skip_info_) {
+      HIP_OK(hipMalloc(reinterpret_cast<void**>(&d_skip_info_), 64));
+      HIP_OK(hipMemset(d_skip_info_, 0, 64));
+    }
+    // the marks are written by the path kernel on a stream of its own
+    if (skip->ready) HIP_OK(hipStreamWaitEvent(stream_, skip->ready, 0));
+  }
   if (!Ensure(&d_chunk_file_, &cap_chunk_file_, n_chunks * 4) || !Ensure(&d_nl_, &cap_nl_, (n_chunks + 8) * 2) ||
       !Ensure(&d_kw_, &cap_kw_, size_t(n_files) * kw_words_ * 4) ||
       !Ensure(&d_flags_, &cap_flags_, size_t(n_files) * 4) ||
@@ -3553,8 +3844,20 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
     z.n_kw = uint64_t(n_files) * kw_words_;
     z.counters = d_counters_;
     z.fs_ctr = n_fullscan_rules_ > 0 ? d_fs_ctr_ : nullptr;
+    z.skip_info = skip ? d_skip_info_ : nullptr;
     chunk_map_kernel<<<blocks, 256, 0, stream_>>>(d_offsets, n_files, used, static_cast<uint32_t*>(d_chunk_file_),
                                                   z);
+  }
+  if (skip) {  // the kept tiles and their runs (d_skip_info_ was cleared by K0)
+    const uint32_t blocks =
+        uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((KeepWords(f_tiles) * 64 + 255) / 256, 4096)));
+    tile_keep_kernel<<<blocks, 256, 0, stream_>>>(d_offsets, n_files, static_cast<const uint32_t*>(d_chunk_file_),
+                                                  skip->d_skip, n_bytes, f_tiles,
+                                                  static_cast<uint64_t*>(d_keep_bits_), d_skip_info_);
+    HIP_OK(hipGetLastError());
+    tile_runs_kernel<<<1, kRunThreads, 0, stream_>>>(static_cast<const uint64_t*>(d_keep_bits_), f_tiles,
+                                                     static_cast<uint2*>(d_runs_), d_skip_info_);
+    HIP_OK(hipGetLastError());
   }
   // K1: streaming filter -> flagged block records
   FilterParams fp;
@@ -3566,11 +3869,14 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
   fp.recs = static_cast<uint32_t*>(d_recs_);
   fp.rec_cap = rec_cap_;
   fp.counters = d_counters_;
-  const uint64_t f_tiles = (n_bytes + kFTile - 1) / kFTile;
-  const uint32_t f_grid =
+  fp.runs = skip ? static_cast<const uint2*>(d_runs_) : nullptr;
+  fp.run_info = skip ? d_skip_info_ : nullptr;
+  uint32_t f_grid =
       uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((f_tiles + kScanWaves - 1) / kScanWaves, 256 * kFWgPerCu)));
+  if (k1_grid_cap_) f_grid = std::min(f_grid, k1_grid_cap_);
   HIP_OK(hipEventRecord(ev[1], stream_));
-  filter_kernel<<<f_grid, kScanThreads, 0, stream_>>>(fp);
+  if (skip) filter_kernel<true><<<f_grid, kScanThreads, 0, stream_>>>(fp);
+  else filter_kernel<false><<<f_grid, kScanThreads, 0, stream_>>>(fp);
   HIP_OK(hipGetLastError());
   HIP_OK(hipEventRecord(ev[2], stream_));
   // K2: confirm + verify
@@ -3722,6 +4028,7 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
   np.fullscan_rules = d_fullscan_rules_;
   np.n_fullscan_rules = n_fullscan_rules_;
   np.fs_chunk = fs_chunk_;
+  np.skip = skip ? skip->d_skip : nullptr;
   np.kw_fold = kw_fold_ ? 1u : 0u;  // no keyword takes 'i' / 'k': the bits are exact without the kernel
 
   if (diag_mode_ == 0) verify_hits_kernel<<<verify_blocks_, 256, 0, stream_>>>(np);
@@ -3987,7 +4294,7 @@ bool GpuEngine::FetchFiles(const uint8_t* d_arena, const uint64_t* d_offsets, ui
 }
 
 bool GpuEngine::Run(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
-                    std::vector<Candidate>* cands, BatchStats* st, FetchOut* fetch) {
+                    std::vector<Candidate>* cands, BatchStats* st, FetchOut* fetch, const SkipIn* skip) {
   HIP_OK(hipSetDevice(device_));
   cands->clear();
   BatchStats local;
@@ -4004,11 +4311,17 @@ bool GpuEngine::Run(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_
   if (n_chunks == 0) n_chunks = 1;
   InitCaps(n_bytes);
   for (int attempt = 0; attempt < 8; attempt++) {
-    if (!EnqueuePhase(d_arena, n_bytes, d_offsets, n_files, n_chunks, ev_, ev_fs_)) return false;
+    if (!EnqueuePhase(d_arena, n_bytes, d_offsets, n_files, n_chunks, ev_, ev_fs_, skip)) return false;
     uint32_t cnt[16];
     if (!h_run_cnt_) HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&h_run_cnt_), 64, hipHostMallocDefault));
     HIP_OK(hipMemcpyAsync(h_run_cnt_, d_counters_, sizeof(cnt), hipMemcpyDeviceToHost, stream_));
+    const bool has_skip = skip && skip->d_skip && n_bytes > 0;
+    if (has_skip) {
+      if (!h_run_skip_) HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&h_run_skip_), 64, hipHostMallocDefault));
+      HIP_OK(hipMemcpyAsync(h_run_skip_, d_skip_info_, 64, hipMemcpyDeviceToHost, stream_));
+    }
     HIP_OK(WaitStream());
+    if (has_skip) NoteSkip(h_run_skip_, st);
     std::memcpy(cnt, h_run_cnt_, sizeof(cnt));
     if (std::getenv("TSG_STATS_DEBUG"))
       std::fprintf(stderr, "counters: hits %u cands %u special %u recs %u folds %u\n", cnt[0], cnt[1], cnt[2], cnt[7],
@@ -4090,6 +4403,15 @@ bool GpuEngine::Run(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_
   }
   err_ = "candidate buffers kept overflowing";
   return false;
+}
+
+void GpuEngine::NoteSkip(const uint32_t* info, BatchStats* st) const {
+  st->skip_runs = info[kSkRuns];
+  st->tiles = info[kSkTiles];
+  st->skip_tiles = info[kSkTiles] - info[kSkKept];
+  st->skip_files = info[kSkFiles];
+  st->skip_bytes = uint64_t(info[kSkBytes]) | (uint64_t(info[kSkBytes + 1]) << 32);
+  st->skip_wave_runs = info[kSkWaveRuns];
 }
 
 // TSG_DIAG_ITEMS: appends "item kind first_id exact_matches passed_on" lines

@@ -40,6 +40,31 @@ struct PathTable {
 // a literal shorter than 2 or longer than 64 bytes, over 256 positions).
 bool BuildPathTable(const std::vector<std::pair<std::string, uint32_t>>& lits, PathTable* t);
 
+// The "surely allowed" decision: a second shift-and beside the
+// prefilter's, over the exact literal forms of the allow-path regexes that
+// have one (rules.h ExactPathLiterals).  Indexed by the raw byte: a
+// case-sensitive position accepts one byte, a (?i) position both cases.  A
+// path that is ASCII-only, at most kSureMaxPath bytes long and completes a
+// literal is matched by that literal's regex, so its file is allow-listed
+// whatever its bytes hold: the scan may skip them.  The decision never says
+// yes for a path the host's exact AllowPath would refuse; it says no for every
+// non-ASCII or over-long path and when no rule has an exact form.
+struct SureTable {
+  uint64_t B[256][4];     // positions that accept the byte
+  uint64_t S[4], S0[4];   // first positions: injected at every byte / at offset 0 only (^ literals)
+  uint64_t E[4], EZ[4];   // last positions: honoured anywhere / at the path's last byte only ($ literals)
+  uint32_t words;         // 0: no exact form (or the literals do not fit): nothing is surely allowed
+};
+constexpr uint64_t kSureMaxPath = 4096;
+struct SureLit {          // one exact literal: per position the byte(s) it accepts
+  std::vector<std::pair<uint8_t, uint8_t>> pos;
+  bool begin = false, end = false;
+};
+// False (words = 0) when there is no literal or they do not fit 4 x 64 positions.
+bool BuildSureTable(const std::vector<SureLit>& lits, SureTable* t);
+// The kernel's decision on the host (the model the tests check against the oracle).
+bool SureAllowHost(const SureTable& t, const uint8_t* p, uint64_t n);
+
 class PathFilter {
  public:
   PathFilter(int device, const PathTable& t);
@@ -63,12 +88,41 @@ class PathFilter {
     return RunImpl(nullptr, nullptr, h_paths, h_off, n, out, err);
   }
 
+  // The split form, for a scan that skips the surely allowed files: Submit
+  // launches the kernel (and the read-back copies) on a slot's stream and
+  // returns at once; with want_skip the kernel also fills the slot's per-file
+  // skip bytes (1 = surely allowed) and `ready` is recorded behind it, for the
+  // scan's stream to wait on.  Finish waits for the read-back and returns the
+  // reported paths, as Run does.  The slot -- the skip bytes -- stays the
+  // caller's until Release, which the caller calls once the scan's GPU phase
+  // is over.  Give either host or device paths, as to Run / RunHost.
+  struct Pending {
+    int slot = -1;
+    const uint8_t* d_skip = nullptr;  // null without want_skip (or without a sure table)
+    hipEvent_t ready = nullptr;
+    uint32_t n = 0, guess = 0;
+  };
+  void SetSureTable(const SureTable& t);  // before the first Submit; a table with words = 0 is ignored
+  bool has_sure() const { return d_sure_ != nullptr; }
+  bool Submit(const uint8_t* d_paths, const uint64_t* d_off, const uint8_t* h_paths, const uint64_t* h_off,
+              uint32_t n, bool want_skip, Pending* p, std::string* err);
+  bool Finish(Pending* p, std::vector<PathHit>* out, std::string* err);
+  void Release(Pending* p);
+
  private:
   bool RunImpl(const uint8_t* d_paths, const uint64_t* d_off, const uint8_t* h_paths, const uint64_t* h_off,
-               uint32_t n, std::vector<PathHit>* out, std::string* err);
+               uint32_t n, std::vector<PathHit>* out, std::string* err) {
+    Pending p;
+    const bool ok = Submit(d_paths, d_off, h_paths, h_off, n, false, &p, err) && Finish(&p, out, err);
+    Release(&p);
+    return ok;
+  }
   struct Slot {
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
+    hipEvent_t ready = nullptr;  // behind the kernel: the skip bytes are written
+    uint8_t* d_skip = nullptr;   // one byte per file (Submit with want_skip)
+    size_t skip_cap = 0;
     uint32_t* d_cnt = nullptr;  // two counters used in turn: each launch zeroes the next one's
     uint32_t parity = 0;
     uint32_t* h_cnt = nullptr;
@@ -82,7 +136,8 @@ class PathFilter {
     size_t stage_cap = 0;
     bool busy = false;
   };
-  static constexpr int kSlots = 4;
+  // (a scan that skips holds its slot through its GPU phase: as many as scans in flight)
+  static constexpr int kSlots = 8;
   std::mutex mu_;
   std::condition_variable cv_;
   Slot slots_[kSlots];
@@ -90,6 +145,7 @@ class PathFilter {
   int device_ = 0;
   std::string err_;
   PathTable* d_table_ = nullptr;
+  SureTable* d_sure_ = nullptr;
 };
 
 }  // namespace tsg

@@ -1092,6 +1092,97 @@ std::vector<std::string> RequiredLiterals(const Regex& re) {
 
 namespace {
 
+struct LitTok {
+  uint8_t kind;  // 0 a byte position, 1 ^, 2 $
+  uint8_t a, b;
+};
+using LitSeq = std::vector<LitTok>;
+
+// The language of node i as at most kMaxPathAlts token sequences; false when
+// it is not a finite set of literals (or the set is larger).
+bool ExpandPathLit(const std::vector<Node>& N, int i, std::vector<LitSeq>* out) {
+  const Node& n = N[size_t(i)];
+  out->clear();
+  switch (n.op) {
+    case NodeOp::Empty:
+      out->push_back({});
+      return true;
+    case NodeOp::Class: {
+      uint8_t m[3];
+      uint32_t k = 0;
+      for (auto& r : n.ranges)
+        for (uint32_t c = r.first; c <= r.second && c < 0x80 && k < 3; c++) m[k++] = uint8_t(c);
+      // one character, or a letter's two cases; members outside ASCII never occur in an ASCII path
+      if (k == 1) out->push_back({LitTok{0, m[0], m[0]}});
+      else if (k == 2 && (m[0] ^ m[1]) == 0x20 && (m[1] | 0x20) >= 'a' && (m[1] | 0x20) <= 'z')
+        out->push_back({LitTok{0, m[0], m[1]}});
+      else return false;
+      return true;
+    }
+    case NodeOp::Assert:
+      if (n.assert_op == kEmptyBeginText) out->push_back({LitTok{1, 0, 0}});
+      else if (n.assert_op == kEmptyEndText) out->push_back({LitTok{2, 0, 0}});
+      else return false;
+      return true;
+    case NodeOp::Capture:
+      return ExpandPathLit(N, n.subs[0], out);
+    case NodeOp::Cat: {
+      out->push_back({});
+      std::vector<LitSeq> sub, next;
+      for (int s : n.subs) {
+        if (!ExpandPathLit(N, s, &sub) || out->size() * sub.size() > kMaxPathAlts) return false;
+        next.clear();
+        for (auto& a : *out)
+          for (auto& b : sub) {
+            next.push_back(a);
+            next.back().insert(next.back().end(), b.begin(), b.end());
+          }
+        out->swap(next);
+      }
+      return true;
+    }
+    case NodeOp::Alt: {
+      std::vector<LitSeq> sub;
+      for (int s : n.subs) {
+        if (!ExpandPathLit(N, s, &sub) || out->size() + sub.size() > kMaxPathAlts) return false;
+        out->insert(out->end(), sub.begin(), sub.end());
+      }
+      return !out->empty();
+    }
+    case NodeOp::Repeat: {
+      if (!(n.max == 1 && (n.min == 0 || n.min == 1))) return false;
+      if (!ExpandPathLit(N, n.subs[0], out) || out->size() + 1 > kMaxPathAlts) return false;
+      if (n.min == 0) out->push_back({});
+      return true;
+    }
+    default:
+      return false;
+  }
+}
+
+}  // namespace
+
+bool ExactPathLiterals(const Regex& re, std::vector<PathLit>* out) {
+  out->clear();
+  std::vector<LitSeq> seqs;
+  if (re.root() < 0 || !ExpandPathLit(re.nodes(), re.root(), &seqs) || seqs.empty()) return false;
+  for (auto& s : seqs) {
+    PathLit l;
+    size_t a = 0, b = s.size();
+    while (a < b && s[a].kind == 1) l.begin = true, a++;
+    while (b > a && s[b - 1].kind == 2) l.end = true, b--;
+    for (size_t q = a; q < b; q++) {
+      if (s[q].kind != 0) return false;  // an assertion inside the literal
+      l.pos.push_back({s[q].a, s[q].b});
+    }
+    if (l.pos.empty() || l.pos.size() > 64) return false;  // (an empty alternative matches every path)
+    out->push_back(std::move(l));
+  }
+  return true;
+}
+
+namespace {
+
 // The prefilter item of anchor literal li of `best`: the sets before it, the
 // literal's sets (the union over same-folded variants), the lookahead sets.
 FilterItem AnchorItem(const Regex& re, const Cand& best, size_t li, uint32_t aid) {

@@ -126,6 +126,21 @@ struct CompiledRules {
 // `re` contains, or empty if none is known.  Used as a MatchString prefilter.
 std::vector<std::string> RequiredLiterals(const Regex& re);
 
+// The exact literal form of a path regex, where it has one: MatchString(re,
+// path) on an ASCII path is true iff one of the alternatives occurs in it
+// (at offset 0 with `begin`, ending at the last byte with `end`).  The regex
+// must be an alternation / concatenation of single characters (under (?i) a
+// letter's two cases; a fold partner outside ASCII cannot occur in an ASCII
+// path), `x?`, groups, and ^ / $ without (?m); the expansion is capped at
+// kMaxPathAlts alternatives of 1..64 bytes.  Anything else -- wider classes,
+// other repeats, `.`, line or word assertions -- has no exact form.
+struct PathLit {
+  std::vector<std::pair<uint8_t, uint8_t>> pos;  // the byte(s) each position accepts (equal when one)
+  bool begin = false, end = false;
+};
+constexpr size_t kMaxPathAlts = 16;
+bool ExactPathLiterals(const Regex& re, std::vector<PathLit>* out);
+
 // Optional inputs of the compiler.  calib: a sample of the bytes the scanner
 // will see (e.g. its first batch).  With one, a rule that has both a literal
 // anchor and a class-run anchor takes the one whose prefilter item fires less

@@ -48,6 +48,11 @@ struct Matcher {
 // MatchString of the regex is true iff one of them occurs (anchored as given).
 bool SimpleLiteral(const std::string& src, std::vector<std::string>* lits, bool* begin, bool* end);
 
+// The sure table (pathfilter.h) of the path regexes that have an exact literal
+// form (rules.h ExactPathLiterals; null entries have none); false when none
+// has or the literals do not fit.  has_form (optional): per regex.
+bool SureTableOf(const std::vector<const Regex*>& res, SureTable* t, std::vector<uint8_t>* has_form);
+
 struct AllowRuleSpec {
   std::string id;
   std::unique_ptr<Matcher> regex, path;
@@ -351,7 +356,10 @@ class SecretScanner {
                   HostStats* hs, FetchWindowStats* ws, std::string* err) const;
   // RuleGpu::max_len per compiled rule (the exclude-block rules included)
   std::vector<uint32_t> RuleMaxLens() const;
-  std::vector<uint8_t> AllowedPaths(const BatchInput& in) const;
+  // pend (optional): the path kernel was submitted already (Scan, for the skip list): its hits are read
+  std::vector<uint8_t> AllowedPaths(const BatchInput& in, PathFilter::Pending* pend = nullptr) const;
+  // The exact literal forms of the global allow-path rules that have one; false when none has.
+  bool BuildSureAllow(SureTable* t) const;
   // Global.AllowPath (scanner.go:57-59)
   bool AllowPath(const uint8_t* p, size_t n) const;
 
@@ -438,6 +446,7 @@ class SecretScanner {
   bool AllowPathRules(const uint8_t* p, size_t n, uint64_t lit_rules) const;
   // GPU allow-path prefilter (pathfilter.h): built when every path rule has usable literals
   std::unique_ptr<PathFilter> path_filter_;
+  bool gpu_skip_allowed_ = false;  // the sure table is on the GPU and TSG_GPU_SKIP_ALLOWED is not 0
   std::unique_ptr<FindingMaterializer> mat_;  // GPU findings of HBM-resident batches
   std::atomic<int> gpu_findings_{0};
   mutable std::mutex fetch_opt_mu_;

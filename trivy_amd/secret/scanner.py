@@ -579,6 +579,16 @@ class ScanResult:
             raise RuntimeError("tsg_result_fetch_window_stats failed: %s" % _lib.last_error(self._sc._L))
         return {k: getattr(s, k) for k, _ in s._fields_ if k != "struct_size"}
 
+    def skip_stats(self):
+        """What the scan's skip list did (tsg_debug_result_skip): the files the path kernel found surely
+        allow-listed and their bytes, the 4-KiB tiles the streaming filter left out, the runs of kept
+        tiles, the most runs one of its waves walked, the arena's tiles; all zero without one."""
+        out = (c.c_uint64 * 6)()
+        self._sc._L.tsg_debug_result_skip.argtypes = [c.c_void_p, c.c_void_p]
+        if self._sc._L.tsg_debug_result_skip(self._h, out) != 0:
+            raise RuntimeError("tsg_debug_result_skip failed")
+        return dict(zip(("files", "bytes", "tiles_dropped", "runs", "wave_runs_max", "tiles"), map(int, out)))
+
     def raw(self, lo=None, hi=None):
         p = c.c_void_p()
         n = c.c_uint64()

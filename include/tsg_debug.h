@@ -182,6 +182,13 @@ int tsg_debug_sure_allow(const char* const* patterns, uint32_t n_patterns, const
  * transform).  TSG_DIAG_K1_GRID=<n> at scanner creation caps the filter's grid
  * at n workgroups, so a small arena still gives a wave many tiles. */
 int tsg_debug_result_skip(const struct tsg_result* r, uint64_t out[6]);
+/* The span of a resident scan's K0 phase (chunk map with the clears, kept tiles,
+ * their runs) on the stream it ran on, in ms.  In a pipeline that phase runs on
+ * a stream of its own beside the kernels of the scan before, so it is no part
+ * of tsg_stats.ms_chunkmap_kernel, which is the time the streaming filter
+ * still waited for it (TSG_OVERLAP_K0=0 at scanner creation: the phase runs on
+ * the engine stream and the two agree).  Summed over the chunks of a host batch. */
+int tsg_debug_result_k0(const struct tsg_result* r, double* ms_k0);
 
 /* Thread-local text of the last error. */
 const char* tsg_last_error(void);

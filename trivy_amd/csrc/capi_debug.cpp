@@ -402,4 +402,10 @@ int tsg_debug_result_skip(const struct tsg_result* r, uint64_t out[6]) {
   std::memcpy(out, r->skip, sizeof(r->skip));
   return 0;
 }
+
+int tsg_debug_result_k0(const struct tsg_result* r, double* ms_k0) {
+  if (!r || !ms_k0) return -1;
+  *ms_k0 = r->ms_k0;
+  return 0;
+}
 }

@@ -19,6 +19,7 @@ struct tsg_result {
   tsg::FetchWindowStats win;  // tsg_result_fetch_window_stats (the windows fetch; zero otherwise)
   // tsg_debug_result_skip: files marked, their bytes, tiles dropped, runs, most runs per K1 wave, tiles
   uint64_t skip[6] = {0, 0, 0, 0, 0, 0};
+  float ms_k0 = 0;  // tsg_debug_result_k0: the K0 phase's own span (BatchStats::ms_k0)
   std::string json;        // tsg_result_json: every file (built once)
   std::string json_range;  // tsg_result_json_range: the last range asked for
   const tsg::SecretScanner* owner;

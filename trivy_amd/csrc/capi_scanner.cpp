@@ -407,6 +407,7 @@ int ScanImpl(tsg_scanner* s, const tsg_batch* b, const ExtFields& x, tsg_result*
   st.ms_xform_kernel = gs.ms_xform;
   const uint64_t sk[6] = {gs.skip_files, gs.skip_bytes, gs.skip_tiles, gs.skip_runs, gs.skip_wave_runs, gs.tiles};
   std::memcpy(r->skip, sk, sizeof(sk));
+  r->ms_k0 = gs.ms_k0;
   *out = r.release();
   return 0;
 }

@@ -113,6 +113,7 @@ struct BatchStats {
   float ms_finalize = 0, ms_chunkmap = 0;
   float ms_h2d_span = 0;  // RunHost: first copy issued -> last chunk done (the ingest-inclusive GPU time)
   float ms_xform = 0;     // RunHost with kinds: pre-transform kernels (part of ms_total)
+  float ms_k0 = 0;        // the K0 phase's own span on the stream it ran on (ms_chunkmap: what K1 still waited for)
   uint64_t h2d_chunks = 0;
   bool hit_overflow = false, cand_overflow = false;
   // a scan with a skip list (SkipIn): the files marked and their bytes, the 4-KiB tiles K1 left out,
@@ -121,9 +122,9 @@ struct BatchStats {
 };
 
 // Files whose bytes the result does not need: d_skip[f] != 0
-// for a file whose path is surely allow-listed (pathfilter.h).  The engine's
-// stream waits for `ready` before K0; the bytes stay readable until the scan's
-// GPU phase is over.  K1 then streams only the 4-KiB tiles that hold a byte of
+// for a file whose path is surely allow-listed (pathfilter.h).  The stream K0
+// runs on waits for `ready`; the bytes stay readable until the scan's GPU phase
+// is over.  K1 then streams only the 4-KiB tiles that hold a byte of
 // some other file, and the full scan makes no pair for a marked file.
 struct SkipIn {
   const uint8_t* d_skip = nullptr;
@@ -179,10 +180,13 @@ class GpuEngine {
 
   // Split form of Run for pipelined callers: Enqueue (with the engine's lock
   // held) puts the whole GPU phase and the copies of the counters and of the
-  // full candidate buffer into pinned host memory on the stream and returns;
-  // Collect (no lock) waits for that ticket.  The next scan's kernels queue
-  // right behind the copies, so the GPU does not idle while a caller wakes
-  // up, reads back and releases the lock.  Enqueue returns false when no
+  // full candidate buffer into pinned host memory on the engine's streams and
+  // returns; Collect (no lock) waits for that ticket.  The next scan's kernels
+  // queue right behind the finalize kernel, so the GPU does not idle while a
+  // caller wakes up, reads back and releases the lock; its K0 phase runs on a
+  // stream of its own beside this scan's last kernels, and the copies on
+  // another beside the next scan's (TSG_OVERLAP_K0=0 /
+  // TSG_READBACK_STREAM=0 put either back on the engine stream).  Enqueue returns false when no
   // ticket is free or a diagnostic mode is on (then call Run); Collect sets
   // *rerun when a buffer overflowed (then call Run under the lock: it grows
   // the buffers and rescans).
@@ -224,14 +228,59 @@ class GpuEngine {
 
  private:
   bool Ensure(void** p, size_t* cap, size_t need);
+  // The buffers a scan's K0 phase writes before its K1 may start, or the
+  // read-back and the fetch read after its finalize kernel.
+  // Two sets, taken in turn by Enqueue: K0 of scan i + 1 fills the other set
+  // on aux_stream_ while scan i's kernels run, and scan i's candidates leave
+  // on rb_stream_ while scan i + 1's kernels run.  Everything produced and
+  // consumed between K1 and finalize (d_nl_, d_recs_, d_hits_, d_folds_,
+  // d_wins_, the full-scan lists) stays single: only stream_ touches it.
+  struct WorkSet {
+    void* chunk_file = nullptr; size_t cap_chunk_file = 0;
+    // scans with a skip list: the kept-tile bitmap, the runs of kept tiles (begin tile, kept tiles before),
+    // and 16 counters: [0] runs [1] kept tiles [2] last tile kept [3] files marked [4,5] their bytes (u64)
+    // [6] most runs walked by a K1 wave [7] tiles
+    void* keep_bits = nullptr; size_t cap_keep_bits = 0;
+    void* runs = nullptr; size_t cap_runs = 0;
+    uint32_t* skip_info = nullptr;
+    void* kw = nullptr; size_t cap_kw = 0;
+    void* flags = nullptr; size_t cap_flags = 0;
+    void* cands = nullptr; size_t cap_cands = 0;
+    uint32_t* counters = nullptr;  // [0] hits [1] cands [2] special files [3] hit overflow [4] cand overflow
+                                   // [7] flagged-block records [8] record overflow
+                                   // [9] fold sites [10] fold-site overflow
+                                   // [6] full-scan list overflow [11] anchor-item matches [13] open pairs
+    uint32_t* fs_ctr = nullptr;    // [0] pairs [1..4] tasks [5] wave pairs
+    // free_ev: the last read of the set by the scan that used it (recorded beside Slot::done);
+    // k0_done: the last K0 phase that filled it on aux_stream_.  *_rec: recorded at least once.
+    hipEvent_t free_ev = nullptr, k0_done = nullptr;
+    bool free_rec = false, k0_rec = false;
+  };
+  static constexpr int kSets = 2;
+  WorkSet sets_[kSets];
+  uint32_t set_turn_ = 0;                // the set the next Enqueue takes; Run and its fetches use sets_[0]
+  hipStream_t aux_stream_ = nullptr;     // K0 phases of Enqueue'd scans (highest priority; TSG_OVERLAP_K0=0: unused)
+  hipStream_t rb_stream_ = nullptr;      // counter / candidate read-back of Enqueue'd scans (TSG_READBACK_STREAM=0: unused)
+  bool overlap_k0_ = true, readback_stream_ = true;
+  hipEvent_t ev_k0_[2] = {};             // Run's K0 span (Slot::ev_k0 for Enqueue'd scans)
+  // The end of the last K2 enqueued on stream_: a K0 phase on aux_stream_ starts behind it, beside the
+  // latency-bound fold / verify / finalize kernels, never beside K1 or K2 (§4.10: launched together with
+  // a K1, K0's workgroups take wave slots first and leave K1's two workgroups per CU unevenly placed for
+  // the whole kernel; beside K2 it costs K2 what it saves).
+  hipEvent_t k2_done_ = nullptr;
+  bool k2_rec_ = false;
+  bool EnsureSets(uint64_t n_chunks, uint32_t n_files, uint64_t f_tiles, bool skip);
   bool EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
-                    uint64_t n_chunks, hipEvent_t* ev, hipEvent_t ev_fs, const SkipIn* skip = nullptr);
+                    uint64_t n_chunks, WorkSet& W, bool k0_aux, hipEvent_t* ev, hipEvent_t ev_fs, hipEvent_t* ev_k0,
+                    const SkipIn* skip = nullptr);
   void InitCaps(uint64_t n_bytes);
   struct Slot {  // one in-flight Enqueue: its phase events and pinned read-back buffers
     hipEvent_t ev[7] = {};
     hipEvent_t ev_fs = nullptr, done = nullptr;
+    hipEvent_t ev_k0[2] = {};    // the K0 phase's span on the stream it ran on
+    hipEvent_t fin = nullptr, rb_done = nullptr;  // finalize done (stream_) / read-back done (rb_stream_)
     uint32_t* h_cnt = nullptr;
-    uint32_t* h_skip = nullptr;  // pinned copy of the skip counters (d_skip_info_), scans with a skip list
+    uint32_t* h_skip = nullptr;  // pinned copy of the skip counters (WorkSet::skip_info), scans with a skip list
     bool has_skip = false;
     Candidate* h_cands = nullptr;
     size_t h_cap = 0;
@@ -272,15 +321,16 @@ class GpuEngine {
   // the counters are shared by the scans in flight, in stream order: a pack
   // waits (ev_drained_) for the copy of the round before it, of this scan or of
   // the one before, and the copy (fetch_stream_) for its pack (ev_packed_).
-  bool IssueFetch(const uint8_t* d_arena, const uint64_t* d_offsets, uint32_t n_files, const uint32_t* h_flags,
-                  uint64_t direct, uint64_t stage, uint64_t copy_bytes, uint8_t* h_dst, void* h_ctr, hipEvent_t ev0);
+  bool IssueFetch(const WorkSet& W, const uint8_t* d_arena, const uint64_t* d_offsets, uint32_t n_files,
+                  const uint32_t* h_flags, uint64_t direct, uint64_t stage, uint64_t copy_bytes, uint8_t* h_dst,
+                  void* h_ctr, hipEvent_t ev0);
   bool FetchNow(const uint8_t* d_arena, const uint64_t* d_offsets, uint32_t n_files, std::vector<uint8_t> want,
                 bool upload_flags, FetchOut* out);
   void NoteFetch(uint64_t packed, uint64_t total);
   // windows mode (fetch_windows.h): the same rounds, events, staging buffer and fetch stream
-  bool IssueFetchWin(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
-                     const FetchWinParams& prm, uint64_t stage, uint64_t copy_bytes, uint8_t* h_dst, void* h_ctr,
-                     hipEvent_t ev0);
+  bool IssueFetchWin(const WorkSet& W, const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets,
+                     uint32_t n_files, const FetchWinParams& prm, uint64_t stage, uint64_t copy_bytes, uint8_t* h_dst,
+                     void* h_ctr, hipEvent_t ev0);
   bool FetchNowWin(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
                    const std::vector<Candidate>& cands, FetchOut* out);
   std::atomic<uint64_t> fetchw_stage_bytes_{uint64_t(256) << 20};  // SetFetchSizes' stage, rounded to granules
@@ -364,27 +414,13 @@ class GpuEngine {
   void* d_recs_ = nullptr; size_t cap_recs_ = 0;
   uint32_t rec_cap_ = 0, fold_cap_ = 0, n_fitems_ = 0;
   // per-batch buffers
-  void* d_chunk_file_ = nullptr; size_t cap_chunk_file_ = 0;
   void* d_nl_ = nullptr; size_t cap_nl_ = 0;
-  // scans with a skip list: the kept-tile bitmap, the runs of kept tiles (begin tile, kept tiles before),
-  // and 16 counters: [0] runs [1] kept tiles [2] last tile kept [3] files marked [4,5] their bytes (u64)
-  // [6] most runs walked by a K1 wave [7] tiles
-  void* d_keep_bits_ = nullptr; size_t cap_keep_bits_ = 0;
-  void* d_runs_ = nullptr; size_t cap_runs_ = 0;
-  uint32_t* d_skip_info_ = nullptr;
-  uint32_t* h_run_skip_ = nullptr;  // pinned (Run)
+  uint32_t* h_run_skip_ = nullptr;  // pinned skip counters (Run)
   uint32_t k1_grid_cap_ = 0;        // TSG_DIAG_K1_GRID: at most this many K1 workgroups (tests; 0: no cap)
   void NoteSkip(const uint32_t* info, BatchStats* st) const;
-  void* d_kw_ = nullptr; size_t cap_kw_ = 0;
-  void* d_flags_ = nullptr; size_t cap_flags_ = 0;
   void* d_hits_ = nullptr; size_t cap_hits_ = 0;
-  void* d_cands_ = nullptr; size_t cap_cands_ = 0;
   void* d_folds_ = nullptr; size_t cap_folds_ = 0;
   void* d_wins_ = nullptr; size_t cap_wins_ = 0;  // TSG_K2_PACK experiment: packed confirm windows
-  uint32_t* d_counters_ = nullptr;  // [0] hits [1] cands [2] special files [3] hit overflow [4] cand overflow
-                                    // [7] flagged-block records [8] record overflow
-                                    // [9] fold sites [10] fold-site overflow
-                                    // [6] full-scan list overflow [11] anchor-item matches [13] open pairs
   // host-batch streaming (RunHost): a ring of staging buffers, a copy stream
   hipStream_t copy_stream_ = nullptr;
   static constexpr int kNStage = 4;  // staging buffers: the copier runs up to three chunks ahead
@@ -448,7 +484,6 @@ class GpuEngine {
   void* d_fs_pairs_ = nullptr; size_t cap_fs_pairs_ = 0;  // FsPair list
   void* d_fs_tasks_ = nullptr; size_t cap_fs_tasks_ = 0;  // 4 x FsTask lists (by NFA width)
   void* d_fs_wave_ = nullptr; size_t cap_fs_wave_ = 0;    // pairs run wave-wide
-  uint32_t* d_fs_ctr_ = nullptr;                          // [0] pairs [1..4] tasks [5] wave pairs
   hipEvent_t ev_fs_ = nullptr;
   hipEvent_t ev_sync_ = nullptr;  // blocking-sync: the host waits asleep, not spinning
   bool blocking_sync_ = true;

@@ -173,7 +173,7 @@ static_assert(kFChunks * kChunk == kFTile && kFChunks == 4, "a tile's newline co
 // ---------------------------------------------------------------------------
 // Scans with a skip list: the tiles K1 streams
 // ---------------------------------------------------------------------------
-// Counters of such a scan (engine.h d_skip_info_), cleared by K0.
+// Counters of such a scan (engine.h WorkSet::skip_info), cleared by K0.
 constexpr uint32_t kSkRuns = 0, kSkKept = 1, kSkTailKept = 2, kSkFiles = 3, kSkBytes = 4 /* u64: 4, 5 */,
                    kSkWaveRuns = 6, kSkTiles = 7;
 
@@ -2574,6 +2574,23 @@ GpuEngine::GpuEngine(const CompiledRules& cr, int device) : device_(device) {
     err_ = "hipStreamCreate failed";
     return;
   }
+  {  // the K0 phase and the read-back of pipelined scans run beside the engine stream
+    if (const char* e = std::getenv("TSG_OVERLAP_K0")) overlap_k0_ = std::atoi(e) != 0;
+    if (const char* e = std::getenv("TSG_READBACK_STREAM")) readback_stream_ = std::atoi(e) != 0;
+    int lo = 0, hi = 0;
+    if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) lo = hi = 0;
+    bool ok = hipStreamCreateWithPriority(&aux_stream_, hipStreamNonBlocking, hi) == hipSuccess &&
+              hipStreamCreateWithFlags(&rb_stream_, hipStreamNonBlocking) == hipSuccess;
+    for (WorkSet& W : sets_)
+      ok = ok && hipEventCreateWithFlags(&W.free_ev, hipEventDisableTiming) == hipSuccess &&
+           hipEventCreateWithFlags(&W.k0_done, hipEventDisableTiming) == hipSuccess;
+    for (auto& e : ev_k0_) ok = ok && hipEventCreate(&e) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&k2_done_, hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+      err_ = "hipStreamCreate / hipEventCreate failed (K0 and read-back streams)";
+      return;
+    }
+  }
   for (auto& e : ev_copied_) hipEventCreateWithFlags(&e, hipEventDisableTiming);
   for (auto& e : ev_h2d_) hipEventCreate(&e);
   for (auto& e : ev_x_) hipEventCreate(&e);
@@ -2619,10 +2636,11 @@ GpuEngine::GpuEngine(const CompiledRules& cr, int device) : device_(device) {
       !Upload(&err_, &d_nfa_, cr.nfa.data(), cr.nfa.size()) ||
       !Upload(&err_, &d_fullscan_rules_, fullscan_rules_.data(), fullscan_rules_.size()))
     return;
-  if (hipMalloc(&d_counters_, 64) != hipSuccess || hipMalloc(&d_fs_ctr_, 64) != hipSuccess) {
-    err_ = "hipMalloc counters";
-    return;
-  }
+  for (WorkSet& W : sets_)
+    if (hipMalloc(&W.counters, 64) != hipSuccess || hipMalloc(&W.fs_ctr, 64) != hipSuccess) {
+      err_ = "hipMalloc counters";
+      return;
+    }
   // streaming prefilter tables (filter.h)
   {
     const FilterTables* ft = cr.filter.get();
@@ -2921,11 +2939,21 @@ GpuEngine::~GpuEngine() {
   if (reaper_.joinable()) reaper_.join();
   hipSetDevice(device_);
   void* ps[] = {d_item_diag_, d_fold_pairs_, d_kwfold_pairs_, d_fold_idx_off_, d_fold_idx_items_, d_fold_first_, d_reach_, d_core_, d_group_items_, d_bucket_groups_, d_ftabs_, d_folds_, d_recs_, d_anchors_,
-                d_rules_, d_rule_kw_, d_nfa_, d_fullscan_rules_, d_counters_, d_chunk_file_, d_nl_, d_kw_,
-                d_flags_, d_hits_, d_cands_, d_fs_pairs_, d_fs_tasks_, d_fs_wave_, d_fs_ctr_, d_xlen_, d_xoff_, d_xscan_,
-                d_xf_, d_gfiles_, d_gdst_, d_gbuf_, d_wins_, d_keep_bits_, d_runs_, d_skip_info_};
+                d_rules_, d_rule_kw_, d_nfa_, d_fullscan_rules_, d_nl_,
+                d_hits_, d_fs_pairs_, d_fs_tasks_, d_fs_wave_, d_xlen_, d_xoff_, d_xscan_,
+                d_xf_, d_gfiles_, d_gdst_, d_gbuf_, d_wins_};
   for (void* p : ps)
     if (p) hipFree(p);
+  for (WorkSet& W : sets_) {
+    for (void* p : {W.chunk_file, W.keep_bits, W.runs, static_cast<void*>(W.skip_info), W.kw, W.flags, W.cands,
+                    static_cast<void*>(W.counters), static_cast<void*>(W.fs_ctr)})
+      if (p) hipFree(p);
+    if (W.free_ev) hipEventDestroy(W.free_ev);
+    if (W.k0_done) hipEventDestroy(W.k0_done);
+  }
+  for (auto& e : ev_k0_)
+    if (e) hipEventDestroy(e);
+  if (k2_done_) hipEventDestroy(k2_done_);
   for (int b = 0; b < kNStage; b++)
   {
     for (void* p : {d_stage_[b], d_stage_off_[b], d_kind_[b], d_gsrc_[b]})
@@ -2943,6 +2971,8 @@ GpuEngine::~GpuEngine() {
       if (e) hipEventDestroy(e);
     if (S.ev_fs) hipEventDestroy(S.ev_fs);
     if (S.done) hipEventDestroy(S.done);
+    for (hipEvent_t e : {S.ev_k0[0], S.ev_k0[1], S.fin, S.rb_done})
+      if (e) hipEventDestroy(e);
     if (S.h_cnt) hipHostFree(S.h_cnt);
     if (S.h_skip) hipHostFree(S.h_skip);
     if (S.h_cands) hipHostFree(S.h_cands);
@@ -2970,14 +3000,22 @@ GpuEngine::~GpuEngine() {
   for (void* h : {static_cast<void*>(h_run_cnt_), static_cast<void*>(h_run_skip_), h_run_cands_, h_gup_, h_gbuf_})
     if (h) hipHostFree(h);
   if (copy_stream_) hipStreamDestroy(copy_stream_);
+  if (aux_stream_) hipStreamDestroy(aux_stream_);
+  if (rb_stream_) hipStreamDestroy(rb_stream_);
   if (stream_) hipStreamDestroy(stream_);
 }
 
 bool GpuEngine::Ensure(void** p, size_t* cap, size_t need) {
   if (*p && *cap >= need) return true;
-  if (*p) {  // queued work (an Enqueue'd scan) may still read the old buffer
+  if (*p) {
+    // Queued work (an Enqueue'd scan) may still read the old buffer, on any of
+    // the engine's streams (§4.10 rule 4).  The K0 stream goes first: the engine
+    // stream waits for it, and the read-back and fetch streams for the engine's.
+    HIP_OK(hipStreamSynchronize(aux_stream_));
     HIP_OK(hipStreamSynchronize(stream_));
-    hipFree(*p);
+    HIP_OK(hipStreamSynchronize(rb_stream_));
+    if (fetch_stream_) HIP_OK(hipStreamSynchronize(fetch_stream_));
+    hipFree(*p);  // (waits for the whole device besides)
   }
   *p = nullptr;
   // (+1/8: a batch slightly larger than the last does not free and reallocate again --
@@ -3355,6 +3393,7 @@ bool GpuEngine::RunHost(const uint8_t* h_arena, uint64_t n_bytes, const uint64_t
         st->fold_sites += cs.fold_sites;
         st->ms_finalize += cs.ms_finalize;
         st->ms_chunkmap += cs.ms_chunkmap;
+        st->ms_k0 += cs.ms_k0;
         st->ms_total += cs.ms_total;
       }
     }
@@ -3530,7 +3569,9 @@ bool GpuEngine::Enqueue(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t
   auto fail = [&] {
     // copies into the slot's pinned buffers may be queued: let them finish
     // before the slot (and its buffers) can be reused or freed
+    (void)hipStreamSynchronize(aux_stream_);
     (void)hipStreamSynchronize(stream_);
+    (void)hipStreamSynchronize(rb_stream_);
     if (fetch && fetch_stream_) (void)hipStreamSynchronize(fetch_stream_);
     if (S.lease) GiveFetchBuf(S.lease, S.lease_cap);
     S.lease = nullptr;
@@ -3546,8 +3587,11 @@ bool GpuEngine::Enqueue(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t
   if (!S.done) {
     bool ok = hipEventCreateWithFlags(&S.done, hipEventBlockingSync | hipEventDisableTiming) == hipSuccess &&
               hipEventCreate(&S.ev_fs) == hipSuccess &&
+              hipEventCreateWithFlags(&S.fin, hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(&S.rb_done, hipEventDisableTiming) == hipSuccess &&
               hipHostMalloc(reinterpret_cast<void**>(&S.h_cnt), 64, hipHostMallocDefault) == hipSuccess;
     for (auto& e : S.ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    for (auto& e : S.ev_k0) ok = ok && hipEventCreate(&e) == hipSuccess;
     if (!ok) {
       err_ = "ticket events / pinned counters";
       return fail();
@@ -3620,18 +3664,46 @@ bool GpuEngine::Enqueue(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t
     err_ = "pinned skip counters";
     return fail();
   }
-  if (!EnqueuePhase(d_arena, n_bytes, d_offsets, n_files, n_chunks, S.ev, S.ev_fs, skip) ||
-      hipMemcpyAsync(S.h_cnt, d_counters_, 64, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
-      (S.has_skip && hipMemcpyAsync(S.h_skip, d_skip_info_, 64, hipMemcpyDeviceToHost, stream_) != hipSuccess) ||
-      hipMemcpyAsync(S.h_cands, d_cands_, size_t(n_copy) * sizeof(Candidate), hipMemcpyDeviceToHost, stream_) !=
-          hipSuccess ||
-      // the fetch right behind: no host round trip between the candidates and its launch
-      (fetch && (!(S.win ? IssueFetchWin(d_arena, n_bytes, d_offsets, n_files, S.prm, S.stage, S.fetch_copy,
-                                         static_cast<uint8_t*>(S.lease), S.h_fctr, S.ev_f[0])
-                         : IssueFetch(d_arena, d_offsets, n_files, nullptr, S.direct, S.stage, S.fetch_copy,
-                                      static_cast<uint8_t*>(S.lease), S.h_fctr, S.ev_f[0])) ||
-                 hipEventRecord(S.ev_f[1], fetch_stream_) != hipSuccess)) ||
-      hipEventRecord(S.done, fetch ? fetch_stream_ : stream_) != hipSuccess) {
+  WorkSet& W = sets_[set_turn_];  // (4 slots, 2 sets: a slot and a set do not stay paired)
+  set_turn_ = (set_turn_ + 1) % kSets;
+  auto enqueue = [&]() -> bool {
+    if (!EnqueuePhase(d_arena, n_bytes, d_offsets, n_files, n_chunks, W, overlap_k0_, S.ev, S.ev_fs, S.ev_k0, skip))
+      return false;
+    // The read-back, behind finalize: on a stream of its own, so the next scan's
+    // K1 does not queue behind 64 B x n_copy of copies (TSG_READBACK_STREAM=0: on
+    // the engine stream).  Not copy_stream_: the staging ring's H2D copies must
+    // not wait for it.
+    hipStream_t rs = stream_;
+    if (readback_stream_) {
+      HIP_OK(hipEventRecord(S.fin, stream_));
+      HIP_OK(hipStreamWaitEvent(rb_stream_, S.fin, 0));
+      rs = rb_stream_;
+    }
+    HIP_OK(hipMemcpyAsync(S.h_cnt, W.counters, 64, hipMemcpyDeviceToHost, rs));
+    if (S.has_skip) HIP_OK(hipMemcpyAsync(S.h_skip, W.skip_info, 64, hipMemcpyDeviceToHost, rs));
+    HIP_OK(hipMemcpyAsync(S.h_cands, W.cands, size_t(n_copy) * sizeof(Candidate), hipMemcpyDeviceToHost, rs));
+    hipStream_t ds = rs;  // the stream whose tail ends the scan's last read of its set
+    if (fetch) {
+      // the fetch right behind finalize on the engine stream (its kernels read the scan's own
+      // set): no host round trip between the candidates and its launch
+      if (!(S.win ? IssueFetchWin(W, d_arena, n_bytes, d_offsets, n_files, S.prm, S.stage, S.fetch_copy,
+                                  static_cast<uint8_t*>(S.lease), S.h_fctr, S.ev_f[0])
+                  : IssueFetch(W, d_arena, d_offsets, n_files, nullptr, S.direct, S.stage, S.fetch_copy,
+                               static_cast<uint8_t*>(S.lease), S.h_fctr, S.ev_f[0])))
+        return false;
+      HIP_OK(hipEventRecord(S.ev_f[1], fetch_stream_));
+      if (readback_stream_) {  // S.done covers the read-back too
+        HIP_OK(hipEventRecord(S.rb_done, rb_stream_));
+        HIP_OK(hipStreamWaitEvent(fetch_stream_, S.rb_done, 0));
+      }
+      ds = fetch_stream_;
+    }
+    HIP_OK(hipEventRecord(S.done, ds));
+    HIP_OK(hipEventRecord(W.free_ev, ds));  // rule 1: the K0 that next fills the set waits for this
+    W.free_rec = true;
+    return true;
+  };
+  if (!enqueue()) {
     if (err_.empty()) err_ = "Enqueue: HIP call failed";
     return fail();
   }
@@ -3796,42 +3868,93 @@ bool GpuEngine::Collect(Ticket* t, std::vector<Candidate>* cands, BatchStats* st
   if (S.has_fs) hipEventElapsedTime(&st->ms_fullscan, S.ev_fs, S.ev[5]);
   hipEventElapsedTime(&st->ms_chunkmap, S.ev[0], S.ev[1]);
   hipEventElapsedTime(&st->ms_total, S.ev[0], S.ev[6]);
+  hipEventElapsedTime(&st->ms_k0, S.ev_k0[0], S.ev_k0[1]);
   release();
   return true;
 }
 
-// The GPU phase of one scan, enqueued on stream_: clears, K0 .. finalize,
-// with the phase events recorded into ev[0..6] (ev_fs before the full scan).
+// Both work sets sized for the batch (§4.10 rule 4): a set regrown alone could
+// be freed while the other's scan runs, and the next Enqueue would regrow that
+// one in turn -- two device-wide waits instead of one.
+bool GpuEngine::EnsureSets(uint64_t n_chunks, uint32_t n_files, uint64_t f_tiles, bool skip) {
+  for (WorkSet& W : sets_) {
+    if (skip) {
+      if (!Ensure(&W.keep_bits, &W.cap_keep_bits, KeepWords(f_tiles) * 8) ||
+          !Ensure(&W.runs, &W.cap_runs, (f_tiles / 2 + 2) * sizeof(uint2)))
+        return false;
+      if (!W.skip_info) {
+        HIP_OK(hipMalloc(reinterpret_cast<void**>(&W.skip_info), 64));
+        HIP_OK(hipMemset(W.skip_info, 0, 64));
+      }
+    }
+    if (!Ensure(&W.chunk_file, &W.cap_chunk_file, n_chunks * 4) ||
+        !Ensure(&W.kw, &W.cap_kw, size_t(n_files) * kw_words_ * 4) ||
+        !Ensure(&W.flags, &W.cap_flags, size_t(n_files) * 4) ||
+        !Ensure(&W.cands, &W.cap_cands, size_t(cand_cap_) * sizeof(Candidate)))
+      return false;
+  }
+  return true;
+}
+
+// The GPU phase of one scan: clears, K0 .. finalize, with the phase events
+// recorded into ev[0..6] (ev_fs before the full scan) and the K0 phase's own
+// span into ev_k0[0..1].  K1 .. finalize run on stream_; the K0 phase -- it
+// needs only the offsets and the skip marks, which exist when the scan is
+// submitted -- on aux_stream_ (k0_aux) beside the kernels of the scan before,
+// or on stream_ too.  What the K0 phase writes, and what is read after
+// finalize, lies in the work set W; the order that keeps that right
+// (DESIGN.md §4.10):
+//  1. Set reuse.  Enqueue takes the two sets in turn, so W was last used by
+//     the Enqueue'd scan before the last.  The stream K0 runs on waits for
+//     W.free_ev, recorded beside that scan's Slot::done: behind its read-back
+//     and, for a device-only batch, its fetch (kernels and copies).  Slots and
+//     sets are not paired (4 slots, 2 sets): the event belongs to the set.
+//  2. K1 ordering.  stream_ waits for this scan's own k0_done before ev[1].
+//  3. Synchronous paths.  Run (and with it RunHost, the gather path and the
+//     rerun after Collect) and the fetches it issues use sets_[0] with
+//     everything on stream_ (k0_aux false).  stream_ then waits for W.free_ev
+//     and for the last W.k0_done: an Enqueue'd scan's K0 on aux_stream_ and its
+//     read-back on rb_stream_ are over before the set is written again.  Run
+//     waits for its own work before it returns, so nothing it queued is left
+//     for a later Enqueue to order against.
+//  4. Regrowth.  Ensure frees a buffer only after every stream of the engine
+//     drained (and hipFree waits for the device); both sets are sized together
+//     (EnsureSets), under the lock the caller of Enqueue / Run holds.
+//  5. Off-stream readers.  The buffers that stay single (d_nl_, d_recs_,
+//     d_hits_, d_folds_, d_wins_, the full-scan lists) are touched by kernels on
+//     stream_ only: fetch.hip and fetch_windows.hip run on stream_ and read the
+//     set's candidates and counter besides the arena; materialize.hip and
+//     classify.hip read the arena and the offsets alone.
 bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
-                             uint64_t n_chunks, hipEvent_t* ev, hipEvent_t ev_fs, const SkipIn* skip) {
+                             uint64_t n_chunks, WorkSet& W, bool k0_aux, hipEvent_t* ev, hipEvent_t ev_fs,
+                             hipEvent_t* ev_k0, const SkipIn* skip) {
   const uint64_t f_tiles = (n_bytes + kFTile - 1) / kFTile;
   if (skip && (!skip->d_skip || f_tiles == 0)) skip = nullptr;
-  if (skip) {
-    if (!Ensure(&d_keep_bits_, &cap_keep_bits_, KeepWords(f_tiles) * 8) ||
-        !Ensure(&d_runs_, &cap_runs_, (f_tiles / 2 + 2) * sizeof(uint2)))
-      return false;
-    if (!d_skip_info_) {
-      HIP_OK(hipMalloc(reinterpret_cast<void**>(&d_skip_info_), 64));
-      HIP_OK(hipMemset(d_skip_info_, 0, 64));
-    }
-    // the marks are written by the path kernel on a stream of its own
-    if (skip->ready) HIP_OK(hipStreamWaitEvent(stream_, skip->ready, 0));
-  }
-  if (!Ensure(&d_chunk_file_, &cap_chunk_file_, n_chunks * 4) || !Ensure(&d_nl_, &cap_nl_, (n_chunks + 8) * 2) ||
-      !Ensure(&d_kw_, &cap_kw_, size_t(n_files) * kw_words_ * 4) ||
-      !Ensure(&d_flags_, &cap_flags_, size_t(n_files) * 4) ||
+  if (!EnsureSets(n_chunks, n_files, f_tiles, skip != nullptr)) return false;
+  if (!Ensure(&d_nl_, &cap_nl_, (n_chunks + 8) * 2) ||
       !Ensure(&d_folds_, &cap_folds_, size_t(fold_cap_) * sizeof(FoldSite)) ||
       !Ensure(&d_recs_, &cap_recs_, size_t(rec_cap_) * 4) ||
-      !Ensure(&d_hits_, &cap_hits_, size_t(hit_cap_) * 12) ||
-      !Ensure(&d_cands_, &cap_cands_, size_t(cand_cap_) * sizeof(Candidate)))
+      !Ensure(&d_hits_, &cap_hits_, size_t(hit_cap_) * 12))
     return false;
   if (n_fullscan_rules_ > 0 &&
       (!Ensure(&d_fs_pairs_, &cap_fs_pairs_, size_t(fs_pair_cap_) * sizeof(FsPair)) ||
        !Ensure(&d_fs_wave_, &cap_fs_wave_, size_t(fs_pair_cap_) * 4) ||
        !Ensure(&d_fs_tasks_, &cap_fs_tasks_, size_t(fs_task_cap_) * 4 * sizeof(FsTask))))
     return false;
-  HIP_OK(hipEventRecord(ev[0], stream_));  // the GPU phase: K0 (with the clears) .. finalize
-  if (d_item_diag_) HIP_OK(hipMemsetAsync(d_item_diag_, 0, 8 * std::max<size_t>(n_fitems_, 1), stream_));
+  const hipStream_t k0s = k0_aux ? aux_stream_ : stream_;
+  // the marks are written by the path kernel on a stream of its own
+  if (skip && skip->ready) HIP_OK(hipStreamWaitEvent(k0s, skip->ready, 0));
+  if (W.free_rec) HIP_OK(hipStreamWaitEvent(k0s, W.free_ev, 0));                // rule 1
+  if (!k0_aux && W.k0_rec) HIP_OK(hipStreamWaitEvent(stream_, W.k0_done, 0));  // rule 3
+  // K0 starts behind the K2 of the scan before, beside its latency-bound tail: launched together with
+  // a K1, its workgroups take wave slots first and K1's placement suffers for the whole kernel (+0.8 ms
+  // on C2); beside K2 it slows K2 by 0.1 ms
+  if (k0_aux && k2_rec_) HIP_OK(hipStreamWaitEvent(aux_stream_, k2_done_, 0));
+  if (!k0_aux) {
+    HIP_OK(hipEventRecord(ev[0], stream_));  // the GPU phase: K0 (with the clears) .. finalize
+    if (d_item_diag_) HIP_OK(hipMemsetAsync(d_item_diag_, 0, 8 * std::max<size_t>(n_fitems_, 1), stream_));
+  }
+  HIP_OK(hipEventRecord(ev_k0[0], k0s));
   {  // every chunk below n_bytes gets its file (no clear needed)
     const uint64_t used = (n_bytes + kChunk - 1) / kChunk;
     const uint64_t runs = (used + kK0Run - 1) / kK0Run;
@@ -3839,25 +3962,33 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
     const uint64_t work = std::max(runs, clear_q);
     const uint32_t blocks = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((work + 255) / 256, 8192)));
     ClearParams z;
-    z.flags = static_cast<uint32_t*>(d_flags_);
-    z.kw = static_cast<uint32_t*>(d_kw_);
+    z.flags = static_cast<uint32_t*>(W.flags);
+    z.kw = static_cast<uint32_t*>(W.kw);
     z.n_kw = uint64_t(n_files) * kw_words_;
-    z.counters = d_counters_;
-    z.fs_ctr = n_fullscan_rules_ > 0 ? d_fs_ctr_ : nullptr;
-    z.skip_info = skip ? d_skip_info_ : nullptr;
-    chunk_map_kernel<<<blocks, 256, 0, stream_>>>(d_offsets, n_files, used, static_cast<uint32_t*>(d_chunk_file_),
-                                                  z);
+    z.counters = W.counters;
+    z.fs_ctr = n_fullscan_rules_ > 0 ? W.fs_ctr : nullptr;
+    z.skip_info = skip ? W.skip_info : nullptr;
+    chunk_map_kernel<<<blocks, 256, 0, k0s>>>(d_offsets, n_files, used, static_cast<uint32_t*>(W.chunk_file), z);
+    HIP_OK(hipGetLastError());
   }
-  if (skip) {  // the kept tiles and their runs (d_skip_info_ was cleared by K0)
+  if (skip) {  // the kept tiles and their runs (W.skip_info was cleared by K0)
     const uint32_t blocks =
         uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((KeepWords(f_tiles) * 64 + 255) / 256, 4096)));
-    tile_keep_kernel<<<blocks, 256, 0, stream_>>>(d_offsets, n_files, static_cast<const uint32_t*>(d_chunk_file_),
-                                                  skip->d_skip, n_bytes, f_tiles,
-                                                  static_cast<uint64_t*>(d_keep_bits_), d_skip_info_);
+    tile_keep_kernel<<<blocks, 256, 0, k0s>>>(d_offsets, n_files, static_cast<const uint32_t*>(W.chunk_file),
+                                              skip->d_skip, n_bytes, f_tiles, static_cast<uint64_t*>(W.keep_bits),
+                                              W.skip_info);
     HIP_OK(hipGetLastError());
-    tile_runs_kernel<<<1, kRunThreads, 0, stream_>>>(static_cast<const uint64_t*>(d_keep_bits_), f_tiles,
-                                                     static_cast<uint2*>(d_runs_), d_skip_info_);
+    tile_runs_kernel<<<1, kRunThreads, 0, k0s>>>(static_cast<const uint64_t*>(W.keep_bits), f_tiles,
+                                                 static_cast<uint2*>(W.runs), W.skip_info);
     HIP_OK(hipGetLastError());
+  }
+  HIP_OK(hipEventRecord(ev_k0[1], k0s));
+  if (k0_aux) {  // rule 2: K1 starts behind the scan's own K0; ev[0] -> ev[1] is what it still waits for
+    HIP_OK(hipEventRecord(W.k0_done, aux_stream_));
+    W.k0_rec = true;
+    HIP_OK(hipEventRecord(ev[0], stream_));
+    if (d_item_diag_) HIP_OK(hipMemsetAsync(d_item_diag_, 0, 8 * std::max<size_t>(n_fitems_, 1), stream_));
+    HIP_OK(hipStreamWaitEvent(stream_, W.k0_done, 0));
   }
   // K1: streaming filter -> flagged block records
   FilterParams fp;
@@ -3868,9 +3999,9 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
   fp.nl = static_cast<uint16_t*>(d_nl_);
   fp.recs = static_cast<uint32_t*>(d_recs_);
   fp.rec_cap = rec_cap_;
-  fp.counters = d_counters_;
-  fp.runs = skip ? static_cast<const uint2*>(d_runs_) : nullptr;
-  fp.run_info = skip ? d_skip_info_ : nullptr;
+  fp.counters = W.counters;
+  fp.runs = skip ? static_cast<const uint2*>(W.runs) : nullptr;
+  fp.run_info = skip ? W.skip_info : nullptr;
   uint32_t f_grid =
       uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((f_tiles + kScanWaves - 1) / kScanWaves, 256 * kFWgPerCu)));
   if (k1_grid_cap_) f_grid = std::min(f_grid, k1_grid_cap_);
@@ -3884,7 +4015,7 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
   cp.arena = d_arena;
   cp.n_bytes = n_bytes;
   cp.off = d_offsets;
-  cp.chunk_file = static_cast<const uint32_t*>(d_chunk_file_);
+  cp.chunk_file = static_cast<const uint32_t*>(W.chunk_file);
   cp.nl = static_cast<const uint16_t*>(d_nl_);
   cp.reach = d_reach_;
   cp.tabs = d_ftabs_;
@@ -3900,14 +4031,14 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
   cp.nfa = d_nfa_;
   cp.recs = static_cast<const uint32_t*>(d_recs_);
   cp.rec_cap = rec_cap_;
-  cp.flags = static_cast<uint32_t*>(d_flags_);
-  cp.counters = d_counters_;
+  cp.flags = static_cast<uint32_t*>(W.flags);
+  cp.counters = W.counters;
   cp.hits = static_cast<uint32_t*>(d_hits_);
   cp.hit_cap = hit_cap_;
   cp.folds = static_cast<FoldSite*>(d_folds_);
   cp.fold_cap = fold_cap_;
   cp.diag = diag_confirm_;
-  cp.kwbits = static_cast<uint32_t*>(d_kw_);
+  cp.kwbits = static_cast<uint32_t*>(W.kw);
   cp.kw_words = kw_words_;
   cp.core = d_core_;
   cp.group_items = d_group_items_;
@@ -3929,7 +4060,7 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
   if (k2_pack && diag_mode_ == 0) {  // (experiment) the windows packed between K1 and K2, outside K2's events
     if (!Ensure(&d_wins_, &cap_wins_, size_t(rec_cap_) * 64)) return false;
     pack_windows_kernel<<<8192, 256, 0, stream_>>>(d_arena, n_bytes, static_cast<const uint32_t*>(d_recs_), rec_cap_,
-                                                   d_counters_, static_cast<uint8_t*>(d_wins_));
+                                                   W.counters, static_cast<uint8_t*>(d_wins_));
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(ev[2], stream_));  // re-recorded: K1 + pack count as the scan phase, K2 alone as confirm
     cp.wins = static_cast<const uint8_t*>(d_wins_);
@@ -3942,6 +4073,8 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
   }
   HIP_OK(hipGetLastError());
   HIP_OK(hipEventRecord(ev[3], stream_));
+  HIP_OK(hipEventRecord(k2_done_, stream_));
+  k2_rec_ = true;
   // fold runes: fold-tolerant item matching around each one
   FoldParams fo;
   fo.arena = d_arena;
@@ -3973,7 +4106,7 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
   fo.n_cap_s_idx = n_fold_cap_s_idx_;
   fo.hits = static_cast<uint32_t*>(d_hits_);
   fo.hit_cap = hit_cap_;
-  fo.counters = d_counters_;
+  fo.counters = W.counters;
   if (diag_mode_ == 0) {
     if (lds_tabs_)
       fold_kernel<true><<<fold_grid_, 64 * kFoldWaves, ftabs_fold_bytes_ + 32 * n_fitems_, stream_>>>(fo);
@@ -3999,8 +4132,8 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
     kf.n_cap_k = n_kwf_ck_;
     kf.folds = static_cast<const FoldSite*>(d_folds_);
     kf.fold_cap = fold_cap_;
-    kf.counters = d_counters_;
-    kf.kwbits = static_cast<uint32_t*>(d_kw_);
+    kf.counters = W.counters;
+    kf.kwbits = static_cast<uint32_t*>(W.kw);
     kf.kw_words = kw_words_;
     kwfold_kernel<<<1024, 64 * kFoldWaves, 0, stream_>>>(kf);
     HIP_OK(hipGetLastError());
@@ -4014,16 +4147,16 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
   np.anchors = d_anchors_;
   np.rules = d_rules_;
   np.rule_kw = d_rule_kw_;
-  np.kwbits = static_cast<const uint32_t*>(d_kw_);
+  np.kwbits = static_cast<const uint32_t*>(W.kw);
   np.kw_words = kw_words_;
-  np.flags = static_cast<const uint32_t*>(d_flags_);
+  np.flags = static_cast<const uint32_t*>(W.flags);
   np.nfa = d_nfa_;
   np.hits = static_cast<const uint32_t*>(d_hits_);
   np.hit_cap = hit_cap_;
-  np.counters = d_counters_;
+  np.counters = W.counters;
   static const uint32_t verify_diag = std::getenv("TSG_DIAG_VERIFY") ? uint32_t(std::atoi(std::getenv("TSG_DIAG_VERIFY"))) : 0u;
   np.diag = verify_diag;
-  np.cands = static_cast<Candidate*>(d_cands_);
+  np.cands = static_cast<Candidate*>(W.cands);
   np.cand_cap = cand_cap_;
   np.fullscan_rules = d_fullscan_rules_;
   np.n_fullscan_rules = n_fullscan_rules_;
@@ -4041,7 +4174,7 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
     fq.tasks = static_cast<FsTask*>(d_fs_tasks_);
     fq.task_cap = fs_task_cap_;
     fq.wave_pairs = static_cast<uint32_t*>(d_fs_wave_);
-    fq.ctr = d_fs_ctr_;
+    fq.ctr = W.fs_ctr;
     fq.task_min = fs_task_bytes_;  // (fq.ctr was cleared by K0)
     const uint64_t pairs = uint64_t(n_files) * n_fullscan_rules_;
     const uint32_t pb = uint32_t(std::min<uint64_t>(std::max<uint64_t>((pairs + 255) / 256, 1), 4096));
@@ -4107,7 +4240,7 @@ void GpuEngine::NoteFetch(uint64_t packed, uint64_t total) {
 // the fetch stream (engine.h).  h_flags: the marked files from the host
 // (pinned, n_files u32) instead of the candidate list of the scan just
 // enqueued.  copy_bytes (a multiple of 16) of the packed layout reach h_dst.
-bool GpuEngine::IssueFetch(const uint8_t* d_arena, const uint64_t* d_offsets, uint32_t n_files,
+bool GpuEngine::IssueFetch(const WorkSet& W, const uint8_t* d_arena, const uint64_t* d_offsets, uint32_t n_files,
                            const uint32_t* h_flags, uint64_t direct, uint64_t stage, uint64_t copy_bytes,
                            uint8_t* h_dst, void* h_ctr, hipEvent_t ev0) {
   if (!EnsureFetchStream()) return false;
@@ -4121,7 +4254,7 @@ bool GpuEngine::IssueFetch(const uint8_t* d_arena, const uint64_t* d_offsets, ui
   if (h_flags)
     HIP_OK(hipMemcpyAsync(FetchFlags(d_fscratch_, n_files), h_flags, size_t(n_files) * 4, hipMemcpyHostToDevice,
                           stream_));
-  HIP_OK(FetchPlan(h_flags ? nullptr : static_cast<const Candidate*>(d_cands_), d_counters_ + 1, cand_cap_, d_offsets,
+  HIP_OK(FetchPlan(h_flags ? nullptr : static_cast<const Candidate*>(W.cands), W.counters + 1, cand_cap_, d_offsets,
                    n_files, direct, d_fscratch_, ctr, stream_));
   HIP_OK(hipMemcpyAsync(h_ctr, ctr, sizeof(FetchCounters), hipMemcpyDeviceToHost, stream_));
   uint8_t* st = static_cast<uint8_t*>(d_fstage_);
@@ -4177,8 +4310,8 @@ bool GpuEngine::FetchNow(const uint8_t* d_arena, const uint64_t* d_offsets, uint
     for (uint32_t f = 0; f < n_files; f++) hf[f] = out->fetched[f];
     h_flags = hf;
   }
-  if (!IssueFetch(d_arena, d_offsets, n_files, h_flags, direct, stage, P.packed, static_cast<uint8_t*>(lease),
-                  h_run_fctr_, ev_run_f_[0]))
+  if (!IssueFetch(sets_[0], d_arena, d_offsets, n_files, h_flags, direct, stage, P.packed,
+                  static_cast<uint8_t*>(lease), h_run_fctr_, ev_run_f_[0]))
     return false;
   for (uint32_t f : P.direct)  // contiguous in the arena: straight to their place
     HIP_OK(hipMemcpyAsync(static_cast<uint8_t*>(lease) + out->off[f], d_arena + out->h_offsets[f],
@@ -4201,9 +4334,9 @@ bool GpuEngine::FetchNow(const uint8_t* d_arena, const uint64_t* d_offsets, uint
 // rounds on the fetch stream -- IssueFetch with fetch_windows.h in the place of fetch.h.  The
 // staging buffer, its two events and the device counter record are the files mode's (one fetch
 // at a time uses them, in stream order).  copy_bytes: a multiple of 256.
-bool GpuEngine::IssueFetchWin(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
-                              const FetchWinParams& prm, uint64_t stage, uint64_t copy_bytes, uint8_t* h_dst,
-                              void* h_ctr, hipEvent_t ev0) {
+bool GpuEngine::IssueFetchWin(const WorkSet& W, const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets,
+                              uint32_t n_files, const FetchWinParams& prm, uint64_t stage, uint64_t copy_bytes,
+                              uint8_t* h_dst, void* h_ctr, hipEvent_t ev0) {
   static_assert(sizeof(FetchWinCounters) == sizeof(FetchCounters), "one device record serves both modes");
   if (!EnsureFetchStream()) return false;
   const size_t stage_need = size_t(std::max<uint64_t>(std::min(stage, copy_bytes), kFetchGranule));
@@ -4213,7 +4346,7 @@ bool GpuEngine::IssueFetchWin(const uint8_t* d_arena, uint64_t n_bytes, const ui
     return false;
   FetchWinCounters* ctr = static_cast<FetchWinCounters*>(d_fctr_);
   HIP_OK(hipEventRecord(ev0, stream_));
-  HIP_OK(FetchWinPlan(static_cast<const Candidate*>(d_cands_), d_counters_ + 1, cand_cap_, d_offsets, n_files, n_bytes,
+  HIP_OK(FetchWinPlan(static_cast<const Candidate*>(W.cands), W.counters + 1, cand_cap_, d_offsets, n_files, n_bytes,
                       d_rule_max_len_, uint32_t(h_rule_max_len_.size()), prm, d_wscratch_, ctr, stream_));
   HIP_OK(hipMemcpyAsync(h_ctr, ctr, sizeof(FetchWinCounters), hipMemcpyDeviceToHost, stream_));
   uint8_t* st = static_cast<uint8_t*>(d_fstage_);
@@ -4266,8 +4399,8 @@ bool GpuEngine::FetchNowWin(const uint8_t* d_arena, uint64_t n_bytes, const uint
   out->lease = lease;
   out->lease_cap = cap;
   out->buf = static_cast<const uint8_t*>(lease);
-  if (!IssueFetchWin(d_arena, n_bytes, d_offsets, n_files, out->prm, stage, packed, static_cast<uint8_t*>(lease),
-                     h_run_fctr_, ev_run_f_[0]))
+  if (!IssueFetchWin(sets_[0], d_arena, n_bytes, d_offsets, n_files, out->prm, stage, packed,
+                     static_cast<uint8_t*>(lease), h_run_fctr_, ev_run_f_[0]))
     return false;
   HIP_OK(hipEventRecord(ev_run_f_[1], fetch_stream_));
   HIP_OK(WaitEvent(ev_run_f_[1]));
@@ -4290,6 +4423,9 @@ bool GpuEngine::FetchNowWin(const uint8_t* d_arena, uint64_t n_bytes, const uint
 bool GpuEngine::FetchFiles(const uint8_t* d_arena, const uint64_t* d_offsets, uint32_t n_files,
                            const std::vector<uint8_t>& want, FetchOut* out) {
   HIP_OK(hipSetDevice(device_));
+  const WorkSet& W = sets_[0];  // FetchNow's plan names the set's counter: ordered as Run is (§4.10 rule 3)
+  if (W.free_rec) HIP_OK(hipStreamWaitEvent(stream_, W.free_ev, 0));
+  if (W.k0_rec) HIP_OK(hipStreamWaitEvent(stream_, W.k0_done, 0));
   return FetchNow(d_arena, d_offsets, n_files, want, true, out);
 }
 
@@ -4310,15 +4446,16 @@ bool GpuEngine::Run(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_
   uint64_t n_chunks = (n_bytes + kChunk - 1) / kChunk;
   if (n_chunks == 0) n_chunks = 1;
   InitCaps(n_bytes);
+  WorkSet& W = sets_[0];  // the synchronous path: one set, everything on stream_ (§4.10 rule 3)
   for (int attempt = 0; attempt < 8; attempt++) {
-    if (!EnqueuePhase(d_arena, n_bytes, d_offsets, n_files, n_chunks, ev_, ev_fs_, skip)) return false;
+    if (!EnqueuePhase(d_arena, n_bytes, d_offsets, n_files, n_chunks, W, false, ev_, ev_fs_, ev_k0_, skip)) return false;
     uint32_t cnt[16];
     if (!h_run_cnt_) HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&h_run_cnt_), 64, hipHostMallocDefault));
-    HIP_OK(hipMemcpyAsync(h_run_cnt_, d_counters_, sizeof(cnt), hipMemcpyDeviceToHost, stream_));
+    HIP_OK(hipMemcpyAsync(h_run_cnt_, W.counters, sizeof(cnt), hipMemcpyDeviceToHost, stream_));
     const bool has_skip = skip && skip->d_skip && n_bytes > 0;
     if (has_skip) {
       if (!h_run_skip_) HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&h_run_skip_), 64, hipHostMallocDefault));
-      HIP_OK(hipMemcpyAsync(h_run_skip_, d_skip_info_, 64, hipMemcpyDeviceToHost, stream_));
+      HIP_OK(hipMemcpyAsync(h_run_skip_, W.skip_info, 64, hipMemcpyDeviceToHost, stream_));
     }
     HIP_OK(WaitStream());
     if (has_skip) NoteSkip(h_run_skip_, st);
@@ -4338,7 +4475,7 @@ bool GpuEngine::Run(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_
     st->cand_overflow = cnt[4] != 0;
     if (cnt[6]) {  // full-scan pair / task list overflow: grow to the counts seen
       uint32_t fc[16];
-      HIP_OK(hipMemcpy(fc, d_fs_ctr_, sizeof(fc), hipMemcpyDeviceToHost));
+      HIP_OK(hipMemcpy(fc, W.fs_ctr, sizeof(fc), hipMemcpyDeviceToHost));
       fs_pair_cap_ = std::max<uint32_t>(fs_pair_cap_, fc[0] + fc[0] / 4 + 1024);
       const uint32_t mt = std::max(std::max(fc[1], fc[2]), std::max(fc[3], fc[4]));
       constexpr uint64_t kMaxTasks = 0x7FFFFFFFu / sizeof(FsTask) / 4;
@@ -4370,7 +4507,7 @@ bool GpuEngine::Run(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_
     if (cnt[1]) {
       const size_t nb = size_t(cnt[1]) * sizeof(Candidate);
       if (!EnsureHost(&h_run_cands_, &cap_h_run_cands_, nb)) return false;
-      HIP_OK(hipMemcpyAsync(h_run_cands_, d_cands_, nb, hipMemcpyDeviceToHost, stream_));
+      HIP_OK(hipMemcpyAsync(h_run_cands_, W.cands, nb, hipMemcpyDeviceToHost, stream_));
       HIP_OK(WaitStream());
       std::memcpy(cands->data(), h_run_cands_, nb);
     }
@@ -4389,6 +4526,7 @@ bool GpuEngine::Run(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_
     st->fold_sites = cnt[9];
     hipEventElapsedTime(&st->ms_chunkmap, ev_[0], ev_[1]);
     hipEventElapsedTime(&st->ms_total, ev_[0], ev_[6]);
+    hipEventElapsedTime(&st->ms_k0, ev_k0_[0], ev_k0_[1]);
     if (fetch) {  // a device-only batch: the candidate files' bytes, sized exactly
       std::vector<uint8_t> want(n_files, 0);
       for (const Candidate& c : *cands)

@@ -589,6 +589,15 @@ class ScanResult:
             raise RuntimeError("tsg_debug_result_skip failed")
         return dict(zip(("files", "bytes", "tiles_dropped", "runs", "wave_runs_max", "tiles"), map(int, out)))
 
+    def k0_ms(self):
+        """The K0 phase's own span in ms (tsg_debug_result_k0): in a pipeline it runs beside the scan
+        before, and ms_chunkmap_kernel is only what the streaming filter still waited for."""
+        out = c.c_double()
+        self._sc._L.tsg_debug_result_k0.argtypes = [c.c_void_p, c.c_void_p]
+        if self._sc._L.tsg_debug_result_k0(self._h, c.byref(out)) != 0:
+            raise RuntimeError("tsg_debug_result_k0 failed")
+        return out.value
+
     def raw(self, lo=None, hi=None):
         p = c.c_void_p()
         n = c.c_uint64()

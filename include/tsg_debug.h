@@ -68,6 +68,9 @@ int tsg_debug_compile_ex(const struct tsg_global* g, const struct tsg_compile_op
 void tsg_debug_compiled_free(tsg_compiled* c);
 int tsg_debug_compiled_info(const tsg_compiled* c, struct tsg_table_info* out);
 int tsg_debug_rule(const tsg_compiled* c, uint32_t i, tsg_debug_rule_info* out);
+/* 1 when every match of rule i holds one of its keywords (rules.h RuleGpu::kw_match_implied: the
+ * kernels then neither test nor report its keyword gate), 0 otherwise, -1 for no such rule. */
+int tsg_debug_rule_gate_implied(const tsg_compiled* c, uint32_t i);
 int tsg_debug_anchor(const tsg_compiled* c, uint32_t j, uint32_t* rule, uint32_t* lit_len,
                      int32_t* off_lo, int32_t* off_hi);
 const char* tsg_debug_keyword(const tsg_compiled* c, uint32_t k);
@@ -189,6 +192,40 @@ int tsg_debug_result_skip(const struct tsg_result* r, uint64_t out[6]);
  * still waited for it (TSG_OVERLAP_K0=0 at scanner creation: the phase runs on
  * the engine stream and the two agree).  Summed over the chunks of a host batch. */
 int tsg_debug_result_k0(const struct tsg_result* r, double* ms_k0);
+
+/* ---- the candidate engine's stages (trivy_amd/csrc/engine.h StageDump) ----
+ * One synchronous scan (GpuEngine::Run) of a host batch on HIP device `device`,
+ * by an engine built from the compiled rules with the scanner's own constructor
+ * (the TSG_* variant switches read there apply).  The arena is uploaded into an
+ * allocation of exactly n_bytes + 64 whose last 64 bytes are `tail`: bytes no
+ * file owns, which no stage may attribute to one.  What the kernels left behind
+ * comes back before the dropped candidates are erased.  The caller sets the
+ * buffers and their capacities (in records); up to the capacity is written and
+ * the n_* fields receive the full counts:
+ *   hits        (file, file-relative literal end, anchor id) as three u64 each
+ *   kw          n_files x kw_words keyword bit words; flags: one u32 per file
+ *   nl, chunk_file   one entry per 1-KiB chunk of the arena
+ *   recs        flagged 16-B block indices (arena byte / 16)
+ *   cands       64-B Candidate records, kCandDrop ones included
+ * counters: the engine's 16 counters; caps: {hit, record, candidate} capacity
+ * of the device lists in this scan. */
+typedef struct tsg_debug_stage_dump {
+  uint32_t struct_size;  /* sizeof(tsg_debug_stage_dump) */
+  uint32_t kw_words;
+  uint32_t counters[16];
+  uint32_t caps[3];
+  uint32_t reserved_;
+  uint64_t* hits;        uint64_t hits_cap, n_hits;
+  uint32_t* kw;          uint64_t kw_cap, n_kw;
+  uint32_t* flags;       uint64_t flags_cap, n_flags;
+  uint16_t* nl;          uint64_t nl_cap, n_nl;
+  uint32_t* chunk_file;  uint64_t chunk_file_cap, n_chunk_file;
+  uint32_t* recs;        uint64_t recs_cap, n_recs;
+  void* cands;           uint64_t cands_cap, n_cands;
+} tsg_debug_stage_dump;
+int tsg_debug_engine_stages(const tsg_compiled* c, int device, const uint8_t* arena, uint64_t n_bytes,
+                            const uint64_t* offsets, uint32_t n_files, const uint8_t tail[64],
+                            tsg_debug_stage_dump* out);
 
 /* Thread-local text of the last error. */
 const char* tsg_last_error(void);

@@ -55,7 +55,8 @@ def test_classify_stats_layout(tmp_path):
 
 def test_symbols_exist():
     L = _lib.lib()
-    for name in ("tsg_analyzer_classify_device", "tsg_analyzer_submit_device", "tsg_debug_classify"):
+    for name in ("tsg_analyzer_classify_device", "tsg_analyzer_submit_device", "tsg_debug_classify",
+                 "tsg_debug_engine_stages", "tsg_debug_rule_gate_implied"):
         assert hasattr(L, name), name
     from trivy_amd import analyzer
     for name in ("ClassifyDevice", "AnalyzeDevice", "AnalyzeDeviceAsync"):

@@ -374,6 +374,73 @@ int tsg_debug_sparse_tail(const tsg_global* g, const tsg_batch* b, const void* c
   return 0;
 }
 
+int tsg_debug_engine_stages(const tsg_compiled* c, int device, const uint8_t* arena, uint64_t n_bytes,
+                            const uint64_t* offsets, uint32_t n_files, const uint8_t tail[64],
+                            tsg_debug_stage_dump* out) {
+  if (!c || !offsets || !tail || !out || (n_bytes && !arena)) {
+    tsg::SetError("tsg_debug_engine_stages: NULL argument");
+    return -2;
+  }
+  if (out->struct_size != sizeof(tsg_debug_stage_dump)) {
+    tsg::SetError("tsg_debug_engine_stages: unknown tsg_debug_stage_dump.struct_size");
+    return -2;
+  }
+  if (!WinArgsOk("tsg_debug_engine_stages", offsets, n_files, nullptr)) return -2;
+  if (offsets[n_files] != n_bytes) {
+    tsg::SetError("tsg_debug_engine_stages: offsets must end at n_bytes");
+    return -2;
+  }
+  void *d_arena = nullptr, *d_off = nullptr;
+  hipError_t e = hipSetDevice(device);
+  auto ok = [&](hipError_t r) {
+    if (e == hipSuccess) e = r;
+    return e == hipSuccess;
+  };
+  tsg::StageDump d;
+  std::string run_err;
+  // the arena as the library's callers give it: n_bytes + 64 readable bytes and no more
+  if (ok(e) && ok(hipMalloc(&d_arena, n_bytes + 64)) && ok(hipMalloc(&d_off, (size_t(n_files) + 1) * 8)) &&
+      ok(hipMemcpy(static_cast<uint8_t*>(d_arena) + n_bytes, tail, 64, hipMemcpyHostToDevice)) &&
+      (n_bytes == 0 || ok(hipMemcpy(d_arena, arena, n_bytes, hipMemcpyHostToDevice))) &&
+      ok(hipMemcpy(d_off, offsets, (size_t(n_files) + 1) * 8, hipMemcpyHostToDevice))) {
+    std::unique_ptr<tsg::GpuEngine> eng(new tsg::GpuEngine(c->cr, device));
+    std::vector<tsg::Candidate> cands;
+    if (!eng->ok() || !eng->Run(static_cast<const uint8_t*>(d_arena), n_bytes, static_cast<const uint64_t*>(d_off),
+                                n_files, &cands, nullptr, nullptr, nullptr, &d))
+      run_err = eng->error().empty() ? "engine failed" : eng->error();
+  }
+  for (void* p : {d_arena, d_off})
+    if (p) (void)hipFree(p);
+  if (e != hipSuccess || !run_err.empty()) {
+    tsg::SetError(std::string("tsg_debug_engine_stages: ") + (e != hipSuccess ? hipGetErrorString(e) : run_err.c_str()));
+    return -1;
+  }
+  out->kw_words = d.kw_words;
+  std::memcpy(out->counters, d.counters, sizeof(out->counters));
+  out->caps[0] = d.hit_cap;
+  out->caps[1] = d.rec_cap;
+  out->caps[2] = d.cand_cap;
+  auto put = [](void* dst, uint64_t cap, uint64_t* n, const void* src, size_t count, size_t rec) {
+    *n = count;
+    const size_t k = size_t(std::min<uint64_t>(cap, count));
+    if (dst && k) std::memcpy(dst, src, k * rec);
+  };
+  std::vector<uint64_t> hits(3 * d.hits.size());
+  for (size_t i = 0; i < d.hits.size(); i++) {
+    hits[3 * i] = d.hits[i].file;
+    hits[3 * i + 1] = d.hits[i].end;
+    hits[3 * i + 2] = d.hits[i].aid;
+  }
+  put(out->hits, out->hits_cap, &out->n_hits, hits.data(), d.hits.size(), 24);
+  put(out->kw, out->kw_cap, &out->n_kw, d.kw.data(), d.kw.size(), 4);
+  put(out->flags, out->flags_cap, &out->n_flags, d.flags.data(), d.flags.size(), 4);
+  put(out->nl, out->nl_cap, &out->n_nl, d.nl.data(), d.nl.size(), 2);
+  put(out->chunk_file, out->chunk_file_cap, &out->n_chunk_file, d.chunk_file.data(), d.chunk_file.size(), 4);
+  put(out->recs, out->recs_cap, &out->n_recs, d.recs.data(), d.recs.size(), 4);
+  put(out->cands, out->cands_cap, &out->n_cands, d.cands.data(), d.cands.size(), sizeof(tsg::Candidate));
+  return 0;
+}
+
 int tsg_debug_pool_budget(void) { return tsg::PoolBudget(); }
 
 int tsg_debug_sure_allow(const char* const* patterns, uint32_t n_patterns, const uint8_t* paths, const uint64_t* off,

@@ -12,6 +12,10 @@ struct tsg_scanner {
   std::unique_ptr<tsg::SecretScanner> s;
 };
 
+struct tsg_compiled {  // tsg_debug_compile (tsg_debug.h)
+  tsg::CompiledRules cr;
+};
+
 struct tsg_result {
   tsg::BatchResult files;
   tsg_stats stats;

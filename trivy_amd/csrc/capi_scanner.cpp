@@ -15,10 +15,6 @@
 #include "tsg_debug.h"
 #include "tsg_scanner.h"
 
-struct tsg_compiled {
-  tsg::CompiledRules cr;
-};
-
 namespace {
 // Results are destroyed on a background thread: a batch's findings are
 // thousands of small heap blocks written by the tail's worker threads, and
@@ -653,6 +649,11 @@ int tsg_debug_rule(const tsg_compiled* c, uint32_t i, tsg_debug_rule_info* out) 
   out->kw_ids = c->cr.rule_kw.data() + r.kw_off;
   out->n_kw = r.kw_cnt;
   return 0;
+}
+
+int tsg_debug_rule_gate_implied(const tsg_compiled* c, uint32_t i) {
+  if (i >= c->cr.rules.size()) return -1;
+  return c->cr.rules[i].kw_match_implied ? 1 : 0;
 }
 
 int tsg_debug_anchor(const tsg_compiled* c, uint32_t j, uint32_t* rule, uint32_t* lit_len, int32_t* off_lo,

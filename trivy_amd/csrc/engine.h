@@ -121,6 +121,27 @@ struct BatchStats {
   uint64_t skip_files = 0, skip_bytes = 0, skip_tiles = 0, skip_runs = 0, skip_wave_runs = 0, tiles = 0;
 };
 
+// The intermediate buffers of one synchronous scan (Run's optional `dump`;
+// tsg_debug_engine_stages): copied out after the last kernel
+// of the attempt that did not overflow, before the dropped candidates are
+// erased.  Tests compare each stage with a CPU model; no product path asks
+// for it.
+struct StageHit {
+  uint32_t file, aid;  // anchor id
+  uint64_t end;        // the literal's end, file-relative
+};
+struct StageDump {
+  uint32_t counters[16] = {};
+  uint32_t kw_words = 0, hit_cap = 0, rec_cap = 0, cand_cap = 0;
+  std::vector<StageHit> hits;        // min(counters[0], hit_cap)
+  std::vector<uint32_t> kw;          // n_files x kw_words
+  std::vector<uint32_t> flags;       // n_files
+  std::vector<uint16_t> nl;          // '\n' per 1-KiB chunk, ceil(n_bytes / kChunk)
+  std::vector<uint32_t> recs;        // min(counters[7], rec_cap) flagged 16-B block indices
+  std::vector<uint32_t> chunk_file;  // ceil(n_bytes / kChunk)
+  std::vector<Candidate> cands;      // all counters[1], kCandDrop ones included
+};
+
 // Files whose bytes the result does not need: d_skip[f] != 0
 // for a file whose path is surely allow-listed (pathfilter.h).  The stream K0
 // runs on waits for `ready`; the bytes stay readable until the scan's GPU phase
@@ -145,8 +166,10 @@ class GpuEngine {
   // candidates are copied back into `cands`.
   // With fetch (a device-only batch): the candidate files' bytes are brought
   // back too, sized exactly (the candidates are known before the fetch is issued).
+  // With dump (tests): the scan's intermediate buffers are copied out as well.
   bool Run(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
-           std::vector<Candidate>* cands, BatchStats* st, FetchOut* fetch = nullptr, const SkipIn* skip = nullptr);
+           std::vector<Candidate>* cands, BatchStats* st, FetchOut* fetch = nullptr, const SkipIn* skip = nullptr,
+           StageDump* dump = nullptr);
   // The files want[f] != 0 of a device-resident arena into *out (synchronous;
   // the caller holds the engine's lock).  For the files a GPU pre-transform of
   // resident bytes left as they were read.
@@ -365,6 +388,7 @@ class GpuEngine {
   bool GatherTail(const std::vector<Candidate>& part, uint32_t f0, uint32_t nf, const std::vector<uint64_t>& xoff,
                   const uint64_t* raw_off, const uint8_t* kinds, std::vector<uint64_t>* tail_len, TailOut* tail);
   void DumpItemDiag();
+  bool DumpStages(const WorkSet& W, const uint32_t* cnt, uint64_t n_bytes, uint32_t n_files, StageDump* d);
   std::vector<uint8_t> h_items_kind_;
   std::vector<uint32_t> h_items_id_;
   std::string err_;

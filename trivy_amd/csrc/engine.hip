@@ -835,7 +835,7 @@ constexpr uint32_t kHitAidBits = 24;
 __device__ __forceinline__ uint32_t hit_aid_word(uint32_t aid, uint64_t end) {
   return aid | (uint32_t(end >> 32) << kHitAidBits);
 }
-__device__ __forceinline__ void hit_unpack(const uint32_t* h, uint32_t* f, uint64_t* end, uint32_t* aid) {
+__host__ __device__ __forceinline__ void hit_unpack(const uint32_t* h, uint32_t* f, uint64_t* end, uint32_t* aid) {
   *f = h[0];
   *end = uint64_t(h[1]) | (uint64_t(h[2] >> kHitAidBits) << 32);
   *aid = h[2] & ((1u << kHitAidBits) - 1u);
@@ -2498,7 +2498,8 @@ __global__ __launch_bounds__(256) void finalize_kernel(NfaParams P) {
       const uint64_t fe = P.off[file + 1];
       uint64_t lo = wabs;  // [lo, fe) still unsearched
       found = 0;
-      while (found < 3 && lo < fe && lo - wabs < kNlReach) {
+      // (<=: a '\n' exactly kNlReach away lies in the block a walk from a 16-B aligned wlo reads next)
+      while (found < 3 && lo < fe && lo - wabs <= kNlReach) {
         const uint64_t ck = lo / kChunk;  // wave-uniform
         if (P.nl[ck] == 0) {              // no '\n' in [lo, (ck + 1) * kChunk)
           lo = (ck + 1) * kChunk;
@@ -4429,8 +4430,40 @@ bool GpuEngine::FetchFiles(const uint8_t* d_arena, const uint64_t* d_offsets, ui
   return FetchNow(d_arena, d_offsets, n_files, want, true, out);
 }
 
+// The work set and the single buffers of the scan Run just waited for, copied
+// to the host (StageDump; blocking copies, the scan's stream is idle).
+bool GpuEngine::DumpStages(const WorkSet& W, const uint32_t* cnt, uint64_t n_bytes, uint32_t n_files, StageDump* d) {
+  std::memcpy(d->counters, cnt, sizeof(d->counters));
+  d->kw_words = kw_words_;
+  d->hit_cap = hit_cap_;
+  d->rec_cap = rec_cap_;
+  d->cand_cap = cand_cap_;
+  const uint64_t used = (n_bytes + kChunk - 1) / kChunk;
+  const size_t n_hits = std::min(cnt[0], hit_cap_), n_recs = std::min(cnt[7], rec_cap_);
+  std::vector<uint32_t> raw(3 * n_hits);
+  d->kw.assign(size_t(n_files) * kw_words_, 0);
+  d->flags.assign(n_files, 0);
+  d->nl.assign(used, 0);
+  d->recs.assign(n_recs, 0);
+  d->chunk_file.assign(used, 0);
+  auto get = [&](void* dst, const void* src, size_t bytes) {
+    return bytes == 0 || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+  };
+  if (!get(raw.data(), d_hits_, raw.size() * 4) || !get(d->kw.data(), W.kw, d->kw.size() * 4) ||
+      !get(d->flags.data(), W.flags, d->flags.size() * 4) || !get(d->nl.data(), d_nl_, d->nl.size() * 2) ||
+      !get(d->recs.data(), d_recs_, d->recs.size() * 4) ||
+      !get(d->chunk_file.data(), W.chunk_file, d->chunk_file.size() * 4)) {
+    err_ = "stage dump: device to host copy failed";
+    return false;
+  }
+  d->hits.resize(n_hits);
+  for (size_t i = 0; i < n_hits; i++) hit_unpack(&raw[3 * i], &d->hits[i].file, &d->hits[i].end, &d->hits[i].aid);
+  return true;
+}
+
 bool GpuEngine::Run(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
-                    std::vector<Candidate>* cands, BatchStats* st, FetchOut* fetch, const SkipIn* skip) {
+                    std::vector<Candidate>* cands, BatchStats* st, FetchOut* fetch, const SkipIn* skip,
+                    StageDump* dump) {
   HIP_OK(hipSetDevice(device_));
   cands->clear();
   BatchStats local;
@@ -4510,6 +4543,10 @@ bool GpuEngine::Run(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_
       HIP_OK(hipMemcpyAsync(h_run_cands_, W.cands, nb, hipMemcpyDeviceToHost, stream_));
       HIP_OK(WaitStream());
       std::memcpy(cands->data(), h_run_cands_, nb);
+    }
+    if (dump) {  // the stream is idle: nothing of this scan is in flight
+      dump->cands = *cands;
+      if (!DumpStages(W, cnt, n_bytes, n_files, dump)) return false;
     }
     // closed keyword gates (finalize_kernel) never reach the host
     cands->erase(std::remove_if(cands->begin(), cands->end(), [](const Candidate& c) { return c.flags & kCandDrop; }),

@@ -40,6 +40,23 @@ int tsg_debug_xform(int device, const uint8_t* raw, uint64_t n_bytes, const uint
  * first min(size, 300) bytes. */
 int tsg_debug_classify(int device, const uint8_t* raw, uint64_t n_bytes, const uint64_t* offsets, uint32_t n_files,
                        uint8_t* flags);
+/* The census of the files a transform changes (trivy_amd/csrc/census.hip) on a
+ * host batch, on HIP device `device`.  raw holds n_bytes + 64 bytes: the arena
+ * and its readable tail, uploaded as given into an allocation of exactly that
+ * size (the caller chooses the tail: bytes no file owns, which must not reach a
+ * mark).  kinds per file as tsg_debug_xform's.  mark_out receives one byte per
+ * file: 1 for kind 2 and kind 3, 1 for a kind-1 file that holds a 0x0D, else 0. */
+int tsg_debug_transform_census(int device, const uint8_t* raw, uint64_t n_bytes, const uint64_t* offsets,
+                               uint32_t n_files, const uint8_t* kinds, uint8_t* mark_out);
+/* The gather of files from a resident arena into a packed buffer
+ * (trivy_amd/csrc/census.hip GatherDeviceFiles) on HIP device `device`.  raw
+ * holds n_bytes + 64 bytes as above.  File i is raw[src_off[i] .. src_off[i] +
+ * dst_off[i + 1] - dst_off[i]) and lands at out + dst_off[i]: src_off has
+ * n_files entries in any order, dst_off n_files + 1 ascending ones (dst_off[0]
+ * need not be 0).  out holds dst_off[n_files] + 64 bytes; it is uploaded before
+ * the kernel and read back after it, so every byte no file owns returns as given. */
+int tsg_debug_gather_device(int device, const uint8_t* raw, uint64_t n_bytes, const uint64_t* src_off,
+                            const uint64_t* dst_off, uint32_t n_files, uint8_t* out);
 /* regexp.MatchString: 1 = match, 0 = no match, <0 = compile error. */
 int tsg_regex_match(const char* pattern, const uint8_t* text, uint64_t n);
 

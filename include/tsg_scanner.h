@@ -121,7 +121,9 @@ typedef struct tsg_batch {
    * is kind 0 (valid for host, gathered and resident batches alike).
    * host_arena / host_offsets then hold the bytes as read.  With dev_arena
    * the bytes as read are resident: dev_arena holds them, host_offsets lays
-   * them out as read, and host_arena is NULL or holds the same bytes. */
+   * them out as read, and host_arena is NULL or holds the same bytes; how such
+   * a batch is scanned -- in rewritten chunks, or the unchanged files where they
+   * lie -- is the scanner's tsg_scanner_set_resident_transform mode. */
   const uint8_t* transform;
   /* optional: the FilePath bytes packed in HBM (dev_path_offsets: n_files + 1
    * u64, device) -- the global allow-path rules (scanner.go:381-386) are then
@@ -268,8 +270,11 @@ int tsg_result_fetch_stats(const tsg_result* r, tsg_fetch_stats* out);
  *     findings' lines are read from the resident arena by the GPU findings pass.
  * A field given as 0 means its default.  Windows apply to untransformed
  * device-only batches (host_arena NULL, dev_arena set, no transform); a batch
- * with a transform keeps the files fetch whatever the mode (its transformed
- * bytes are not resident as a whole) and reports mode_used 0.  The options take
+ * with a transform scanned in chunks (TSG_RESIDENT_CHUNKED, the default) keeps
+ * the files fetch whatever the mode (its transformed bytes are not resident as
+ * a whole) and reports mode_used 0; scanned in TSG_RESIDENT_SPLIT mode, the
+ * files its transform leaves as read are an untransformed device-only batch
+ * and take the windows fetch like one (mode_used 1).  The options take
  * effect with the next submitted scan.  TSG_FETCH_MODE=windows at scanner
  * creation sets the initial mode.  Unknown struct_size, mode > 1 and
  * back_bytes in 1..3 are argument errors (<0, with a text). */
@@ -289,7 +294,7 @@ int tsg_scanner_set_fetch_options(tsg_scanner* s, const tsg_fetch_options* opt);
 int tsg_scanner_get_fetch_options(const tsg_scanner* s, tsg_fetch_options* out);
 
 /* What the windows fetch of a scan did.  mode_used: 1 when the batch went the
- * windows route, 0 otherwise (a host arena, a transform, or the mode off) --
+ * windows route, 0 otherwise (a host arena, a transform scanned in chunks, or the mode off) --
  * the other fields are then zero.  granules / runs: the 256-B granules fetched
  * and the contiguous pieces they form; window_bytes = granules * 256;
  * sparse_files: files answered from their pieces; whole_files: files with
@@ -306,6 +311,42 @@ typedef struct tsg_fetch_window_stats {
 } tsg_fetch_window_stats;
 #define TSG_FETCH_WINDOW_STATS_SIZE_V1 ((uint32_t)(offsetof(tsg_fetch_window_stats, ms_fallback) + sizeof(double)))
 int tsg_result_fetch_window_stats(const tsg_result* r, tsg_fetch_window_stats* out);
+
+/* How a resident batch with a transform (dev_arena and transform both set) is scanned.
+ *   TSG_RESIDENT_CHUNKED (the default)  every chunk of the arena is copied into the
+ *     staging ring, rewritten by the pre-transform and scanned, one chunk after the
+ *     other; the candidate files the transform left as read are fetched whole.
+ *   TSG_RESIDENT_SPLIT  a census kernel first marks the files the transform really
+ *     changes (kind 2, kind 3, and kind 1 with a '\r' in it).  The unmarked files are
+ *     scanned where they lie, as an untransformed resident batch that skips the
+ *     marked ones: pipelined, and for a device-only batch with the scanner's fetch
+ *     mode (files or windows).  The marked files of kind 1 and 2 alone are gathered,
+ *     rewritten and scanned as a small second batch.  Results are the same; what
+ *     differs is how many bytes are copied, rewritten and fetched
+ *     (tsg_result_split_stats).
+ * The mode takes effect with the next submitted scan.  TSG_RESIDENT_TRANSFORM=split
+ * at scanner creation sets the initial mode.  Another mode is an argument error (<0,
+ * with a text). */
+#define TSG_RESIDENT_CHUNKED 0u
+#define TSG_RESIDENT_SPLIT 1u
+int tsg_scanner_set_resident_transform(tsg_scanner* s, uint32_t mode);
+int tsg_scanner_get_resident_transform(const tsg_scanner* s, uint32_t* mode);
+
+/* What the split scan did (versioned: the caller sets struct_size, an unknown size
+ * is refused before anything else is read or written).  mode_used: 1 when the batch
+ * took the split, else 0 and every other field 0 (no transform, no dev_arena, an
+ * empty batch, or the mode off).  files / bytes_in_place: the files scanned where
+ * they lie; _changed: the files of the second batch; _dropped: the kind-3 files.
+ * ms_census: the census kernels (HIP events); ms_sub: the second batch's scan, wall
+ * time, beside the in-place scan's kernels (0 when no file changed). */
+typedef struct tsg_split_stats {
+  uint32_t struct_size;
+  uint32_t mode_used;
+  uint64_t files_in_place, bytes_in_place, files_changed, bytes_changed, files_dropped, bytes_dropped;
+  double ms_census, ms_sub;
+} tsg_split_stats;
+#define TSG_SPLIT_STATS_SIZE_V1 ((uint32_t)(offsetof(tsg_split_stats, ms_sub) + sizeof(double)))
+int tsg_result_split_stats(const tsg_result* r, tsg_split_stats* out);
 
 /* Page-lock a caller's host buffer (hipHostRegister) so batches in it stream
  * to the GPU asynchronously (the engine's staging ring: copies of this and of

@@ -26,7 +26,15 @@ and, for the windows mode, the window stats per step (granules, runs, window byt
 fallback files and the fallback's share of the files with candidates, ms_fallback) beside the fetch
 stats of both device-only modes.
 
-Usage: python tools/device_only_bench.py [--gb 4] [--steps 20] [--warmup 5] [--depth 3] [--analyze]
+--analyze --resident split: AnalyzeDevice alone, blocks in chunked mode alternating with blocks in
+split mode (Scanner.set_resident_transform) on one scanner, with the files fetch or, with --fetch
+windows, the windows fetch in force for both.  Printed: ms per step of both modes with every
+block's figure (the claim to check: the split's slowest block is below the chunked mode's fastest),
+the split stats (ms_census against the arena's size among them), the fetch and window stats and
+ms_gpu_total of both.
+
+Usage: python tools/device_only_bench.py [--gb 4] [--steps 20] [--warmup 5] [--depth 3]
+                                         [--analyze [--resident split]]
                                          [--fetch windows [--fwd N] [--fwd-cap N] [--back N]] [--out FILE]
 """
 import argparse
@@ -52,10 +60,14 @@ def main():
     ap.add_argument("--analyze", action="store_true", help="the AnalyzeDevice leg instead of mirrored / device-only")
     ap.add_argument("--fetch", choices=["files", "windows"], default="files",
                     help="windows: the three-mode leg (mirrored / files fetch / windows fetch)")
+    ap.add_argument("--resident", choices=["chunked", "split"], default="chunked",
+                    help="with --analyze; split: chunked and split blocks of AnalyzeDevice interleaved")
     ap.add_argument("--fwd", type=int, default=None)
     ap.add_argument("--fwd-cap", type=int, default=None)
     ap.add_argument("--back", type=int, default=None)
     args = ap.parse_args()
+    if args.analyze and args.resident == "split":
+        return resident_leg(args)
     if args.analyze:
         return analyze_leg(args)
     if args.fetch == "windows":
@@ -310,6 +322,90 @@ def analyze_leg(args):
         "ms_fetch": med([f["ms_fetch"] for f in fetch[True]]),
         "candidates": int(stats[True][-1]["candidates"]), "findings": int(findings[True]),
     }
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+
+
+def resident_leg(args):
+    import torch
+    import trivy_amd.secret as secret
+    from trivy_amd import corpus
+    from trivy_amd.analyzer import SecretAnalyzer
+
+    R = corpus.generate(int(args.gb * 1e9), seed=corpus.SEED, crlf_share=0.05)  # the bytes as read
+    dev = torch.device("cuda", 0)
+    d_arena = torch.from_numpy(R.arena).to(dev)
+    d_offs = torch.from_numpy(R.offsets.view(np.int64)).to(dev)
+    torch.cuda.synchronize()
+    sc = secret.NewScanner(None, device=0, calibration=R.arena[:min(R.n_bytes, 16_000_000)])
+    an = SecretAnalyzer(sc)
+    if args.fetch == "windows":
+        sc.set_fetch_mode("windows", back=args.back, fwd=args.fwd, fwd_cap=args.fwd_cap)
+    modes = ("chunked", "split")
+
+    def block(mode, n):
+        sc.set_resident_transform(mode)  # (in force for the scans submitted from here on)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        inflight, res = [], []
+
+        def take(p):
+            r = p.wait(False)
+            res.append({"stats": r.stats(), "fetch": r.fetch_stats(), "win": r.fetch_window_stats(),
+                        "split": r.split_stats()})
+        for _ in range(n):
+            inflight.append(an.AnalyzeDeviceAsync(d_arena, R.offsets, R.path_ptrs, "/corpus", dev_offsets=d_offs))
+            if len(inflight) >= args.depth:
+                take(inflight.pop(0))
+        while inflight:
+            take(inflight.pop(0))
+        return time.perf_counter() - t0, res
+
+    for mode in modes:
+        block(mode, args.warmup)
+    per = {m: [] for m in modes}
+    res = {m: [] for m in modes}
+    done = 0
+    while done < args.steps:
+        n = min(args.block, args.steps - done)
+        for mode in modes:
+            s, r = block(mode, n)
+            per[mode].append(1e3 * s / n)
+            res[mode] += r
+        done += n
+    sc.set_resident_transform("chunked")
+    findings = {m: res[m][-1]["stats"]["findings"] for m in modes}
+    assert findings["chunked"] == findings["split"], findings
+    assert all(r["split"]["mode_used"] == (m == "split") for m in modes for r in res[m])
+
+    def med(xs):
+        return float(statistics.median(xs))
+
+    def of(m, group, key):
+        return med([r[group][key] for r in res[m]])
+
+    ms_census = of("split", "split", "ms_census")
+    out = {
+        "tool": "device_only_bench --analyze --resident split", "fetch": args.fetch, "gb": R.n_bytes / 1e9,
+        "files": int(R.n_files), "steps": args.steps, "block": args.block, "depth": args.depth,
+        "chunked_ms_per_step": med(per["chunked"]), "split_ms_per_step": med(per["split"]),
+        "chunked_blocks_ms": per["chunked"], "split_blocks_ms": per["split"],
+        "split_slowest_below_chunked_fastest": max(per["split"]) < min(per["chunked"]),
+        "split_stats": {k: of("split", "split", k) for k in res["split"][-1]["split"]},
+        "census_gbps": R.n_bytes / 1e6 / ms_census if ms_census > 0 else 0.0,
+        "findings": int(findings["split"]),
+    }
+    for m in modes:
+        out[m] = {
+            "ms_gpu_total": of(m, "stats", "ms_gpu_total"), "ms_xform_kernel": of(m, "stats", "ms_xform_kernel"),
+            "ms_host_exact": of(m, "stats", "ms_host_exact"), "candidates": int(res[m][-1]["stats"]["candidates"]),
+            "fetch": {k: of(m, "fetch", k) for k in res[m][-1]["fetch"]},
+            "window": {k: of(m, "win", k) for k in res[m][-1]["win"]},
+        }
     line = json.dumps(out)
     print(line)
     if args.out:

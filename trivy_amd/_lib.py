@@ -77,6 +77,49 @@ def regex_match(pattern: str, text: bytes) -> bool:
     return rc == 1
 
 
+GATHER_PIECE = 16384  # csrc/xform.h kGatherPiece
+
+
+def transform_census(raw: bytes, offsets, kinds, tail: bytes = b"", device=0) -> bytes:
+    """tsg_debug_transform_census: one mark byte per file (1: the transform of its kind changes it).
+    offsets: n_files + 1 from 0 to len(raw); tail: up to 64 bytes placed behind the arena (0x00 after)."""
+    L = lib()
+    c = ctypes
+    n_files = len(offsets) - 1
+    if len(kinds) != n_files or len(tail) > 64:
+        raise ValueError("transform_census: one kind per file, a tail of at most 64 bytes")
+    buf = c.create_string_buffer(bytes(raw) + bytes(tail).ljust(64, b"\0"), len(raw) + 64)
+    off = (c.c_uint64 * (n_files + 1))(*[int(x) for x in offsets])
+    kd = (c.c_uint8 * max(1, n_files))(*[int(k) for k in kinds])
+    mark = (c.c_uint8 * max(1, n_files))()
+    L.tsg_debug_transform_census.restype = c.c_int
+    L.tsg_debug_transform_census.argtypes = [c.c_int, c.c_void_p, c.c_uint64, c.c_void_p, c.c_uint32, c.c_void_p,
+                                             c.c_void_p]
+    if L.tsg_debug_transform_census(int(device), buf, len(raw), off, n_files, kd, mark) != 0:
+        raise RuntimeError(last_error(L))
+    return bytes(mark[:n_files])
+
+
+def gather_device(raw: bytes, src_off, dst_off, out: bytes, tail: bytes = b"", device=0) -> bytes:
+    """tsg_debug_gather_device: `out` (dst_off[-1] + 64 bytes) with file i, raw[src_off[i] ..) of length
+    dst_off[i + 1] - dst_off[i], written at dst_off[i]; every other byte of it as given."""
+    L = lib()
+    c = ctypes
+    n_files = len(src_off)
+    if len(dst_off) != n_files + 1 or len(out) != int(dst_off[-1]) + 64 or len(tail) > 64:
+        raise ValueError("gather_device: n + 1 destination offsets, an output of dst_off[-1] + 64 bytes")
+    buf = c.create_string_buffer(bytes(raw) + bytes(tail).ljust(64, b"\0"), len(raw) + 64)
+    so = (c.c_uint64 * max(1, n_files))(*[int(x) for x in src_off])
+    do = (c.c_uint64 * (n_files + 1))(*[int(x) for x in dst_off])
+    ob = c.create_string_buffer(bytes(out), len(out))
+    L.tsg_debug_gather_device.restype = c.c_int
+    L.tsg_debug_gather_device.argtypes = [c.c_int, c.c_void_p, c.c_uint64, c.c_void_p, c.c_void_p, c.c_uint32,
+                                          c.c_void_p]
+    if L.tsg_debug_gather_device(int(device), buf, len(raw), so, do, n_files, ob) != 0:
+        raise RuntimeError(last_error(L))
+    return ob.raw
+
+
 def go_bytes_to_lower(b: bytes) -> bytes:
     out = ctypes.create_string_buffer(len(b) * 3 + 4)
     n = lib().tsg_go_bytes_to_lower(b, len(b), out, len(out))

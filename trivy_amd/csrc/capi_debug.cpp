@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "capi_internal.h"
+#include "census.h"
 #include "classify.h"
 #include "fetch_host.h"
 #include "fetch_windows.h"
@@ -129,6 +130,96 @@ int tsg_debug_classify(int device, const uint8_t* raw, uint64_t n_bytes, const u
   if (s) (void)hipStreamDestroy(s);
   if (e != hipSuccess) {
     tsg::SetError(std::string("tsg_debug_classify: ") + hipGetErrorString(e));
+    return -1;
+  }
+  return 0;
+}
+
+int tsg_debug_transform_census(int device, const uint8_t* raw, uint64_t n_bytes, const uint64_t* offsets,
+                                uint32_t n_files, const uint8_t* kinds, uint8_t* mark_out) {
+  if (!offsets || offsets[0] != 0 || offsets[n_files] != n_bytes) {
+    tsg::SetError("offsets must run from 0 to n_bytes");
+    return -2;
+  }
+  for (uint32_t f = 0; f < n_files; f++)
+    if (offsets[f + 1] < offsets[f]) {
+      tsg::SetError("offsets must ascend");
+      return -2;
+    }
+  void *d_raw = nullptr, *d_off = nullptr, *d_kind = nullptr, *d_mark = nullptr;
+  hipStream_t s = nullptr;
+  hipError_t e = hipSetDevice(device);
+  auto ok = [&](hipError_t r) {
+    if (e == hipSuccess) e = r;
+    return e == hipSuccess;
+  };
+  if (ok(e) && ok(hipStreamCreate(&s)) && ok(hipMalloc(&d_raw, n_bytes + 64)) &&
+      ok(hipMalloc(&d_off, (size_t(n_files) + 1) * 8)) && ok(hipMalloc(&d_kind, size_t(n_files) + 1)) &&
+      ok(hipMalloc(&d_mark, size_t(n_files) + 1)) &&
+      ok(hipMemcpy(d_raw, raw, n_bytes + 64, hipMemcpyHostToDevice)) &&  // (the caller's tail with it)
+      ok(hipMemcpy(d_off, offsets, (size_t(n_files) + 1) * 8, hipMemcpyHostToDevice)) &&
+      ok(hipMemcpy(d_kind, kinds, n_files, hipMemcpyHostToDevice)) &&
+      ok(hipMemset(d_mark, 0xEE, size_t(n_files) + 1)) &&  // (a mark the kernels leave unwritten shows up)
+      ok(tsg::TransformCensus(static_cast<const uint8_t*>(d_raw), n_bytes, static_cast<const uint64_t*>(d_off),
+                              static_cast<const uint8_t*>(d_kind), n_files, static_cast<uint8_t*>(d_mark), s)) &&
+      ok(hipStreamSynchronize(s)))
+    ok(hipMemcpy(mark_out, d_mark, n_files, hipMemcpyDeviceToHost));
+  for (void* p : {d_raw, d_off, d_kind, d_mark})
+    if (p) (void)hipFree(p);
+  if (s) (void)hipStreamDestroy(s);
+  if (e != hipSuccess) {
+    tsg::SetError(std::string("tsg_debug_transform_census: ") + hipGetErrorString(e));
+    return -1;
+  }
+  return 0;
+}
+
+int tsg_debug_gather_device(int device, const uint8_t* raw, uint64_t n_bytes, const uint64_t* src_off,
+                            const uint64_t* dst_off, uint32_t n_files, uint8_t* out) {
+  if (!src_off || !dst_off) {
+    tsg::SetError("tsg_debug_gather_device: offsets missing");
+    return -2;
+  }
+  std::vector<tsg::GatherItem> items;
+  for (uint32_t f = 0; f < n_files; f++) {
+    if (dst_off[f + 1] < dst_off[f]) {
+      tsg::SetError("tsg_debug_gather_device: destination offsets must ascend");
+      return -2;
+    }
+    const uint64_t len = dst_off[f + 1] - dst_off[f];
+    if (src_off[f] > n_bytes || len > n_bytes - src_off[f]) {
+      tsg::SetError("tsg_debug_gather_device: a file leaves the arena");
+      return -2;
+    }
+    for (uint32_t q = 0; uint64_t(q) * tsg::kGatherPiece < len; q++) items.push_back(tsg::GatherItem{f, q});
+  }
+  const uint64_t out_bytes = dst_off[n_files] + 64;
+  const size_t item_bytes = items.size() * sizeof(tsg::GatherItem);
+  void *d_raw = nullptr, *d_src = nullptr, *d_dst = nullptr, *d_items = nullptr, *d_out = nullptr;
+  hipStream_t s = nullptr;
+  hipError_t e = hipSetDevice(device);
+  auto ok = [&](hipError_t r) {
+    if (e == hipSuccess) e = r;
+    return e == hipSuccess;
+  };
+  if (ok(e) && ok(hipStreamCreate(&s)) && ok(hipMalloc(&d_raw, n_bytes + 64)) &&
+      ok(hipMalloc(&d_src, (size_t(n_files) + 1) * 8)) && ok(hipMalloc(&d_dst, (size_t(n_files) + 1) * 8)) &&
+      ok(hipMalloc(&d_items, item_bytes + 8)) && ok(hipMalloc(&d_out, out_bytes)) &&
+      ok(hipMemcpy(d_raw, raw, n_bytes + 64, hipMemcpyHostToDevice)) &&
+      ok(hipMemcpy(d_src, src_off, size_t(n_files) * 8, hipMemcpyHostToDevice)) &&
+      ok(hipMemcpy(d_dst, dst_off, (size_t(n_files) + 1) * 8, hipMemcpyHostToDevice)) &&
+      (items.empty() || ok(hipMemcpy(d_items, items.data(), item_bytes, hipMemcpyHostToDevice))) &&
+      ok(hipMemcpy(d_out, out, out_bytes, hipMemcpyHostToDevice)) &&  // (what no file owns comes back as it was)
+      ok(tsg::GatherDeviceFiles(static_cast<const uint8_t*>(d_raw), static_cast<const uint64_t*>(d_src),
+                                static_cast<const uint64_t*>(d_dst), static_cast<const tsg::GatherItem*>(d_items),
+                                uint32_t(items.size()), static_cast<uint8_t*>(d_out), s)) &&
+      ok(hipStreamSynchronize(s)))
+    ok(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
+  for (void* p : {d_raw, d_src, d_dst, d_items, d_out})
+    if (p) (void)hipFree(p);
+  if (s) (void)hipStreamDestroy(s);
+  if (e != hipSuccess) {
+    tsg::SetError(std::string("tsg_debug_gather_device: ") + hipGetErrorString(e));
     return -1;
   }
   return 0;

@@ -21,6 +21,7 @@ struct tsg_result {
   tsg_stats stats;
   tsg::FetchStats fetch;  // tsg_result_fetch_stats (device-only batches; zero otherwise)
   tsg::FetchWindowStats win;  // tsg_result_fetch_window_stats (the windows fetch; zero otherwise)
+  tsg::SplitStats split;      // tsg_result_split_stats (the split scan of a resident batch with a transform)
   // tsg_debug_result_skip: files marked, their bytes, tiles dropped, runs, most runs per K1 wave, tiles
   uint64_t skip[6] = {0, 0, 0, 0, 0, 0};
   float ms_k0 = 0;  // tsg_debug_result_k0: the K0 phase's own span (BatchStats::ms_k0)

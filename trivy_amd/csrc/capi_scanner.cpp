@@ -263,6 +263,7 @@ struct ExtFields {  // the fields past tsg_batch that a caller's struct_size cov
   // (not a batch field) the scanner's fetch options as they were when the scan was submitted
   int fetch_windows = -1;
   tsg::FetchWinParams fetch_prm;
+  int resident_split = -1;  // (likewise: tsg_scanner_set_resident_transform)
 };
 
 ExtFields ExtOf(const tsg_batch_ext* b) {
@@ -307,6 +308,7 @@ int tsg_scan_submit_ext(tsg_scanner* s, const tsg_batch_ext* b, tsg_pending** ou
   ExtFields x = ExtOf(b);
   if (!CheckBatch(&bc, x)) return -1;
   if (s && s->s) x.fetch_windows = s->s->GetFetchOptions(&x.fetch_prm) ? 1 : 0;  // (a later set is for later scans)
+  if (s && s->s) x.resident_split = s->s->ResidentTransform() == tsg::kResidentSplit ? 1 : 0;
   std::unique_ptr<tsg_pending> p(new tsg_pending());
   tsg_pending* pp = p.get();
   pp->th = std::thread([s, bc, x, pp] {
@@ -364,12 +366,13 @@ int ScanImpl(tsg_scanner* s, const tsg_batch* b, const ExtFields& x, tsg_result*
   in.gather_src = x.gather_src;
   in.fetch_windows = x.fetch_windows;
   in.fetch_prm = x.fetch_prm;
+  in.resident_split = x.resident_split;
   std::unique_ptr<tsg_result> r(new tsg_result());
   r->owner = s->s.get();
   tsg::BatchStats gs;
   tsg::HostStats hs;
   std::string err;
-  if (!s->s->Scan(in, &r->files, &gs, &hs, &err, &r->fetch, &r->win)) {
+  if (!s->s->Scan(in, &r->files, &gs, &hs, &err, &r->fetch, &r->win, &r->split)) {
     tsg::SetError(err);
     return -1;
   }
@@ -788,6 +791,51 @@ int tsg_result_fetch_window_stats(const tsg_result* r, tsg_fetch_window_stats* o
   out->fallback_files = r->win.fallback_files;
   out->fallback_bytes = r->win.fallback_bytes;
   out->ms_fallback = r->win.ms_fallback;
+  return 0;
+}
+
+int tsg_scanner_set_resident_transform(tsg_scanner* s, uint32_t mode) {
+  if (!s || !s->s) {
+    tsg::SetError("tsg_scanner_set_resident_transform: NULL argument");
+    return -1;
+  }
+  if (mode > TSG_RESIDENT_SPLIT) {
+    tsg::SetError("tsg_scanner_set_resident_transform: mode " + std::to_string(mode) +
+                  " (0 = chunked, 1 = split are the modes)");
+    return -1;
+  }
+  s->s->SetResidentTransform(mode);
+  return 0;
+}
+
+int tsg_scanner_get_resident_transform(const tsg_scanner* s, uint32_t* mode) {
+  if (!s || !s->s || !mode) {
+    tsg::SetError("tsg_scanner_get_resident_transform: NULL argument");
+    return -1;
+  }
+  *mode = s->s->ResidentTransform();
+  return 0;
+}
+
+int tsg_result_split_stats(const tsg_result* r, tsg_split_stats* out) {
+  if (!r || !out) {
+    tsg::SetError("tsg_result_split_stats: NULL argument");
+    return -1;
+  }
+  if (out->struct_size != TSG_SPLIT_STATS_SIZE_V1) {
+    tsg::SetError("tsg_result_split_stats: tsg_split_stats.struct_size " + std::to_string(out->struct_size) +
+                  " is not a size this library knows (v1 = " + std::to_string(TSG_SPLIT_STATS_SIZE_V1) + ")");
+    return -1;
+  }
+  out->mode_used = r->split.mode_used;
+  out->files_in_place = r->split.files_in_place;
+  out->bytes_in_place = r->split.bytes_in_place;
+  out->files_changed = r->split.files_changed;
+  out->bytes_changed = r->split.bytes_changed;
+  out->files_dropped = r->split.files_dropped;
+  out->bytes_dropped = r->split.bytes_dropped;
+  out->ms_census = r->split.ms_census;
+  out->ms_sub = r->split.ms_sub;
   return 0;
 }
 

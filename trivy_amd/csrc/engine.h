@@ -150,6 +150,11 @@ struct StageDump {
 struct SkipIn {
   const uint8_t* d_skip = nullptr;
   hipEvent_t ready = nullptr;
+  // The marked files belong to another scan (the split of a resident batch with a
+  // transform): a candidate in one -- its ragged-end tile was
+  // streamed with a neighbour's -- is dropped by the finalize kernel (kCandDrop),
+  // so it reaches neither the fetch nor the host.  Off for the allow-path marks.
+  bool drop_marked = false;
 };
 
 class GpuEngine {
@@ -196,6 +201,9 @@ class GpuEngine {
   // device-mapped host memory (a registered tar layer); each chunk is gathered
   // from there into its staging buffer by a kernel (xform.h GatherHostFiles)
   // instead of one DMA copy -- no host copy of the file bytes.
+  // d_src with gather_src (no gather_base): the files lie scattered in the resident
+  // arena d_src, file f at d_src + gather_src[f]; each chunk is gathered from there
+  // by census.h GatherDeviceFiles (no read leaves the arena and its 64-B tail).
   bool RunHost(const uint8_t* h_arena, uint64_t n_bytes, const uint64_t* h_offsets, uint32_t n_files,
                std::vector<Candidate>* cands, BatchStats* st, const uint8_t* kinds, TailOut* tail,
                std::mutex* dev_mu, std::string* err, const uint8_t* gather_base = nullptr,

@@ -36,6 +36,7 @@
 #include <type_traits>
 
 #include "engine.h"
+#include "census.h"
 #include "fetch.h"
 #include "fetch_host.h"
 #include "fetch_windows.h"
@@ -767,6 +768,7 @@ struct NfaParams {
   uint32_t kw_fold;        // kwfold_kernel ran: with no fold-site overflow the keyword bits are exact in every file
   uint32_t diag;           // TSG_DIAG_VERIFY (timing only): 1 verifies only 1-word NFAs' hits, 2 only the wider ones
   const uint8_t* skip;     // scans with a skip list: per file, 1 = its bytes are not needed (or null)
+  uint32_t drop_marked;    // SkipIn::drop_marked: a candidate of a marked file never reaches the host
 };
 
 // The keyword bits of file f may miss occurrences through U+0130 / U+212A
@@ -2447,6 +2449,8 @@ __global__ __launch_bounds__(256) void finalize_kernel(NfaParams P) {
     uint32_t fl = gate_flags(P, rg, file);
     if (rg.gate == kGateKeywords && !rg.kw_match_implied && !kw_bits_inexact(P, file) && !(fl & kCandGateOpen))
       fl |= kCandDrop;
+    // (a marked file's ragged-end tile was streamed with its neighbour's: another scan owns the file)
+    if (P.drop_marked && P.skip[file]) fl |= kCandDrop;
     // the last three '\n' before wlo: 1 KiB per step, lane 0 on the highest
     // 16-B block; a lane's newlines take ranks after those of the lanes above.
     // A 1-KiB chunk whose K1 count is 0 is skipped whole (long single lines).
@@ -3121,6 +3125,7 @@ struct GpuEngine::HostCall {
   const uint8_t* gather_dev = nullptr;  // device address of the mapped gather_base (RunHost)
   const uint64_t* gather_src = nullptr;
   const uint8_t* d_src = nullptr;  // the bytes as read are resident in HBM (RunHost d_src)
+  bool gather_device = false;      // gather_dev is a resident arena (RunHost d_src + gather_src), not mapped host memory
   bool cancelled = false;  // ring_mu_: a chunk failed; the call's later slots are not copied
   hipEvent_t ev0 = nullptr, ev1 = nullptr;  // first copy issued / last chunk scanned
   bool ev0_recorded = false;
@@ -3203,10 +3208,10 @@ bool GpuEngine::CopyChunk(const StageJob& j, std::string* err) {
     if ((x = hipMemcpyAsync(d_stage_off_[b], h_off_[b], (size_t(nf) + 1) * 8, hipMemcpyHostToDevice, copy_stream_)) !=
             hipSuccess ||
         (x = hipMemcpyAsync(ds, hs, src_bytes + item_bytes, hipMemcpyHostToDevice, copy_stream_)) != hipSuccess ||
-        (x = GatherHostFiles(c.gather_dev, reinterpret_cast<const uint64_t*>(ds),
-                             static_cast<const uint64_t*>(d_stage_off_[b]),
-                             reinterpret_cast<const GatherItem*>(ds + src_bytes), uint32_t(items.size()), d,
-                             copy_stream_)) != hipSuccess ||
+        (x = (c.gather_device ? GatherDeviceFiles : GatherHostFiles)(
+             c.gather_dev, reinterpret_cast<const uint64_t*>(ds), static_cast<const uint64_t*>(d_stage_off_[b]),
+             reinterpret_cast<const GatherItem*>(ds + src_bytes), uint32_t(items.size()), d, copy_stream_)) !=
+            hipSuccess ||
         (x = hipMemsetAsync(d + (e - a), 0, 64, copy_stream_)) != hipSuccess ||
         (c.kinds && (x = hipMemcpyAsync(d_kind_[b], c.kinds + j.f0, nf, hipMemcpyHostToDevice, copy_stream_)) !=
                         hipSuccess) ||
@@ -3296,7 +3301,7 @@ bool GpuEngine::RunHost(const uint8_t* h_arena, uint64_t n_bytes, const uint64_t
   };
   if (kinds && !tail) return set_err("RunHost: a transformed batch needs a tail output");
   if (gather_base && (!gather_src || !kinds)) return set_err("RunHost: a gathered batch needs source offsets and kinds");
-  if (d_src && (!kinds || gather_base)) return set_err("RunHost: a device source needs kinds and no gather");
+  if (d_src && (!kinds || gather_base)) return set_err("RunHost: a device source needs kinds and no host gather");
   if (n_files == 0) return true;
   const uint8_t* gather_dev = nullptr;
   if (gather_base) {  // the device address of the mapped host buffer (tsg_host_register_mapped)
@@ -3320,6 +3325,11 @@ bool GpuEngine::RunHost(const uint8_t* h_arena, uint64_t n_bytes, const uint64_t
   call.gather_dev = gather_dev;
   call.gather_src = gather_src;
   call.d_src = d_src;
+  if (d_src && gather_src) {  // the files lie scattered in the resident arena d_src: gathered by a kernel
+    call.gather_dev = d_src;
+    call.gather_device = true;
+    call.d_src = nullptr;
+  }
   if (hipSetDevice(device_) != hipSuccess || hipEventCreate(&call.ev0) != hipSuccess ||
       hipEventCreate(&call.ev1) != hipSuccess) {
     if (call.ev0) hipEventDestroy(call.ev0);
@@ -4163,6 +4173,7 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
   np.n_fullscan_rules = n_fullscan_rules_;
   np.fs_chunk = fs_chunk_;
   np.skip = skip ? skip->d_skip : nullptr;
+  np.drop_marked = skip && skip->drop_marked ? 1u : 0u;
   np.kw_fold = kw_fold_ ? 1u : 0u;  // no keyword takes 'i' / 'k': the bits are exact without the kernel
 
   if (diag_mode_ == 0) verify_hits_kernel<<<verify_blocks_, 256, 0, stream_>>>(np);

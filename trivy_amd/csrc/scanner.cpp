@@ -1,8 +1,10 @@
 // Exact host tail of the drop-in Scanner (see scanner.h for the line map).
 #include "scanner.h"
 
+#include "census.h"
 #include "fetch_host.h"
 #include "parallel.h"
+#include "split_host.h"
 
 #include <pthread.h>
 #include <algorithm>
@@ -471,12 +473,41 @@ bool Matcher::Match(const uint8_t* s, size_t n) const {
   return re->Match(s, int64_t(n));
 }
 
+// One census pass's stream, events and buffers (census.h; the split scan of a
+// resident batch with a transform).  A scan takes a context from the scanner's
+// pool and gives it back once its GPU phase is over, so the censuses of several
+// scans in flight run side by side, each on its own stream, and none takes the
+// scanner's GPU lock.
+struct CensusCtx {
+  hipStream_t s = nullptr;
+  hipEvent_t e0 = nullptr, ready = nullptr, done = nullptr;
+  void *d_kind = nullptr, *d_mark = nullptr;
+  uint8_t *h_kind = nullptr, *h_mark = nullptr;  // pinned
+  size_t cap_d = 0, cap_h = 0;
+  ~CensusCtx() {
+    if (d_kind) (void)hipFree(d_kind);
+    if (d_mark) (void)hipFree(d_mark);
+    if (h_kind) (void)hipHostFree(h_kind);
+    if (h_mark) (void)hipHostFree(h_mark);
+    for (hipEvent_t e : {e0, ready, done})
+      if (e) (void)hipEventDestroy(e);
+    if (s) (void)hipStreamDestroy(s);
+  }
+};
+struct CensusPool {
+  std::mutex mu;
+  std::vector<std::unique_ptr<CensusCtx>> free;
+};
+void CensusPoolDeleter::operator()(CensusPool* p) const { delete p; }
+
 SecretScanner::SecretScanner(std::vector<RuleSpec> rules, std::vector<AllowRuleSpec> allow,
                              std::vector<std::unique_ptr<Regex>> exclude, int device, std::string* err,
                              const CompileOptions* opt)
     : rules_(std::move(rules)), allow_(std::move(allow)), exclude_(std::move(exclude)) {
   rule_rank_ = RuleRanks(rules_);
   if (const char* fm = std::getenv("TSG_FETCH_MODE")) fetch_windows_ = std::strcmp(fm, "windows") == 0;
+  if (const char* rt = std::getenv("TSG_RESIDENT_TRANSFORM")) resident_split_.store(std::strcmp(rt, "split") == 0);
+  census_.reset(new CensusPool());
   std::vector<RuleSrc> src;
   for (auto& r : rules_) src.push_back({r.id, r.regex_src, r.keywords, r.has_regex});
   for (size_t g = 0; g < exclude_.size(); g++) {
@@ -1573,10 +1604,101 @@ static uint64_t BuildSparse(const HostWindowPlan& P, const std::vector<const uin
                             uint32_t n_files, SparseBatch* sb, std::vector<const uint8_t*>* fdata,
                             std::vector<uint64_t>* flen);
 
+static std::unique_ptr<CensusCtx> TakeCensus(CensusPool* pool) {
+  {
+    std::lock_guard<std::mutex> g(pool->mu);
+    if (!pool->free.empty()) {
+      std::unique_ptr<CensusCtx> c = std::move(pool->free.back());
+      pool->free.pop_back();
+      return c;
+    }
+  }
+  std::unique_ptr<CensusCtx> c(new CensusCtx());
+  if (hipStreamCreateWithFlags(&c->s, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&c->e0) != hipSuccess ||
+      hipEventCreate(&c->ready) != hipSuccess || hipEventCreate(&c->done) != hipSuccess)
+    return nullptr;
+  return c;
+}
+
+static void GiveCensus(CensusPool* pool, std::unique_ptr<CensusCtx> c) {
+  std::lock_guard<std::mutex> g(pool->mu);
+  if (pool->free.size() < 4) pool->free.push_back(std::move(c));  // (else freed here)
+}
+
+// The kinds go up, the census runs, the marks come down to pinned memory, all
+// on the context's stream: `ready` after the kernels (the engine's streams wait
+// for it), `done` after the copy (the host waits for it).
+static bool SubmitCensus(CensusCtx* c, const uint8_t* arena, uint64_t n_bytes, const uint64_t* d_off,
+                         const uint8_t* kinds, uint32_t n, std::string* err) {
+  hipError_t e = hipSuccess;
+  auto ok = [&](hipError_t r) {
+    if (e == hipSuccess) e = r;
+    return e == hipSuccess;
+  };
+  const size_t want = size_t(n) + n / 4 + 256;
+  if (c->cap_d < n) {
+    if (c->d_kind) (void)hipFree(c->d_kind);
+    if (c->d_mark) (void)hipFree(c->d_mark);
+    c->d_kind = c->d_mark = nullptr;
+    c->cap_d = 0;
+    if (ok(hipMalloc(&c->d_kind, want)) && ok(hipMalloc(&c->d_mark, want))) c->cap_d = want;
+  }
+  if (ok(e) && c->cap_h < n) {
+    if (c->h_kind) (void)hipHostFree(c->h_kind);
+    if (c->h_mark) (void)hipHostFree(c->h_mark);
+    c->h_kind = c->h_mark = nullptr;
+    c->cap_h = 0;
+    if (ok(hipHostMalloc(reinterpret_cast<void**>(&c->h_kind), want, hipHostMallocDefault)) &&
+        ok(hipHostMalloc(reinterpret_cast<void**>(&c->h_mark), want, hipHostMallocDefault)))
+      c->cap_h = want;
+  }
+  if (ok(e)) {
+    std::memcpy(c->h_kind, kinds, n);
+    ok(hipMemcpyAsync(c->d_kind, c->h_kind, n, hipMemcpyHostToDevice, c->s)) && ok(hipEventRecord(c->e0, c->s)) &&
+        ok(TransformCensus(arena, n_bytes, d_off, static_cast<const uint8_t*>(c->d_kind), n,
+                           static_cast<uint8_t*>(c->d_mark), c->s)) &&
+        ok(hipEventRecord(c->ready, c->s)) &&
+        ok(hipMemcpyAsync(c->h_mark, c->d_mark, n, hipMemcpyDeviceToHost, c->s)) && ok(hipEventRecord(c->done, c->s));
+  }
+  if (e != hipSuccess) {
+    *err = std::string("split scan: census: ") + hipGetErrorString(e);
+    (void)hipStreamSynchronize(c->s);
+    return false;
+  }
+  return true;
+}
+
+static void AddSubStats(const BatchStats& s, BatchStats* t) {  // the sub-batch's scan into the batch's stats
+  t->hits += s.hits;
+  t->follow_hits += s.follow_hits;
+  t->candidates += s.candidates;
+  t->special_files += s.special_files;
+  t->flagged_blocks += s.flagged_blocks;
+  t->fullscan_tasks += s.fullscan_tasks;
+  t->fold_sites += s.fold_sites;
+  t->hit_overflow = t->hit_overflow || s.hit_overflow;
+  t->cand_overflow = t->cand_overflow || s.cand_overflow;
+  t->ms_scan += s.ms_scan;
+  t->ms_confirm += s.ms_confirm;
+  t->ms_careful += s.ms_careful;
+  t->ms_verify += s.ms_verify;
+  t->ms_fullscan += s.ms_fullscan;
+  t->ms_finalize += s.ms_finalize;
+  t->ms_chunkmap += s.ms_chunkmap;
+  t->ms_k0 += s.ms_k0;
+  t->ms_total += s.ms_total;
+  t->ms_xform = s.ms_xform;
+  t->ms_h2d_span = s.ms_h2d_span;
+  t->h2d_chunks = s.h2d_chunks;
+}
+
 bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst, HostStats* hst, std::string* err,
-                         FetchStats* fst, FetchWindowStats* wst) {
+                         FetchStats* fst, FetchWindowStats* wst, SplitStats* sst) {
   double t0 = NowMs();
   if (fst) *fst = FetchStats();
+  SplitStats slocal;
+  if (!sst) sst = &slocal;
+  *sst = SplitStats();
   FetchWindowStats wlocal;
   if (!wst) wst = &wlocal;
   *wst = FetchWindowStats();
@@ -1645,7 +1767,11 @@ bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst
   const bool dev_only = in.dev_arena && !in.host_arena;
   FetchOut fetch;
   fetch.h_offsets = in.host_offsets;
-  FetchOut* fp = dev_only && !in.transform ? &fetch : nullptr;
+  // A resident batch with a transform, split mode: the files the transform leaves
+  // as they are take the untransformed resident path below, the others a sub-batch of their own.
+  const bool split = in.transform && in.dev_arena && in.n_files && n_bytes &&
+                     (in.resident_split >= 0 ? in.resident_split != 0 : resident_split_.load() != 0);
+  FetchOut* fp = dev_only && (!in.transform || split) ? &fetch : nullptr;
   // the windows fetch (fetch_layout.h): untransformed device-only batches, where the mode is on and the
   // GPU findings pass exists (the sparse files' lines are read from the resident arena)
   if (fp && mat_) {
@@ -1675,7 +1801,65 @@ bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst
     dev_offsets = static_cast<const uint64_t*>(own_off.p);
   }
   GpuEngine::Ticket ticket;
-  if (in.transform && in.dev_arena) {
+  // the split's census: its marks are the in-place scan's skip list (the allow-path marks are not
+  // combined with them: a batch with a transform has no path kernel, as in the chunked path)
+  struct CensusGuard {
+    CensusPool* pool = nullptr;
+    std::unique_ptr<CensusCtx> c;
+    ~CensusGuard() {
+      if (c) GiveCensus(pool, std::move(c));
+    }
+  } census;
+  if (split) {
+    census.pool = census_.get();
+    if (hipSetDevice(engine->device()) == hipSuccess) census.c = TakeCensus(census.pool);
+    if (!census.c) gpu_err = "split scan: census stream / events";
+    if (!census.c || !SubmitCensus(census.c.get(), in.dev_arena, n_bytes, dev_offsets, in.transform, in.n_files,
+                                   &gpu_err)) {
+      census.c.reset();  // (SubmitCensus waited for what it had queued)
+      allow_thread.join();
+      *err = gpu_err;
+      return false;
+    }
+    skip_in.d_skip = static_cast<const uint8_t*>(census.c->d_mark);
+    skip_in.ready = census.c->ready;
+    skip_in.drop_marked = true;
+    skip = &skip_in;
+  }
+  SplitPlan plan;
+  std::vector<Candidate> sub_cands;
+  BatchStats sub_st;
+  bool sub_ok = true;
+  std::string sub_err;
+  // The sub-batch, beside the in-place scan's kernels: the marks on the host, the changed files
+  // gathered from the arena into the staging ring, rewritten and scanned (RunHost takes the GPU
+  // lock per chunk); their transformed bytes come back in `tail`, indexed by sub-batch file.
+  auto run_sub = [&] {
+    const double s0 = NowMs();
+    float ms = 0;
+    if (hipEventSynchronize(census.c->done) != hipSuccess) {
+      sub_err = "split scan: waiting for the census failed";
+      return false;
+    }
+    (void)hipEventElapsedTime(&ms, census.c->e0, census.c->ready);
+    sst->ms_census = ms;
+    if (!PlanSplit(census.c->h_mark, in.transform, in.host_offsets, in.n_files, &plan, &sub_err)) return false;
+    sst->mode_used = 1;
+    sst->files_in_place = plan.files_in_place;
+    sst->bytes_in_place = plan.bytes_in_place;
+    sst->files_changed = plan.files_changed;
+    sst->bytes_changed = plan.bytes_changed;
+    sst->files_dropped = plan.files_dropped;
+    sst->bytes_dropped = plan.bytes_dropped;
+    if (plan.ids.empty()) return true;  // no file changes: no second scan
+    if (!engine->RunHost(nullptr, plan.off.back(), plan.off.data(), uint32_t(plan.ids.size()), &sub_cands, &sub_st,
+                         plan.kinds.data(), &tail, &gpu_mu_[slot], &sub_err, nullptr, plan.src.data(), in.dev_arena))
+      return false;
+    if (!RemapSubCandidates(plan, tail.raw, &sub_cands, &sub_err)) return false;
+    sst->ms_sub = NowMs() - s0;
+    return true;
+  };
+  if (in.transform && in.dev_arena && !split) {
     // resident bytes as read: RunHost's chunk pipeline with a device source; the transformed
     // candidate files come back in `tail`, the ones the transform left alone through the fetch
     ok = engine->RunHost(nullptr, n_bytes, in.host_offsets, in.n_files, &cands, gst, in.transform, &tail,
@@ -1704,6 +1888,7 @@ bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst
       ok = engine->Run(in.dev_arena, n_bytes, dev_offsets, in.n_files, &cands, gst, fp, skip);
     if (!ok && gpu_err.empty()) gpu_err = engine->error();
   }
+  if (split && ok) sub_ok = run_sub();
   if (ticket.slot >= 0) {
     bool rerun = false;
     ok = engine->Collect(&ticket, &cands, gst, &rerun, &gpu_err, fp);
@@ -1711,6 +1896,16 @@ bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst
       std::lock_guard<std::mutex> g(gpu_mu_[slot]);
       ok = engine->Run(in.dev_arena, n_bytes, dev_offsets, in.n_files, &cands, gst, fp, skip);
       if (!ok) gpu_err = engine->error();  // read under the engine's lock
+    }
+  }
+  if (split) {
+    if (ok && !sub_ok) {
+      ok = false;
+      gpu_err = sub_err;
+    }
+    if (!ok) {  // nothing may still read the marks when the context goes back
+      (void)hipStreamSynchronize(engine->stream());
+      (void)hipStreamSynchronize(census.c->s);
     }
   }
   allow_thread.join();
@@ -1731,7 +1926,8 @@ bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst
   uint64_t n_touched = 0;
   uint32_t fallback_rounds = 0;
   double fallback_ms = 0;
-  if (in.transform) {  // gathered files from tail.buf, identity-transformed ones in place
+  std::vector<uint8_t> host_only;
+  if (in.transform && !split) {  // gathered files from tail.buf, identity-transformed ones in place
     fdata.assign(in.n_files, nullptr);
     flen.assign(in.n_files, 0);
     for (const Candidate& c : cands) {
@@ -1794,6 +1990,38 @@ bool SecretScanner::Scan(const BatchInput& in, BatchResult* out, BatchStats* gst
     tin.file_data = fdata.data();
     tin.file_len = flen.data();
     tin.file_data_is_arena = true;
+  } else if (split) {  // a mirrored batch: the in-place files where the host arena holds them
+    fdata.assign(in.n_files, nullptr);
+    flen.assign(in.n_files, 0);
+    for (uint32_t f = 0; f < in.n_files; f++) {
+      fdata[f] = in.host_arena + in.host_offsets[f];
+      flen[f] = in.host_offsets[f + 1] - in.host_offsets[f];
+    }
+    tin.file_data = fdata.data();
+    tin.file_len = flen.data();
+    tin.file_data_is_arena = true;
+  }
+  if (split) {
+    // Both scans' candidates.  The changed files are read from the sub-batch's tail and their
+    // findings made by the host: the resident arena holds their bytes as read, not as transformed,
+    // so neither the GPU findings pass nor the sparse views may serve them.
+    if (const size_t stray = DropMarkedCandidates(census.c->h_mark, in.n_files, &cands)) {
+      *err = "split scan: " + std::to_string(stray) + " in-place candidates in marked files";
+      return false;
+    }
+    if (sparse.sparse.size() == in.n_files)  // (a window of a neighbour may have touched a changed file)
+      for (uint32_t f : plan.ids) n_touched -= (sparse.sparse[f] || (fdata[f] && flen[f])) ? 1 : 0;
+    host_only.assign(in.n_files, 0);
+    MergeChanged(plan, tail.buf.data(), tail.off, &fdata, &flen, &host_only,
+                 sparse.sparse.size() == in.n_files ? &sparse.sparse : nullptr);
+    tin.host_only = host_only.data();
+    cands.insert(cands.end(), sub_cands.begin(), sub_cands.end());
+    if (gst) {
+      AddSubStats(sub_st, gst);
+      gst->bytes = n_bytes;
+      gst->files = in.n_files;
+    }
+    GiveCensus(census.pool, std::move(census.c));  // the GPU phase is over: the marks may go
   }
   if (fst) {
     fst->rounds = fetch.rounds;
@@ -2192,7 +2420,7 @@ bool SecretScanner::HostTail(const BatchInput& in, std::vector<Candidate>* cands
         return;
       }
     }
-    if (!gpu_mat) {
+    if (!gpu_mat || (in.host_only && in.host_only[f])) {
       ScanFile(data, len, std::string_view(p, pn), bin, t_group.data(), t_group.size(), &tmp[k], gpu_windows);
       return;
     }
@@ -2253,7 +2481,9 @@ bool SecretScanner::HostTail(const BatchInput& in, std::vector<Candidate>* cands
     }
     if (in.window_stats) {
       uint64_t n_whole = 0;  // files with candidates whose bytes all came back with the windows
-      for (size_t k = 0; k < nf; k++) n_whole += !SB->sparse[group_file(k)] && !allowed[group_file(k)];
+      for (size_t k = 0; k < nf; k++)
+        n_whole += !SB->sparse[group_file(k)] && !allowed[group_file(k)] &&
+                   !(in.host_only && in.host_only[group_file(k)]);
       in.window_stats->whole_files = n_whole;
       in.window_stats->sparse_files = n_sparse.load();
       in.window_stats->fallback_files = again.size();

@@ -277,6 +277,9 @@ struct BatchInput {
   // file_data holds the bytes of dev_arena (a device-only batch's fetched files): the GPU findings
   // pass may read the resident arena for them
   bool file_data_is_arena = false;
+  // optional, per file (with file_data): file_data[f] does not hold the arena's bytes (a changed file of the
+  // split scan: its transformed bytes), so the host makes its findings whatever file_data_is_arena says
+  const uint8_t* host_only = nullptr;
   const uint8_t* dev_paths = nullptr;   // optional: the paths packed in HBM (the allow-path prefilter runs
   const uint64_t* dev_path_off = nullptr;  // on the GPU, pathfilter.h); n_files + 1 offsets, device
   const uint8_t* host_paths = nullptr;      // optional: the paths packed in host memory (copied to HBM for
@@ -291,6 +294,9 @@ struct BatchInput {
   // the fetch options this scan was submitted under (-1: the scanner's, as Scan finds them)
   int fetch_windows = -1;
   FetchWinParams fetch_prm;
+  // how a resident batch with a transform is scanned, as it was when the scan was submitted
+  // (-1: the scanner's mode, as Scan finds it; 0 chunked, 1 split)
+  int resident_split = -1;
 };
 
 struct HostStats {
@@ -303,6 +309,22 @@ struct FetchStats {
   uint32_t rounds = 0;
   uint64_t files = 0, bytes = 0, direct_files = 0;
   double ms_fetch = 0;
+};
+
+// What the split scan of a resident batch with a transform did (tsg_split_stats).
+// All zero for a batch that did not take the split.
+struct SplitStats {
+  uint32_t mode_used = 0;
+  uint64_t files_in_place = 0, bytes_in_place = 0, files_changed = 0, bytes_changed = 0, files_dropped = 0,
+           bytes_dropped = 0;
+  double ms_census = 0;  // the census kernels (HIP events)
+  double ms_sub = 0;     // the sub-batch's scan, wall time
+};
+constexpr uint32_t kResidentChunked = 0, kResidentSplit = 1;
+
+struct CensusPool;  // scanner.cpp: the census passes' streams, events and buffers
+struct CensusPoolDeleter {
+  void operator()(CensusPool* p) const;
 };
 
 class SecretScanner {
@@ -323,7 +345,14 @@ class SecretScanner {
 
   // Thread-safe: concurrent scans report failures through *err only (no shared state).
   bool Scan(const BatchInput& in, BatchResult* out, BatchStats* gst, HostStats* hst, std::string* err,
-            FetchStats* fst = nullptr, FetchWindowStats* wst = nullptr);
+            FetchStats* fst = nullptr, FetchWindowStats* wst = nullptr, SplitStats* sst = nullptr);
+  // How a resident batch with a transform (dev_arena + transform) is scanned: kResidentChunked, every
+  // chunk copied and rewritten (RunHost with a device source), or kResidentSplit, the files the
+  // transform leaves as they are scanned where they lie and only the others rewritten (DESIGN.md
+  // §4.12).  Takes effect with the next scan submitted.  TSG_RESIDENT_TRANSFORM=split at creation
+  // sets the initial mode.
+  void SetResidentTransform(uint32_t mode) { resident_split_.store(mode == kResidentSplit ? 1 : 0); }
+  uint32_t ResidentTransform() const { return resident_split_.load() ? kResidentSplit : kResidentChunked; }
   // How device-only batches' bytes come back (tsg_fetch_options): windows != 0 the windows fetch
   // (fetch_layout.h); takes effect with the next scan submitted.  TSG_FETCH_MODE=windows at
   // creation sets the initial mode.
@@ -452,6 +481,8 @@ class SecretScanner {
   mutable std::mutex fetch_opt_mu_;
   bool fetch_windows_ = false;
   FetchWinParams fetch_prm_;
+  std::atomic<int> resident_split_{0};
+  std::unique_ptr<CensusPool, CensusPoolDeleter> census_;
 
  public:
   // 1 / 0 / 2: GPU / host / auto (GPU while host-bound) findings for HBM-resident

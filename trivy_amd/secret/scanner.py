@@ -102,6 +102,15 @@ class _CFetchWindowStats(c.Structure):  # tsg_fetch_window_stats (versioned: str
                                           "fallback_files", "fallback_bytes")] + [("ms_fallback", c.c_double)]
 
 
+class _CSplitStats(c.Structure):  # tsg_split_stats (versioned: struct_size first)
+    _fields_ = [("struct_size", c.c_uint32), ("mode_used", c.c_uint32)] + \
+               [(n, c.c_uint64) for n in ("files_in_place", "bytes_in_place", "files_changed", "bytes_changed",
+                                          "files_dropped", "bytes_dropped")] + \
+               [("ms_census", c.c_double), ("ms_sub", c.c_double)]
+
+
+SPLIT_STATS_SIZE_V1 = c.sizeof(_CSplitStats)                # TSG_SPLIT_STATS_SIZE_V1
+RESIDENT_MODES = ("chunked", "split")                       # TSG_RESIDENT_CHUNKED, TSG_RESIDENT_SPLIT
 FETCH_OPTIONS_SIZE_V1 = c.sizeof(_CFetchOptions)            # TSG_FETCH_OPTIONS_SIZE_V1
 FETCH_WINDOW_STATS_SIZE_V1 = c.sizeof(_CFetchWindowStats)   # TSG_FETCH_WINDOW_STATS_SIZE_V1
 FETCH_MODES = ("files", "windows")                          # TSG_FETCH_FILES, TSG_FETCH_WINDOWS
@@ -137,6 +146,10 @@ def _declare(L):
         L.tsg_scanner_set_fetch_options.argtypes = [c.c_void_p, c.POINTER(_CFetchOptions)]
         L.tsg_scanner_get_fetch_options.argtypes = [c.c_void_p, c.POINTER(_CFetchOptions)]
         L.tsg_result_fetch_window_stats.argtypes = [c.c_void_p, c.POINTER(_CFetchWindowStats)]
+    if hasattr(L, "tsg_scanner_set_resident_transform"):
+        L.tsg_scanner_set_resident_transform.argtypes = [c.c_void_p, c.c_uint32]
+        L.tsg_scanner_get_resident_transform.argtypes = [c.c_void_p, c.POINTER(c.c_uint32)]
+        L.tsg_result_split_stats.argtypes = [c.c_void_p, c.POINTER(_CSplitStats)]
     if hasattr(L, "tsg_result_records"):
         L.tsg_result_records.argtypes = [c.c_void_p, c.c_void_p, c.c_uint64]
         L.tsg_result_records.restype = c.c_uint64
@@ -497,6 +510,24 @@ class Scanner:
         return {"mode": FETCH_MODES[o.mode], "back": o.back_bytes, "fwd": o.fwd_bytes, "fwd_cap": o.fwd_cap,
                 "max_span": o.max_span}
 
+    def set_resident_transform(self, mode):
+        """How a resident batch with a transform (scan_device with `transform`, SecretAnalyzer.AnalyzeDevice)
+        is scanned (tsg_scanner_set_resident_transform): "chunked" (the default: every chunk copied,
+        rewritten and scanned) or "split" (the files the transform leaves as read are scanned where
+        they lie, only the others rewritten).  Takes effect with the next scan submitted; results
+        never depend on it (ScanResult.split_stats() says what it did)."""
+        if mode not in RESIDENT_MODES:
+            raise ValueError("set_resident_transform: mode must be one of %s" % (RESIDENT_MODES,))
+        if self._L.tsg_scanner_set_resident_transform(self._h, RESIDENT_MODES.index(mode)) != 0:
+            raise ValueError("tsg_scanner_set_resident_transform failed: %s" % _lib.last_error(self._L))
+
+    def resident_transform(self):
+        """The mode in force: "chunked" or "split"."""
+        m = c.c_uint32()
+        if self._L.tsg_scanner_get_resident_transform(self._h, c.byref(m)) != 0:
+            raise RuntimeError("tsg_scanner_get_resident_transform failed: %s" % _lib.last_error(self._L))
+        return RESIDENT_MODES[m.value]
+
     def set_gpu_findings(self, mode) -> int:
         """Findings of HBM-resident batches on the GPU (materialize.h; True / 1), on the host
         (False / 0, the default) or on the GPU while the exact pass is the bound (2)
@@ -577,6 +608,16 @@ class ScanResult:
         s.struct_size = FETCH_WINDOW_STATS_SIZE_V1
         if self._sc._L.tsg_result_fetch_window_stats(self._h, c.byref(s)) != 0:
             raise RuntimeError("tsg_result_fetch_window_stats failed: %s" % _lib.last_error(self._sc._L))
+        return {k: getattr(s, k) for k, _ in s._fields_ if k != "struct_size"}
+
+    def split_stats(self):
+        """What the split scan of a resident batch with a transform did (tsg_result_split_stats):
+        mode_used (0: the batch did not take the split, and the rest is zero), files_in_place,
+        bytes_in_place, files_changed, bytes_changed, files_dropped, bytes_dropped, ms_census, ms_sub."""
+        s = _CSplitStats()
+        s.struct_size = SPLIT_STATS_SIZE_V1
+        if self._sc._L.tsg_result_split_stats(self._h, c.byref(s)) != 0:
+            raise RuntimeError("tsg_result_split_stats failed: %s" % _lib.last_error(self._sc._L))
         return {k: getattr(s, k) for k, _ in s._fields_ if k != "struct_size"}
 
     def skip_stats(self):

@@ -102,6 +102,10 @@ int tsg_debug_filter(const tsg_compiled* c, uint32_t* shape, const uint32_t** re
                      const uint32_t** classes, double* est_fp);
 /* The anchor / fold ids of the prefilter items (items[k] owns ids[ids_off .. ids_off + n_ids)). */
 int tsg_debug_filter_ids(const tsg_compiled* c, const uint32_t** ids, uint32_t* n);
+/* The confirm step's core tables (trivy_amd/csrc/filter.h): out = {core groups (8 items each), distinct
+ * byte columns over all groups (the byte classes the confirm kernel's LDS copy is compressed to: groups x
+ * classes x 8 B), the most groups one bucket holds (lookups per fire), slots of the literal-window hash}. */
+int tsg_debug_filter_core(const tsg_compiled* c, uint32_t out[4]);
 /* Rule i's anchor summary: "[off_lo,off_hi] lit[*][+la] ..." or "-" (no anchor). */
 const char* tsg_debug_rule_anchor(const tsg_compiled* c, uint32_t i);
 

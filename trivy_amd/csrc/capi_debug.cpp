@@ -13,6 +13,7 @@
 #include "classify.h"
 #include "fetch_host.h"
 #include "fetch_windows.h"
+#include "filter.h"
 #include "goregex.h"
 #include "parallel.h"
 #include "xform.h"
@@ -533,6 +534,25 @@ int tsg_debug_engine_stages(const tsg_compiled* c, int device, const uint8_t* ar
 }
 
 int tsg_debug_pool_budget(void) { return tsg::PoolBudget(); }
+
+int tsg_debug_filter_core(const tsg_compiled* c, uint32_t out[4]) {
+  const auto* f = c->cr.filter.get();
+  if (!f) return -1;
+  const uint32_t n_groups = uint32_t(f->core.size() / 256);
+  std::vector<std::vector<uint64_t>> cols;  // distinct byte columns of the core tables
+  for (uint32_t b = 0; b < 256; b++) {
+    std::vector<uint64_t> col(n_groups);
+    for (uint32_t g = 0; g < n_groups; g++) col[g] = f->core[size_t(g) * 256 + b];
+    if (std::find(cols.begin(), cols.end(), col) == cols.end()) cols.push_back(std::move(col));
+  }
+  uint32_t most = 0;
+  for (uint32_t b = 0; b + 1 < f->bucket_groups.size(); b++) most = std::max(most, f->bucket_groups[b + 1] - f->bucket_groups[b]);
+  out[0] = n_groups;
+  out[1] = uint32_t(cols.size());
+  out[2] = most;
+  out[3] = uint32_t(f->hash_keys.size());
+  return 0;
+}
 
 int tsg_debug_sure_allow(const char* const* patterns, uint32_t n_patterns, const uint8_t* paths, const uint64_t* off,
                          uint32_t n_paths, uint8_t* sure, uint8_t* has_form) {

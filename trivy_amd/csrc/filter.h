@@ -4,7 +4,8 @@
 // Each item is reduced to a window of at most `window` consecutive byte sets
 // (the least frequent one under a static byte-frequency prior); windows are
 // clustered into the item buckets (agglomerative, minimising the estimated
-// false-positive rate Σ_bucket Π_slot P(union of the slot's sets)).
+// false-positive rate Σ_bucket Π_slot P(union of the slot's sets)).  With a
+// calibration sample both choices are made by the fires measured on it instead.
 //
 // State layout: n_words u32 registers of 8 slots x 4 buckets; bucket j lives
 // in register j / 4, slot s at bit 4*s + j % 4.  Per input byte b
@@ -86,9 +87,13 @@ TSG_HOST_DEVICE inline uint32_t WindowHash(uint64_t key, uint32_t bits) {
 // Static byte-frequency prior of source/text bytes (sums to 1).
 const std::vector<double>& BytePrior();
 
-// prior: byte frequencies to use instead of BytePrior() (a calibration sample's, CompileOptions)
+// prior: byte frequencies to use instead of BytePrior() (a calibration sample's, CompileOptions).
+// sample: calibration bytes (CompileOptions).  With one, and at most 256 unique items, the windows and
+// the buckets are chosen by the fires measured on a prefix of it instead of the prior's
+// estimate; without one the tables are the prior's.
 bool BuildFilter(const std::vector<FilterItem>& items, uint32_t window, uint32_t n_buckets, FilterTables* out,
-                 std::string* err, const std::vector<double>* prior = nullptr);
+                 std::string* err, const std::vector<double>* prior = nullptr, const uint8_t* sample = nullptr,
+                 uint64_t sample_n = 0);
 
 // The window BuildFilter keeps of an item: its least likely `window` (or fewer)
 // consecutive positions under the prior, [*start, *start + *len).

@@ -1442,7 +1442,14 @@ bool CompileRules(const std::vector<RuleSrc>& src, CompiledRules* out, std::stri
     uint32_t nb = 16, nw = FilterWindow();
     if (const char* e = std::getenv("TSG_FILTER_BUCKETS")) nb = uint32_t(std::atoi(e));
     auto ft = std::make_shared<FilterTables>();
-    if (!BuildFilter(out->items, nw, nb, ft.get(), err, cal_prior_p)) return false;
+    // the sample also drives the windows and the buckets (filter.h), unless its byte
+    // frequencies stand in for the prior (TSG_CALIB_PRIOR) or TSG_CALIB_BUCKETS=0
+    // (A/B: the static prior's clustering with the calibrated anchor choice)
+    const char* cb_env = std::getenv("TSG_CALIB_BUCKETS");
+    const bool by_sample = opt && opt->calib && opt->calib_n && !cal_prior_p && !(cb_env && std::atoi(cb_env) == 0);
+    if (!BuildFilter(out->items, nw, nb, ft.get(), err, cal_prior_p, by_sample ? opt->calib : nullptr,
+                     by_sample ? opt->calib_n : 0))
+      return false;
     out->filter = ft;
   }
   return true;

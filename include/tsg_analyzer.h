@@ -185,6 +185,83 @@ int tsg_analyzer_classify_device(tsg_analyzer* a, const tsg_device_files* f, uin
  * kind is not 2. */
 int tsg_analyzer_submit_device(tsg_analyzer* a, const tsg_device_files* f, tsg_pending** out);
 
+/* An uncompressed tar layer whose bytes exist only in HBM.  Where
+ * the files are is written in the 512-B headers inside the bytes: one streaming
+ * GPU pass (trivy_amd/csrc/tarindex.hip) collects every block that parses as a
+ * header -- the checksum test of the host walk -- and only those come to the
+ * host, which follows the header chain over them by the rules of
+ * tsg_collector_add_tar (PAX path / size, GNU long names, ustar prefix,
+ * path.Clean, whiteouts, opaque dirs, Required).  File data that looks like a
+ * header (a tar inside the layer) is never on the chain and never visited.
+ * Contract: dev_tar is 16-B aligned; 64 readable bytes follow dev_tar + n_bytes
+ * (the dev_arena contract: only the scan kernels use it, the index pass reads
+ * complete 512-B blocks below n_bytes alone); the layer stays valid and
+ * unchanged until the index is freed and every pending made from it is waited
+ * for.  Versioned like tsg_device_files. */
+typedef struct tsg_device_tar {
+  uint32_t struct_size, reserved;
+  const void* dev_tar;
+  uint64_t n_bytes;
+} tsg_device_tar;
+#define TSG_DEVICE_TAR_SIZE_V1 ((uint32_t)(offsetof(tsg_device_tar, n_bytes) + sizeof(uint64_t)))
+
+/* tar: entries, regular, required, whiteouts, opaque_dirs as the host walk counts
+ * them (added, skipped_binary and input_bytes are 0: the index does not read file
+ * contents).  blocks: complete 512-B blocks read; candidates: blocks that parse
+ * as a header; off_chain: candidates the chain never visited; block_fetches:
+ * chain blocks that were no candidate (the end-of-archive block, a corrupted
+ * header), each copied from the device on its own; ext_bytes: bytes of PAX
+ * records and GNU long names copied from the device; kernel_runs: 2 when the
+ * record buffer (n_bytes / 4096 + 1024 records at first) was too small and the
+ * pass ran again with room for the count.  ms_kernel: the kernel run(s), HIP
+ * events; ms_total: the whole call. */
+typedef struct tsg_device_tar_stats {
+  uint32_t struct_size, reserved;
+  tsg_tar_stats tar;
+  uint64_t blocks, candidates, off_chain, block_fetches, ext_bytes, kernel_runs;
+  double ms_kernel, ms_total;
+} tsg_device_tar_stats;
+#define TSG_DEVICE_TAR_STATS_SIZE_V1 ((uint32_t)(offsetof(tsg_device_tar_stats, ms_total) + sizeof(double)))
+
+typedef struct tsg_tar_index tsg_tar_index;
+/* The index of a resident layer: its Required-accepted regular files in walk
+ * order.  st is optional.  Argument errors -- unknown struct_size (of t or st),
+ * NULL analyzer, t, out or dev_tar, dev_tar not 16-B aligned, n_bytes / 512 >=
+ * 2^32 -- return -1 before any GPU work; -2: no GPU engine, or a HIP error (also
+ * one in a copy the walk asked for); a malformed archive returns -3 with the host
+ * walk's message.  The record buffers of the pass (about 13 % of the layer's size
+ * in HBM and as much page-locked host memory, while the call runs) are freed before
+ * it returns when they exceed 16 MiB.  The pass runs on
+ * a stream of its own and does not take the scanner's GPU lock. */
+int tsg_analyzer_index_device_tar(tsg_analyzer* a, const tsg_device_tar* t, tsg_tar_index** out,
+                                  tsg_device_tar_stats* st);
+uint32_t tsg_tar_index_files(const tsg_tar_index* ix);
+/* File i: its cleaned path (no "/" prefix; NUL-terminated, owned by the index),
+ * where its content lies in the layer, and its size.  -1: i out of range. */
+int tsg_tar_index_file(const tsg_tar_index* ix, uint32_t i, const char** path, uint64_t* path_len,
+                       uint64_t* data_off, uint64_t* size);
+/* Every file's layout at once (tsg_tar_index_files values each; any may be NULL):
+ * start, the 512-B boundary where the entry's header chain begins (its PAX / GNU
+ * long-name headers lie there, before its own header) -- where a batch that begins
+ * with this file has its arena; data_off and size as tsg_tar_index_file gives them. */
+int tsg_tar_index_spans(const tsg_tar_index* ix, uint64_t* start, uint64_t* data_off, uint64_t* size);
+/* Files [first, first + count) as one device-only batch with no copy: the layer
+ * itself is the arena, from the 512-B boundary where file `first`'s header chain
+ * starts.  The batch has 2 count + 1 pseudo-files, gap, file, gap, ..., file,
+ * gap: a gap is what lies between two files (headers, padding, every entry
+ * Required refused), has an empty path and is dropped where it lies (transform
+ * kind 3).  IsBinary runs on the GPU over the files' heads, then the batch is
+ * scanned as tsg_analyzer_submit_device scans its own: a binary .pyc is kind 2,
+ * any other binary is dropped.  The scanner's fetch mode and resident-transform
+ * mode apply unchanged.
+ * Result indexing: result file 2 j + 1 is index file first + j; the even results
+ * are the gaps, kind 0.  first + count beyond tsg_tar_index_files is refused (-1)
+ * before any GPU work.  The library owns what it built until tsg_scan_wait;
+ * several submits may be in flight. */
+int tsg_analyzer_submit_device_tar(tsg_analyzer* a, const tsg_tar_index* ix, uint32_t first, uint32_t count,
+                                   tsg_pending** out);
+void tsg_tar_index_free(tsg_tar_index* ix);
+
 #ifdef __cplusplus
 }
 #endif

@@ -248,6 +248,38 @@ int tsg_debug_engine_stages(const tsg_compiled* c, int device, const uint8_t* ar
                             const uint64_t* offsets, uint32_t n_files, const uint8_t tail[64],
                             tsg_debug_stage_dump* out);
 
+/* ---- layers resident in HBM (trivy_amd/csrc/tarindex.hip, tar_index_host.h) ----
+ * tar_headers_kernel alone on HIP device `device`: dev_tar and records_out are
+ * DEVICE pointers, both 16-B aligned (the caller's buffers: records_out holds
+ * `capacity` 528-B records -- u64 block index, 8 B of padding, the 512 header
+ * bytes -- and whatever guard the caller puts after them).  Blocks b < n_bytes /
+ * 512 are read.  *count_out: the candidates found, which may exceed capacity;
+ * records [0, min(count, capacity)) are written, in no particular order.
+ * grid_cap != 0 caps the grid at that many workgroups.  ms_out (optional): the
+ * kernel's time from HIP events. */
+int tsg_debug_tar_headers(int device, const void* dev_tar, uint64_t n_bytes, uint64_t capacity, uint32_t grid_cap,
+                          void* records_out, uint64_t* count_out, double* ms_out);
+/* The record capacity tsg_analyzer_index_device_tar starts with (process-wide;
+ * 0 = the default, n_bytes / 4096 + 1024): a small one forces the second run. */
+void tsg_debug_set_tar_capacity(uint64_t records);
+struct tsg_analyzer;
+struct tsg_tar_index;
+struct tsg_device_tar_stats;
+/* The host half of tsg_analyzer_index_device_tar without a GPU: the candidate
+ * records are given (n_records 528-B records, any order) instead of computed,
+ * and `host_tar` (n_bytes) stands in for the device where the walk copies a
+ * block or a range of the layer.  The index (not submittable: it has no device
+ * layer) and the stats come back as from the real call; kernel_runs is 0. */
+int tsg_debug_index_tar_records(struct tsg_analyzer* a, const uint8_t* host_tar, uint64_t n_bytes,
+                                const void* records, uint64_t n_records, struct tsg_tar_index** out,
+                                struct tsg_device_tar_stats* st);
+/* What tsg_analyzer_submit_device_tar builds for files [first, first + count) of
+ * an index, from given IsBinary flags (one per pseudo-file, 2 count + 1): *base,
+ * the layer offset of the batch's arena; offs, 2 count + 2 offsets from 0; kinds
+ * and binary, 2 count + 1 each.  -1: the range is outside the index. */
+int tsg_debug_tar_batch_plan(const struct tsg_tar_index* ix, uint32_t first, uint32_t count, const uint8_t* flags,
+                             uint64_t* base, uint64_t* offs, uint8_t* kinds, uint8_t* binary);
+
 /* Thread-local text of the last error. */
 const char* tsg_last_error(void);
 

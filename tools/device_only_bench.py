@@ -33,8 +33,16 @@ block's figure (the claim to check: the split's slowest block is below the chunk
 the split stats (ms_census against the arena's size among them), the fetch and window stats and
 ms_gpu_total of both.
 
+--layer [--layer-gb G]: one uncompressed tar layer as bench.py's C4 generator makes it
+(trivy_amd.corpus.generate_layer), put in HBM once.  Blocks of AnalyzeLayerDevice -- the GPU indexes
+the resident layer's headers, the host follows the chain, every batch is scanned where it lies --
+alternate with blocks of AnalyzeLayer(gather=True) on the page-locked, mapped host copy (the fastest
+host layer path), in one process on one scanner, with --fetch / --resident in force for both.  One
+JSON line per mode: ms per step with every block's figure, the index's ms_kernel / ms_total and
+counters, the bytes fetched per step and the host CPUs busy (process CPU time / wall time).
+
 Usage: python tools/device_only_bench.py [--gb 4] [--steps 20] [--warmup 5] [--depth 3]
-                                         [--analyze [--resident split]]
+                                         [--analyze [--resident split]] [--layer [--layer-gb 4]]
                                          [--fetch windows [--fwd N] [--fwd-cap N] [--back N]] [--out FILE]
 """
 import argparse
@@ -62,10 +70,16 @@ def main():
                     help="windows: the three-mode leg (mirrored / files fetch / windows fetch)")
     ap.add_argument("--resident", choices=["chunked", "split"], default="chunked",
                     help="with --analyze; split: chunked and split blocks of AnalyzeDevice interleaved")
+    ap.add_argument("--layer", action="store_true", help="the resident tar layer leg")
+    ap.add_argument("--layer-gb", type=float, default=4.0)
+    ap.add_argument("--arena-mb", type=int, default=256, help="--layer: batch size of both modes")
+    ap.add_argument("--collectors", type=int, default=6, help="--layer: the host mode's collectors")
     ap.add_argument("--fwd", type=int, default=None)
     ap.add_argument("--fwd-cap", type=int, default=None)
     ap.add_argument("--back", type=int, default=None)
     args = ap.parse_args()
+    if args.layer:
+        return layer_leg(args)
     if args.analyze and args.resident == "split":
         return resident_leg(args)
     if args.analyze:
@@ -412,6 +426,95 @@ def resident_leg(args):
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         with open(args.out, "a") as f:
             f.write(line + "\n")
+
+
+def layer_leg(args):
+    import torch
+    import trivy_amd.secret as secret
+    from trivy_amd import corpus
+    from trivy_amd.analyzer import AnalyzerOptions, SecretAnalyzer
+    from trivy_amd.analyzer.secret import Collector
+
+    layer = corpus.generate_layer(int(args.layer_gb * 1e9), seed=corpus.SEED)
+    n_bytes = int(layer.nbytes)
+    dev = torch.device("cuda", 0)
+    d_layer = torch.empty(n_bytes + 64, dtype=torch.uint8, device=dev)  # the 64 readable bytes after the layer
+    d_layer[:n_bytes].copy_(torch.from_numpy(layer))
+    d_layer[n_bytes:].zero_()
+    torch.cuda.synchronize()
+    an = SecretAnalyzer(device=0)
+    an.Init(AnalyzerOptions())
+    sc = an.scanner
+    sc.set_resident_transform(args.resident)
+    if args.fetch == "windows":
+        sc.set_fetch_mode("windows", back=args.back, fwd=args.fwd, fwd_cap=args.fwd_cap)
+    colls = [Collector(an, args.arena_mb << 20, True, gather=True) for _ in range(args.collectors)]
+    unregister = secret.HostRegister(layer, mapped=True)  # registered once, outside the timed region
+    modes = ("device", "host")
+
+    def step(mode):
+        st = {}
+        if mode == "device":
+            an.AnalyzeLayerDevice(d_layer, n_bytes, arena_bytes=args.arena_mb << 20, depth=args.depth, stats=st,
+                                  materialize=False)
+        else:
+            an.AnalyzeLayer(layer, stats=st, materialize=False, colls=colls, registered=True)
+        return st
+
+    def block(mode, n):
+        torch.cuda.synchronize()
+        t0, c0 = time.perf_counter(), time.process_time()
+        sts = [step(mode) for _ in range(n)]
+        wall = time.perf_counter() - t0
+        return wall, (time.process_time() - c0) / wall, sts
+
+    try:
+        for mode in modes:
+            block(mode, args.warmup)
+        per = {m: [] for m in modes}
+        cpus = {m: [] for m in modes}
+        res = {m: [] for m in modes}
+        done = 0
+        while done < args.steps:
+            n = min(args.block, args.steps - done)
+            for mode in modes:
+                s, cpu, sts = block(mode, n)
+                per[mode].append(1e3 * s / n)
+                cpus[mode].append(cpu)
+                res[mode] += sts
+            done += n
+    finally:
+        unregister()
+    findings = {m: res[m][-1]["scan_findings"] for m in modes}
+    assert findings["device"] == findings["host"], findings
+
+    def med(xs):
+        return float(statistics.median(xs))
+
+    claim = max(per["device"]) < min(per["host"])
+    for m in modes:
+        last = res[m][-1]
+        out = {"tool": "device_only_bench --layer", "mode": m, "fetch": args.fetch, "resident": args.resident,
+               "gb": n_bytes / 1e9, "steps": args.steps, "block": args.block, "depth": args.depth,
+               "arena_mb": args.arena_mb, "ms_per_step": med(per[m]), "blocks_ms": per[m],
+               "gbps": n_bytes / 1e6 / med(per[m]), "host_cpus": med(cpus[m]), "findings": int(findings[m]),
+               "device_slowest_below_host_fastest": claim}
+        if m == "device":
+            keys = ("ms_kernel", "ms_total", "blocks", "candidates", "off_chain", "block_fetches", "ext_bytes",
+                    "kernel_runs", "entries", "regular", "required", "files")
+            out["index"] = {k: med([r[k] for r in res[m]]) for k in keys}
+            out["index_kernel_gbps"] = n_bytes / 1e6 / out["index"]["ms_kernel"]
+        else:
+            out["walk_s"] = med([r["walk_s"] for r in res[m]])
+            out["wait_s"] = med([r["wait_s"] for r in res[m]])
+            out["added"] = int(last["added"])
+        out["scan"] = {k[5:]: med([r[k] for r in res[m]]) for k in last if k.startswith("scan_")}
+        line = json.dumps(out)
+        print(line)
+        if args.out:
+            Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
 
 
 if __name__ == "__main__":

@@ -64,12 +64,44 @@ DEVICE_CLASSIFY_STATS_SIZE_V1 = _CDeviceClassifyStats.ms_total.offset + c.sizeof
 XFORM_DROP = 3  # tsg_batch.transform: a file the analyzer skips, dropped from the scan
 
 
+class _CDeviceTar(c.Structure):  # tsg_device_tar (versioned)
+    _fields_ = [("struct_size", c.c_uint32), ("reserved", c.c_uint32), ("dev_tar", c.c_void_p),
+                ("n_bytes", c.c_uint64)]
+
+
+DEVICE_TAR_SIZE_V1 = _CDeviceTar.n_bytes.offset + c.sizeof(c.c_uint64)
+
+
+class _CDeviceTarStats(c.Structure):  # tsg_device_tar_stats (versioned)
+    _fields_ = [("struct_size", c.c_uint32), ("reserved", c.c_uint32), ("tar", _CTarStats)] + \
+               [(n, c.c_uint64) for n in ("blocks", "candidates", "off_chain", "block_fetches", "ext_bytes",
+                                          "kernel_runs")] + [("ms_kernel", c.c_double), ("ms_total", c.c_double)]
+
+    def to_dict(self):
+        d = {n: getattr(self.tar, n) for n in ("entries", "regular", "required", "whiteouts", "opaque_dirs")}
+        d.update({n: getattr(self, n) for n, _ in self._fields_ if n not in ("struct_size", "reserved", "tar")})
+        return d
+
+
+DEVICE_TAR_STATS_SIZE_V1 = _CDeviceTarStats.ms_total.offset + c.sizeof(c.c_double)
+
+
 def _declare(L):
     if getattr(L, "_tsg_analyzer_declared", False):
         return
     L.tsg_analyzer_classify_device.argtypes = [c.c_void_p, c.POINTER(_CDeviceFiles), c.c_void_p, c.c_void_p,
                                                c.POINTER(_CDeviceClassifyStats)]
     L.tsg_analyzer_submit_device.argtypes = [c.c_void_p, c.POINTER(_CDeviceFiles), c.POINTER(c.c_void_p)]
+    L.tsg_analyzer_index_device_tar.argtypes = [c.c_void_p, c.POINTER(_CDeviceTar), c.POINTER(c.c_void_p),
+                                                c.POINTER(_CDeviceTarStats)]
+    L.tsg_tar_index_files.argtypes = [c.c_void_p]
+    L.tsg_tar_index_files.restype = c.c_uint32
+    L.tsg_tar_index_file.argtypes = [c.c_void_p, c.c_uint32, c.POINTER(c.c_void_p), c.POINTER(c.c_uint64),
+                                     c.POINTER(c.c_uint64), c.POINTER(c.c_uint64)]
+    L.tsg_tar_index_spans.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+    L.tsg_analyzer_submit_device_tar.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32,
+                                                 c.POINTER(c.c_void_p)]
+    L.tsg_tar_index_free.argtypes = [c.c_void_p]
     L.tsg_is_binary.argtypes = [c.c_char_p, c.c_uint64]
     L.tsg_extract_printable.argtypes = [c.c_char_p, c.c_uint64, c.c_char_p]
     L.tsg_extract_printable.restype = c.c_uint64
@@ -337,6 +369,93 @@ class PendingDeviceAnalyze:
         return [AnalysisResult(Secrets=[s]) if s.Findings else None for s in self.result.secrets(paths)]
 
 
+class DeviceTarIndex:
+    """The index of a tar layer resident in HBM (tsg_tar_index): its Required-accepted regular files in
+    walk order.  Keeps the layer tensor referenced; the layer must stay unchanged while it lives."""
+
+    def __init__(self, analyzer, h, keep, stats):
+        self._an, self._h, self._keep, self.stats = analyzer, h, keep, stats
+        L = analyzer._L
+        self.n = L.tsg_tar_index_files(h)
+        self.start = np.zeros(max(1, self.n), dtype=np.uint64)  # where each entry's header chain begins
+        self.data_off = np.zeros(max(1, self.n), dtype=np.uint64)
+        self.size = np.zeros(max(1, self.n), dtype=np.uint64)
+        L.tsg_tar_index_spans(h, self.start.ctypes.data, self.data_off.ctypes.data, self.size.ctypes.data)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._an._L.tsg_tar_index_free(self._h)
+            self._h = None
+
+    def path(self, i: int) -> str:
+        pp, pl = c.c_void_p(), c.c_uint64()
+        if self._an._L.tsg_tar_index_file(self._h, i, c.byref(pp), c.byref(pl), None, None) != 0:
+            raise IndexError(i)
+        return c.string_at(pp, pl.value).decode("utf-8", "surrogateescape")
+
+    def files(self):
+        """[(path, data_off, size)]"""
+        return [(self.path(i), int(self.data_off[i]), int(self.size[i])) for i in range(self.n)]
+
+    def batches(self, arena_bytes: int):
+        """[(first, count)]: runs of files spanning at most arena_bytes of the layer, cut at entry
+        boundaries; a larger single file goes alone."""
+        out, i = [], 0
+        end = self.data_off[:self.n] + self.size[:self.n]
+        while i < self.n:
+            start = int(self.start[i])  # the batch's arena begins where file i's header chain does
+            j = int(np.searchsorted(end, start + int(arena_bytes), side="right"))
+            j = min(self.n, max(j, i + 1))
+            out.append((i, j - i))
+            i = j
+        return out
+
+    def submit(self, first: int, count: int) -> "PendingDeviceLayer":
+        h = c.c_void_p()
+        if self._an._L.tsg_analyzer_submit_device_tar(self._an._h, self._h, first, count, c.byref(h)) != 0:
+            raise RuntimeError("tsg_analyzer_submit_device_tar failed: %s" % _lib.last_error(self._an._L))
+        return PendingDeviceLayer(self, h, first, count)
+
+
+class PendingDeviceLayer:
+    """A batch of a resident layer in flight (tsg_analyzer_submit_device_tar).  The batch's result has
+    2 count + 1 pseudo-files, gap, file, gap, ...: wait() hides that and gives one entry per index file."""
+
+    def __init__(self, index: DeviceTarIndex, h, first, count):
+        self._ix, self._h, self.first, self.count = index, h, first, count
+        self.result = None  # the ScanResult, after wait()
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:  # dropped without wait(): join the native thread before the index and the layer go
+            r = c.c_void_p()
+            self._ix._an._L.tsg_scan_wait(h, c.byref(r))
+            self._h = None
+            if r:
+                self._ix._an._L.tsg_result_free(r)
+
+    def wait(self, materialize: bool = True):
+        """Per index file of the batch the Secret when it has findings, else None (materialize=False:
+        the batch's tsg_stats dict)."""
+        L = self._ix._an._L
+        r = c.c_void_p()
+        rc = L.tsg_scan_wait(self._h, c.byref(r))
+        self._h = None
+        if rc != 0:
+            raise RuntimeError("AnalyzeLayerDevice failed: %s" % _lib.last_error(L))
+        self.result = ScanResult(_ScannerRef(L), r)
+        if not materialize:  # the scan counters, with what came back from HBM and the census's time
+            d = self.result.stats()
+            fs, ws, ss = self.result.fetch_stats(), self.result.fetch_window_stats(), self.result.split_stats()
+            d.update({"fetch_files": fs["files"], "fetch_bytes": fs["bytes"], "window_bytes": ws["window_bytes"],
+                      "ms_census": ss["ms_census"]})
+            return d
+        paths = [""] * (2 * self.count + 1)
+        for j in range(self.count):
+            paths[2 * j + 1] = "/" + self._ix.path(self.first + j)  # image files (secret.go:130-135)
+        return [s if s.Findings else None for s in self.result.secrets(paths)[1::2]]
+
+
 def _pipeline(colls, fill, take):
     """Fill the collectors in turn (fill(coll) -> True at the end of the input) and submit
     each batch; with n collectors, n - 1 scans stay in flight while the next batch is
@@ -525,6 +644,92 @@ class SecretAnalyzer:
         the scan where they lie, .pyc binaries and CRLF text are transformed on the GPU, and only the
         files that got candidates come back for the exact pass.  Shaped like AnalyzeBatch."""
         return self.AnalyzeDeviceAsync(dev_arena, offsets, paths, dir_, dev_offsets, nbytes).wait()
+
+    # --- a tar layer resident in HBM -------------------------------------------
+    def _device_layer(self, dev_layer, nbytes):
+        """Checks a resident layer (a torch.uint8 tensor, or an integer device pointer with nbytes) against
+        the contract: on the scanner's device, contiguous, 16-B aligned, nbytes + 64 readable bytes."""
+        if self.scanner is None:
+            raise RuntimeError("the analyzer has no scanner (Init first)")
+        if isinstance(dev_layer, int):
+            if nbytes is None:
+                raise ValueError("AnalyzeLayerDevice: an integer device pointer needs nbytes")
+            return dev_layer, int(nbytes), None
+        import torch
+        t = dev_layer
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise ValueError("AnalyzeLayerDevice: the layer must be a torch.uint8 tensor or an integer device pointer")
+        if t.device.type != "cuda" or (self.device is not None and t.device.index != self.device):
+            raise ValueError("AnalyzeLayerDevice: the layer is on %s, the scanner on device %s" % (t.device, self.device))
+        if not t.is_contiguous():
+            raise ValueError("AnalyzeLayerDevice: the layer must be contiguous")
+        n = t.numel() - 64 if nbytes is None else int(nbytes)
+        if n < 0 or t.numel() < n + 64:
+            raise ValueError("AnalyzeLayerDevice: the tensor holds %d bytes; nbytes + 64 = %d are read"
+                             % (t.numel(), n + 64))
+        return t.data_ptr(), n, t
+
+    def IndexDevice(self, dev_layer, nbytes=None, stats=None) -> DeviceTarIndex:
+        """The DeviceTarIndex of a layer resident in HBM (tsg_analyzer_index_device_tar)."""
+        ptr, n, keep = self._device_layer(dev_layer, nbytes)
+        if ptr % 16 != 0:
+            raise ValueError("AnalyzeLayerDevice: the layer must be 16-B aligned")
+        t = _CDeviceTar(DEVICE_TAR_SIZE_V1, 0, ptr, n)
+        st = _CDeviceTarStats()
+        st.struct_size = DEVICE_TAR_STATS_SIZE_V1
+        h = c.c_void_p()
+        rc = self._L.tsg_analyzer_index_device_tar(self._h, c.byref(t), c.byref(h), c.byref(st))
+        if rc == -3:  # a malformed archive (-2: a HIP error, also one in a copy the walk asked for)
+            raise ValueError("tar layer: %s" % _lib.last_error(self._L))
+        if rc != 0:
+            raise RuntimeError("tsg_analyzer_index_device_tar failed: %s" % _lib.last_error(self._L))
+        d = st.to_dict()
+        if stats is not None:
+            stats.update(d)
+        return DeviceTarIndex(self, h, keep, d)
+
+    def IndexLayerDevice(self, dev_layer, nbytes=None, stats=None):
+        """Where the files of an uncompressed tar layer resident in HBM are: ([(path, data_off, size)] of
+        the regular files Required accepts, in walk order; the stats dict).  The GPU finds the blocks that
+        parse as headers, the host follows the chain over them (tsg_analyzer_index_device_tar)."""
+        ix = self.IndexDevice(dev_layer, nbytes, stats)
+        return ix.files(), ix.stats
+
+    def AnalyzeLayerDevice(self, dev_layer, nbytes=None, arena_bytes: int = 1 << 30, depth: int = 2,
+                           stats: Optional[dict] = None, materialize: bool = True) -> AnalysisResult:
+        """AnalyzeLayer for a layer whose bytes exist only in HBM (a torch.uint8 tensor holding nbytes + 64
+        bytes, nbytes = numel - 64 by default; or an integer pointer with nbytes): exactly what AnalyzeLayer
+        returns for the same bytes on the host.  The layer is indexed on the GPU, cut into batches of at
+        most arena_bytes of layer span at entry boundaries (a larger single file goes alone), and each
+        batch is scanned in place -- the layer itself is the arena -- with up to `depth` in flight."""
+        ix = self.IndexDevice(dev_layer, nbytes)
+        result = AnalysisResult()
+        scan_tot: dict = {}
+        inflight = collections.deque()
+
+        def take(p):
+            out = p.wait(materialize)
+            if materialize:
+                result.Secrets.extend(sec for sec in out if sec is not None)
+            else:
+                for k2, v in out.items():
+                    scan_tot[k2] = scan_tot.get(k2, 0) + v
+        t0 = time.perf_counter()
+        try:
+            for first, count in ix.batches(arena_bytes):
+                while len(inflight) >= max(1, depth):
+                    take(inflight.popleft())
+                inflight.append(ix.submit(first, count))
+            while inflight:
+                take(inflight.popleft())
+        finally:
+            while inflight:  # an error left batches in flight: join them before the index goes
+                inflight.popleft().__del__()
+        if stats is not None:
+            stats.update(ix.stats)
+            stats.update({"scan_" + k2: v for k2, v in scan_tot.items()})
+            stats.update({"files": ix.n, "scan_s": time.perf_counter() - t0})
+        return result
 
     def AnalyzeFS(self, root: str, opt=None, arena_bytes: int = 256 << 20, stats: Optional[dict] = None,
                   materialize: bool = True, colls: Optional[List["Collector"]] = None,

@@ -90,6 +90,8 @@ void GiveCtx(tsg_analyzer* a, std::unique_ptr<ClassifyCtx> c) {
   if (a->classify->free.size() < 4) a->classify->free.push_back(std::move(c));  // (else freed here)
 }
 
+}  // namespace
+
 // The GPU half: flags[f] = IsBinary over file f's head.  ms_kernel from HIP events.
 bool ClassifyOnGpu(tsg_analyzer* a, const tsg_device_files& f, uint8_t* flags, double* ms_kernel, std::string* err) {
   *ms_kernel = 0;
@@ -152,6 +154,8 @@ bool ClassifyOnGpu(tsg_analyzer* a, const tsg_device_files& f, uint8_t* flags, d
   GiveCtx(a, std::move(c));
   return true;
 }
+
+namespace {
 
 double NowMs() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();

@@ -29,6 +29,10 @@ bool CheckDeviceFiles(const tsg_analyzer* a, const tsg_device_files* f, const ch
 // st (optional): files, required, skipped_binary, pyc are filled.
 void DeviceKinds(const tsg_analyzer* a, const tsg_device_files& f, const uint8_t* flags, uint8_t* kind,
                  uint8_t* binary, tsg_device_classify_stats* st);
+// The GPU half (classify.h): flags[i] = IsBinary over file i's head, read from
+// f.dev_arena at f.host_offsets (f.dev_offsets when given); only those fields
+// and n_files are used.  On a pooled stream of its own; ms_kernel from HIP events.
+bool ClassifyOnGpu(tsg_analyzer* a, const tsg_device_files& f, uint8_t* flags, double* ms_kernel, std::string* err);
 // The scan paths: AnalysisInput.FilePath, with the "/" prefix when dir is "" (secret.go:130-135).
 void BuildScanPaths(const tsg_device_files& f, DevicePlan* p);
 // tsg_analyzer_submit_device with the flags given instead of computed on the

@@ -22,6 +22,7 @@
 
 #include "capi_internal.h"
 #include "parallel.h"
+#include "tar_index_host.h"
 
 namespace tsg {
 void SetError(const std::string& e);
@@ -138,62 +139,6 @@ uint64_t StripCR(const uint8_t* in, uint64_t n, uint8_t* out) {
   return w;
 }
 
-// True when path.Clean(p) == p: no empty, "." or ".." element, no trailing
-// slash (other than the root itself).  Most archive names already are clean.
-inline bool GoPathIsClean(const char* p, size_t n) {
-  if (n == 0) return false;
-  if (n == 1) return p[0] != '.';
-  if (p[n - 1] == '/') return false;
-  size_t s = 0;  // element start
-  for (size_t i = 0; i <= n; i++) {
-    if (i < n && p[i] != '/') continue;
-    const size_t len = i - s;
-    if (len == 0 && i != 0) return false;                      // "//" (a leading '/' is the root)
-    if (len == 1 && p[s] == '.') return false;                 // "."
-    if (len == 2 && p[s] == '.' && p[s + 1] == '.') return false;  // ".."
-    s = i + 1;
-  }
-  return true;
-}
-
-// path.Clean (Go, slash-separated).
-std::string GoPathClean(const std::string& path) {
-  if (path.empty()) return ".";
-  if (GoPathIsClean(path.data(), path.size())) return path;
-  const bool rooted = path[0] == '/';
-  const size_t n = path.size();
-  std::string out;
-  out.reserve(n + 1);
-  size_t r = 0, dotdot = 0;
-  if (rooted) {
-    out.push_back('/');
-    r = dotdot = 1;
-  }
-  while (r < n) {
-    if (path[r] == '/') {
-      r++;
-    } else if (path[r] == '.' && (r + 1 == n || path[r + 1] == '/')) {
-      r++;
-    } else if (path[r] == '.' && path[r + 1] == '.' && (r + 2 == n || path[r + 2] == '/')) {
-      r += 2;
-      if (out.size() > dotdot) {  // back to the last '/' at or after dotdot (Go: w--, then while out[w] != '/')
-        size_t w = out.size() - 1;
-        while (w > dotdot && out[w] != '/') w--;
-        out.resize(w);
-      } else if (!rooted) {
-        if (!out.empty()) out.push_back('/');
-        out += "..";
-        dotdot = out.size();
-      }
-    } else {
-      if ((rooted && out.size() != 1) || (!rooted && !out.empty())) out.push_back('/');
-      for (; r < n && path[r] != '/'; r++) out.push_back(path[r]);
-    }
-  }
-  if (out.empty()) return ".";
-  return out;
-}
-
 // filepath.Ext / filepath.Base (Unix).
 std::string GoExt(const std::string& p) {
   for (size_t i = p.size(); i-- > 0 && p[i] != '/';)
@@ -287,100 +232,6 @@ int64_t Add(tsg_collector* c, const char* path, uint64_t plen, bool image, const
   return int64_t(c->files() - 1);
 }
 
-// ---- archive/tar header reading (Go 1.22 archive/tar/reader.go semantics) ----
-bool AllZero(const uint8_t* b) {
-  uint64_t acc;
-  std::memcpy(&acc, b, 8);  // a header starts with its name: almost always decided here
-  if (acc) return false;
-  for (int i = 0; i < 64; i++) {
-    uint64_t w;
-    std::memcpy(&w, b + 8 * i, 8);
-    acc |= w;
-  }
-  return acc == 0;
-}
-std::string CStr(const uint8_t* b, size_t n) {  // parseString: up to the first NUL
-  size_t k = 0;
-  while (k < n && b[k]) k++;
-  return std::string(reinterpret_cast<const char*>(b), k);
-}
-bool ParseNumeric(const uint8_t* b, size_t n, int64_t* out) {  // parseNumeric
-  if (n > 0 && (b[0] & 0x80)) {  // base-256 (two's complement, big-endian)
-    const bool neg = b[0] & 0x40;
-    uint64_t v = 0;
-    for (size_t i = 0; i < n; i++) {
-      uint8_t c = i == 0 ? (b[0] & 0x7F) : b[i];
-      if (neg) c ^= 0xFF;
-      if (i == 0 && neg) c &= 0x7F;
-      if (v >> 56) return false;
-      v = (v << 8) | c;
-    }
-    if (v >> 63) return false;
-    *out = neg ? -int64_t(v) - 1 : int64_t(v);
-    return true;
-  }
-  // parseOctal: trim spaces and NULs at both ends
-  size_t lo = 0, hi = n;
-  while (lo < hi && (b[lo] == ' ' || b[lo] == 0)) lo++;
-  while (hi > lo && (b[hi - 1] == ' ' || b[hi - 1] == 0)) hi--;
-  int64_t v = 0;
-  for (size_t i = lo; i < hi; i++) {
-    if (b[i] < '0' || b[i] > '7') return false;
-    if (v >> 60) return false;
-    v = v * 8 + (b[i] - '0');
-  }
-  *out = v;
-  return true;
-}
-bool ChecksumOK(const uint8_t* b) {
-  int64_t want = 0;
-  if (!ParseNumeric(b + 148, 8, &want)) return false;
-  // the unsigned byte sum with the checksum field read as spaces, else the
-  // signed one (old writers); plain loops, vectorised by the compiler
-  __m256i acc = _mm256_setzero_si256();  // unsigned sum: psadbw against zero, 32 B a step
-  for (int i = 0; i < 512; i += 32)
-    acc = _mm256_add_epi64(acc, _mm256_sad_epu8(_mm256_loadu_si256(reinterpret_cast<const __m256i*>(b + i)),
-                                                 _mm256_setzero_si256()));
-  int32_t u = int32_t(_mm256_extract_epi64(acc, 0) + _mm256_extract_epi64(acc, 1) + _mm256_extract_epi64(acc, 2) +
-                      _mm256_extract_epi64(acc, 3));
-  for (int i = 148; i < 156; i++) u += ' ' - b[i];
-  if (want == u) return true;
-  int32_t s = 0;
-  for (int i = 0; i < 512; i++) s += int8_t(b[i]);
-  for (int i = 148; i < 156; i++) s += ' ' - int8_t(b[i]);
-  return want == s;
-}
-// PAX records "%d %s=%s\n" (parsePAX): path, size and linkpath matter here.
-bool ParsePax(const uint8_t* d, uint64_t n, std::string* path, int64_t* size, bool* has_path, bool* has_size) {
-  uint64_t p = 0;
-  while (p < n) {
-    uint64_t sp = p;
-    while (sp < n && d[sp] != ' ') sp++;
-    if (sp >= n) return false;
-    uint64_t len = 0;
-    for (uint64_t i = p; i < sp; i++) {
-      if (d[i] < '0' || d[i] > '9') return false;
-      len = len * 10 + (d[i] - '0');
-    }
-    if (len < sp - p + 2 || p + len > n || d[p + len - 1] != '\n') return false;
-    const std::string rec(reinterpret_cast<const char*>(d + sp + 1), size_t(len - (sp + 1 - p) - 1));
-    const size_t eq = rec.find('=');
-    if (eq == std::string::npos) return false;
-    const std::string k = rec.substr(0, eq), v = rec.substr(eq + 1);
-    if (k == "path") {
-      *path = v;
-      *has_path = true;
-    } else if (k == "size") {
-      char* e = nullptr;
-      *size = std::strtoll(v.c_str(), &e, 10);
-      if (v.empty() || *e) return false;
-      *has_size = true;
-    }
-    p += len;
-  }
-  return true;
-}
-bool HeaderOnly(char t) { return t == '1' || t == '2' || t == '3' || t == '4' || t == '5' || t == '6'; }
 }  // namespace
 
 extern "C" {
@@ -436,108 +287,17 @@ int64_t tsg_collector_add(tsg_collector* c, const char* path, uint64_t path_len,
 
 }  // extern "C"
 
-namespace tsg {
-// One archive entry as the walk sees it (header chain resolved).
-struct TarEntry {
-  uint64_t start, next;  // header chain start, next entry
-  uint64_t hdr;          // the entry's own header
-  uint64_t data, size;   // content
-  uint64_t long_off, long_len;  // GNU 'L' long name data (long_len == ~0: none)
-  uint8_t what;          // 0 other, 1 whiteout, 2 opaque dir, 3 regular file
-  uint8_t has_pax_path;
-  uint8_t bad;           // the entry header's checksum is wrong (checked on the threads)
-  // The cleaned path (walker/tar.go:46-48): a view of the header's name field
-  // in the archive itself when that is already the answer (a ustar name with
-  // no prefix, clean), else an owned string (PAX / GNU long names, prefixes,
-  // names that Clean changes) -- no allocation per entry on the common path.
-  std::unique_ptr<std::string> fp_own;  // set: the path is *fp_own
-  uint64_t fp_off = 0;
-  uint32_t fp_len = 0;
-  std::string_view path(const uint8_t* tar) const {
-    return fp_own ? std::string_view(*fp_own) : std::string_view(reinterpret_cast<const char*>(tar + fp_off), fp_len);
-  }
-  void own(std::string v) { fp_own.reset(new std::string(std::move(v))); }
-  // filled by the parallel pass
-  uint8_t state;         // 0 not required, 1 binary skipped, 2 add
-  uint8_t bin;
-  uint64_t out_len, out_off;
-};
-
-}  // namespace tsg
-
 namespace {
+using tsg::AllZero;
+using tsg::ChecksumOK;
 using tsg::TarEntry;
 
-// Sequential step of the walk: hop over the header chain starting at p using
-// only what decides the next entry's position (zero block, typeflag, size,
-// PAX size).  Extended headers are checked here (rare); the entry header's
-// checksum and name are resolved later on the ingest threads (Resolve).
-// 0 = entry read, 1 = end of archive, <0 = malformed.
-int ChainEntry(const uint8_t* tar, uint64_t n, uint64_t p, TarEntry* e) {
-  e->start = p;
-  e->long_len = ~uint64_t(0);
-  e->has_pax_path = 0;
-  std::string pax_path;
-  bool has_pax_path = false, has_pax_size = false;
-  int64_t pax_size = 0, size = 0;
-  const uint8_t* h = nullptr;
-  char type = 0;
-  for (;;) {
-    if (p + 512 > n) {
-      if (p >= n) return 1;  // io.EOF without the zero blocks
-      tsg::SetError("tar: truncated header");
-      return -1;
-    }
-    h = tar + p;
-    if (AllZero(h)) return 1;  // end-of-archive marker
-    type = char(h[156]);
-    if (!ParseNumeric(h + 124, 12, &size) || size < 0) {
-      tsg::SetError("tar: invalid size field");
-      return -1;
-    }
-    const uint64_t dsz = HeaderOnly(type) ? 0 : uint64_t(size);
-    const uint64_t data = p + 512;
-    if (data + dsz > n) {
-      tsg::SetError("tar: truncated entry data");
-      return -1;
-    }
-    if (type != 'x' && type != 'L' && type != 'K') break;
-    if (!ChecksumOK(h)) {
-      tsg::SetError("tar: invalid header checksum at offset " + std::to_string(p));
-      return -1;
-    }
-    if (type == 'x' && !ParsePax(tar + data, dsz, &pax_path, &pax_size, &has_pax_path, &has_pax_size)) {
-      tsg::SetError("tar: invalid PAX record");
-      return -1;
-    }
-    if (type == 'L') {
-      e->long_off = data;
-      e->long_len = dsz;
-    }
-    p = data + ((dsz + 511) & ~uint64_t(511));
-  }
-  e->hdr = p;
-  if (has_pax_size) size = pax_size;
-  if (type == '\0') {  // TypeRegA: a directory when the name ends in '/' (resolved name: Resolve)
-    type = '0';
-  }
-  const uint64_t dsz = HeaderOnly(type) ? 0 : uint64_t(size);
-  e->data = p + 512;
-  if (e->data + dsz > n) {
-    tsg::SetError("tar: truncated entry data");
-    return -1;
-  }
-  e->size = dsz;
-  e->next = e->data + ((dsz + 511) & ~uint64_t(511));
-  e->what = type == '0' ? 3 : 0;
-  if (has_pax_path) {
-    e->own(std::move(pax_path));
-    e->has_pax_path = 1;
-  }
-  return 0;
+// The header reading and the per-entry path logic live in tar_index_host.h,
+// written over a block accessor; a layer in host memory is HostTarSrc, a pointer.
+inline int ChainEntry(const uint8_t* tar, uint64_t n, uint64_t p, TarEntry* e) {
+  return tsg::ChainEntryT(tsg::HostTarSrc{tar}, n, p, e);
 }
-
-void Classify(const uint8_t* tar, TarEntry* e);
+inline void Classify(const uint8_t* tar, TarEntry* e) { tsg::ClassifyT(tsg::HostTarSrc{tar}, tar, e); }
 
 // Everything the walk decides about one entry, on the thread that indexed it
 // (its header and path are still in that core's cache): the name (Classify),
@@ -773,65 +533,6 @@ void EndTarWalk(TarWalkCache* w) {
   w->pos = 0;
 }
 }  // namespace tsg
-
-namespace {
-// The entry's name (ustar prefix, GNU long name, PAX path) and header checksum.
-void Resolve(const uint8_t* tar, TarEntry* e) {
-  const uint8_t* h = tar + e->hdr;
-  e->bad = ChecksumOK(h) ? 0 : 1;
-  if (e->has_pax_path) return;
-  if (e->long_len != ~uint64_t(0)) {
-    e->own(CStr(tar + e->long_off, size_t(e->long_len)));
-  } else {
-    auto clen = [](const uint8_t* b, size_t n) {
-      const void* z = std::memchr(b, 0, n);
-      return z ? size_t(static_cast<const uint8_t*>(z) - b) : n;
-    };
-    const size_t nl = clen(h, 100);
-    size_t pl = 0;
-    if (std::memcmp(h + 257, "ustar\0", 6) == 0 && std::memcmp(h + 263, "00", 2) == 0) pl = clen(h + 345, 155);
-    if (pl) {
-      std::string v;
-      v.reserve(pl + 1 + nl);
-      v.append(reinterpret_cast<const char*>(h + 345), pl);
-      v.push_back('/');
-      v.append(reinterpret_cast<const char*>(h), nl);
-      e->own(std::move(v));
-    } else {
-      e->fp_own.reset();
-      e->fp_off = e->hdr;
-      e->fp_len = uint32_t(nl);
-    }
-  }
-}
-
-// LayerTar.Walk's per-entry path logic (walker/tar.go:41-84): clean the name,
-// classify whiteout / opaque markers.
-void Classify(const uint8_t* tar, TarEntry* e) {
-  Resolve(tar, e);
-  std::string_view fp = e->path(tar);
-  if (tar[e->hdr + 156] == '\0' && !fp.empty() && fp.back() == '/') e->what = 0;  // TypeRegA dir
-  if (!tsg::GoPathIsClean(fp.data(), fp.size())) {
-    e->own(tsg::GoPathClean(std::string(fp)));
-    fp = *e->fp_own;
-  }
-  size_t t = 0;
-  while (t < fp.size() && fp[t] == '/') t++;
-  if (t) {
-    if (e->fp_own) {
-      e->fp_own->erase(0, t);
-    } else {
-      e->fp_off += t;
-      e->fp_len -= uint32_t(t);
-    }
-    fp = e->path(tar);
-  }
-  const size_t slash = fp.rfind('/');
-  const std::string_view file_name = fp.substr(slash == std::string_view::npos ? 0 : slash + 1);
-  if (file_name == ".wh..wh..opq") e->what = 2;
-  else if (file_name.substr(0, 4) == ".wh.") e->what = 1;
-}
-}  // namespace
 
 namespace {
 // The bulk part of the walk's accept step: the longest run of whole

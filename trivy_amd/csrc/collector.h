@@ -21,6 +21,8 @@ void FreeTarWalkCache(TarWalkCache* w);
 void EndTarWalk(TarWalkCache* w);  // joins the background index of the next window
 struct ClassifyPool;  // analyze_device.cpp: streams and buffers of the classify passes in flight
 void FreeClassifyPool(ClassifyPool* p);
+struct TarIndexPool;  // device_layer.cpp: streams and buffers of the tar index passes in flight
+void FreeTarIndexPool(TarIndexPool* p);
 }
 
 struct tsg_analyzer {
@@ -38,9 +40,13 @@ struct tsg_analyzer {
   // tsg_analyzer_classify_device / _submit_device: made on first use
   std::mutex classify_mu;
   tsg::ClassifyPool* classify = nullptr;
+  // tsg_analyzer_index_device_tar: made on first use
+  std::mutex tar_index_mu;
+  tsg::TarIndexPool* tar_index = nullptr;
   ~tsg_analyzer() {
     tsg::FreeTarWalkCache(walk);
     tsg::FreeClassifyPool(classify);
+    tsg::FreeTarIndexPool(tar_index);
   }
 };
 

@@ -262,6 +262,49 @@ int tsg_analyzer_submit_device_tar(tsg_analyzer* a, const tsg_tar_index* ix, uin
                                    tsg_pending** out);
 void tsg_tar_index_free(tsg_tar_index* ix);
 
+/* Where the header chain of tsg_analyzer_index_device_tar is walked.  Mode 0,
+ * host (the default): the GPU collects the candidate records and the host walks
+ * the chain over them, as described above.  Mode 1, gpu (opt-in): the candidates
+ * stay in HBM as one bit per block, the GPU reads every candidate as an entry
+ * start, marks the entries the chain from block 0 visits and writes one 64-B
+ * record and the raw name per entry, in walk order (trivy_amd/csrc/tarchain.hip);
+ * the host copies those two buffers, cleans and classifies the names and runs
+ * Required on its threads.  The index, the tar stats, the return code and the
+ * error text are those of mode 0 for any bytes: a layer the GPU walk does not
+ * complete -- a malformed archive, a PAX size that is not plain digits, PAX or
+ * long-name data above 64 KiB, more than 16 extension headers before one entry
+ * -- is indexed again from scratch by mode 0 (tsg_tar_walk_stats.fallback says
+ * why).  In mode 1 the stats of tsg_device_tar_stats mean: candidates, the
+ * candidate blocks; off_chain, those not on the chain; block_fetches and
+ * ext_bytes, what the host copied block by block (0 on a layer the GPU
+ * completes); kernel_runs 1; ms_kernel the sum of the pass's kernels.  The pass
+ * allocates about 20 B per 512-B block in HBM (4 % of the layer) while it runs,
+ * plus the records and names; no page-locked memory beyond those two.
+ * Takes effect with the next index call.  TSG_TAR_WALK=gpu (or host) in the
+ * environment sets the initial mode of analyzers made afterwards.  -1: NULL
+ * analyzer or a mode above 1. */
+int tsg_analyzer_set_tar_walk(tsg_analyzer* a, int mode);
+int tsg_analyzer_get_tar_walk(const tsg_analyzer* a, int* mode);
+
+/* How an index was made (versioned, struct_size first).  walk: the mode in force
+ * for the call; fallback: 0, or why the GPU walk's result was discarded and mode
+ * 0 ran (1 a size field, 2 a PAX record, 3 the form of a PAX size, 4 a cap, 5 a
+ * chain block that is no header candidate, 6 truncation, 7 a layer of 2^31 or
+ * more blocks); chain_entries, name_bytes: what the GPU walk handed over;
+ * segments: of the marking pass; device_bytes: the most HBM the pass held at one
+ * time.  ms_candidates, ms_entries, ms_mark, ms_compact: the kernels by stage
+ * (HIP events); ms_copy: the records and names to the host; ms_host: clean,
+ * classify, Required and the index.  All zero but walk for a mode-0 index. */
+typedef struct tsg_tar_walk_stats {
+  uint32_t struct_size, reserved;
+  uint32_t walk, fallback;
+  uint64_t chain_entries, name_bytes, segments, device_bytes;
+  double ms_candidates, ms_entries, ms_mark, ms_compact, ms_copy, ms_host;
+} tsg_tar_walk_stats;
+#define TSG_TAR_WALK_STATS_SIZE_V1 ((uint32_t)(offsetof(tsg_tar_walk_stats, ms_host) + sizeof(double)))
+/* -1: NULL argument or an unknown struct_size. */
+int tsg_tar_index_walk_stats(const tsg_tar_index* ix, tsg_tar_walk_stats* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -277,6 +277,29 @@ int tsg_debug_index_tar_records(struct tsg_analyzer* a, const uint8_t* host_tar,
  * an index, from given IsBinary flags (one per pseudo-file, 2 count + 1): *base,
  * the layer offset of the batch's arena; offs, 2 count + 2 offsets from 0; kinds
  * and binary, 2 count + 1 each.  -1: the range is outside the index. */
+/* The GPU half of the chain walk alone (tsg_analyzer_set_tar_walk mode 1;
+ * trivy_amd/csrc/tarchain.h) on HIP device `device`: dev_tar is a DEVICE pointer,
+ * 16-B aligned; segment_blocks 0 = the default, else a power of two >= 8;
+ * grid_cap != 0 caps every grid.  The outputs are HOST buffers: up to rec_cap
+ * 64-B records into records_out and up to name_cap bytes into names_out (-3 when
+ * either is too small; *n_records and *name_bytes then say what is needed);
+ * stop_out: 4 words -- kind (0 END, 1 INCOMPLETE), reason, offset, extension
+ * headers hopped before an END inside an entry; *candidates_out: the candidate
+ * blocks.  Nothing is handed over for an INCOMPLETE stop (*n_records = 0). */
+int tsg_debug_tar_chain(int device, const void* dev_tar, uint64_t n_bytes, uint32_t segment_blocks, uint32_t grid_cap,
+                        void* records_out, uint64_t rec_cap, uint64_t* n_records, uint8_t* names_out,
+                        uint64_t name_cap, uint64_t* name_bytes, uint64_t* stop_out, uint64_t* candidates_out);
+/* The fallback reason (tsg_tar_walk_stats.fallback) of the analyzer's last index
+ * call in mode 1, also of one that failed and so left no index to ask; -1: NULL. */
+int tsg_debug_tar_walk_last_fallback(const struct tsg_analyzer* a);
+/* The host half of mode 1 without a GPU: n_records 64-B records in walk order,
+ * their name blob and the stop (4 words as above; it must be END) are given
+ * instead of computed.  The index (not submittable) and the stats come back as
+ * from the real call with candidates_given candidates; kernel_runs is 0. */
+int tsg_debug_index_tar_entries(struct tsg_analyzer* a, const void* records, uint64_t n_records, const uint8_t* names,
+                                uint64_t name_bytes, const uint64_t* stop, uint64_t n_bytes,
+                                uint64_t candidates_given, struct tsg_tar_index** out,
+                                struct tsg_device_tar_stats* st);
 int tsg_debug_tar_batch_plan(const struct tsg_tar_index* ix, uint32_t first, uint32_t count, const uint8_t* flags,
                              uint64_t* base, uint64_t* offs, uint8_t* kinds, uint8_t* binary);
 

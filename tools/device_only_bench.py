@@ -74,6 +74,12 @@ def main():
     ap.add_argument("--layer-gb", type=float, default=4.0)
     ap.add_argument("--arena-mb", type=int, default=256, help="--layer: batch size of both modes")
     ap.add_argument("--collectors", type=int, default=6, help="--layer: the host mode's collectors")
+    ap.add_argument("--walk", choices=("host", "gpu", "both"), default="host",
+                    help="--layer: where the resident layer's header chain is walked (SecretAnalyzer.set_tar_walk); "
+                         "both: a block of each per round, interleaved")
+    ap.add_argument("--layer-format", choices=("ustar", "pax"), default="ustar",
+                    help="--layer: pax rewrites the generated layer with a PAX x header (path, mtime) before every entry")
+    ap.add_argument("--index-only", action="store_true", help="--layer: time IndexDevice alone, no scans, no host leg")
     ap.add_argument("--fwd", type=int, default=None)
     ap.add_argument("--fwd-cap", type=int, default=None)
     ap.add_argument("--back", type=int, default=None)
@@ -428,6 +434,37 @@ def resident_leg(args):
             f.write(line + "\n")
 
 
+def pax_layer(layer):
+    """The ustar layer rewritten as BuildKit writes layers: a PAX x header with path and mtime records
+    before every entry.  One pass over the header chain (names without prefix, octal sizes)."""
+    import numpy as np
+    src = layer.tobytes()
+    n = len(src)
+    xh = bytearray(512)
+    xh[:13] = b"PaxHeaders/x\0"
+    xh[100:124] = b"0000644\x000000000\x000000000\x00"
+    xh[136:148] = b"00000000000\x00"
+    xh[156:157] = b"x"
+    xh[257:265] = b"ustar\x0000"
+    xh[148:156] = b" " * 8
+    base = sum(xh)
+    parts, p = [], 0
+    while p + 512 <= n and src[p] != 0:
+        size = int(src[p + 124:p + 135], 8)
+        name = src[p:p + 100].split(b"\0", 1)[0]
+        k = len(name) + 7  # " path=" + name + newline, and the digits of the length itself
+        k += len(str(k + len(str(k))))
+        rec = b"%d path=%s\n30 mtime=1700000000.123456789\n" % (k, name)
+        f = b"%011o\x00" % len(rec)
+        xh[124:136] = f
+        xh[148:156] = b"%06o\x00 " % (base + sum(f))
+        end = p + 512 + (size + 511) // 512 * 512
+        parts += [bytes(xh), rec.ljust(512, b"\0"), src[p:end]]
+        p = end
+    parts.append(src[p:])
+    return np.frombuffer(b"".join(parts), dtype=np.uint8)
+
+
 def layer_leg(args):
     import torch
     import trivy_amd.secret as secret
@@ -436,6 +473,8 @@ def layer_leg(args):
     from trivy_amd.analyzer.secret import Collector
 
     layer = corpus.generate_layer(int(args.layer_gb * 1e9), seed=corpus.SEED)
+    if args.layer_format == "pax":
+        layer = pax_layer(layer)
     n_bytes = int(layer.nbytes)
     dev = torch.device("cuda", 0)
     d_layer = torch.empty(n_bytes + 64, dtype=torch.uint8, device=dev)  # the 64 readable bytes after the layer
@@ -450,11 +489,19 @@ def layer_leg(args):
         sc.set_fetch_mode("windows", back=args.back, fwd=args.fwd, fwd_cap=args.fwd_cap)
     colls = [Collector(an, args.arena_mb << 20, True, gather=True) for _ in range(args.collectors)]
     unregister = secret.HostRegister(layer, mapped=True)  # registered once, outside the timed region
-    modes = ("device", "host")
+    walks = ("host", "gpu") if args.walk == "both" else (args.walk,)
+    dev_modes = tuple("device" if w == "host" else "device-gpu-walk" for w in walks)
+    modes = dev_modes if args.index_only else dev_modes + ("host",)
 
     def step(mode):
         st = {}
-        if mode == "device":
+        if mode != "host" and (mode == "device-gpu-walk" or hasattr(an._L, "tsg_analyzer_set_tar_walk")):
+            an.set_tar_walk("gpu" if mode == "device-gpu-walk" else "host")
+        if mode != "host" and args.index_only:
+            ix = an.IndexDevice(d_layer, n_bytes, stats=st)
+            st["walk"] = ix.walk_stats
+            st["files"] = ix.n
+        elif mode != "host":
             an.AnalyzeLayerDevice(d_layer, n_bytes, arena_bytes=args.arena_mb << 20, depth=args.depth, stats=st,
                                   materialize=False)
         else:
@@ -485,25 +532,31 @@ def layer_leg(args):
             done += n
     finally:
         unregister()
-    findings = {m: res[m][-1]["scan_findings"] for m in modes}
-    assert findings["device"] == findings["host"], findings
+    if not args.index_only:
+        findings = {m: res[m][-1]["scan_findings"] for m in modes}
+        assert len(set(findings.values())) == 1, findings
 
     def med(xs):
         return float(statistics.median(xs))
 
-    claim = max(per["device"]) < min(per["host"])
+    claim = {m: max(per[m]) < min(per["host"]) for m in dev_modes} if not args.index_only else {}
     for m in modes:
         last = res[m][-1]
         out = {"tool": "device_only_bench --layer", "mode": m, "fetch": args.fetch, "resident": args.resident,
+               "format": args.layer_format, "index_only": args.index_only,
                "gb": n_bytes / 1e9, "steps": args.steps, "block": args.block, "depth": args.depth,
                "arena_mb": args.arena_mb, "ms_per_step": med(per[m]), "blocks_ms": per[m],
-               "gbps": n_bytes / 1e6 / med(per[m]), "host_cpus": med(cpus[m]), "findings": int(findings[m]),
-               "device_slowest_below_host_fastest": claim}
-        if m == "device":
+               "gbps": n_bytes / 1e6 / med(per[m]), "host_cpus": med(cpus[m])}
+        if not args.index_only:
+            out["findings"] = int(findings[m])
+        if m != "host":
+            if not args.index_only:
+                out["device_slowest_below_host_fastest"] = claim[m]
             keys = ("ms_kernel", "ms_total", "blocks", "candidates", "off_chain", "block_fetches", "ext_bytes",
                     "kernel_runs", "entries", "regular", "required", "files")
             out["index"] = {k: med([r[k] for r in res[m]]) for k in keys}
             out["index_kernel_gbps"] = n_bytes / 1e6 / out["index"]["ms_kernel"]
+            out["walk"] = {k: med([r["walk"][k] for r in res[m]]) for k in last["walk"] if k != "walk"}
         else:
             out["walk_s"] = med([r["walk_s"] for r in res[m]])
             out["wait_s"] = med([r["wait_s"] for r in res[m]])

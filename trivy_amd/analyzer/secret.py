@@ -86,9 +86,32 @@ class _CDeviceTarStats(c.Structure):  # tsg_device_tar_stats (versioned)
 DEVICE_TAR_STATS_SIZE_V1 = _CDeviceTarStats.ms_total.offset + c.sizeof(c.c_double)
 
 
+class _CTarWalkStats(c.Structure):  # tsg_tar_walk_stats (versioned)
+    _fields_ = [("struct_size", c.c_uint32), ("reserved", c.c_uint32), ("walk", c.c_uint32), ("fallback", c.c_uint32)] + \
+               [(n, c.c_uint64) for n in ("chain_entries", "name_bytes", "segments", "device_bytes")] + \
+               [(n, c.c_double) for n in ("ms_candidates", "ms_entries", "ms_mark", "ms_compact", "ms_copy", "ms_host")]
+
+    def to_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n not in ("struct_size", "reserved", "walk")}
+        d["walk"] = TAR_WALK_MODES[self.walk] if self.walk < len(TAR_WALK_MODES) else self.walk
+        return d
+
+
+TAR_WALK_STATS_SIZE_V1 = _CTarWalkStats.ms_host.offset + c.sizeof(c.c_double)
+TAR_WALK_MODES = ("host", "gpu")  # tsg_analyzer_set_tar_walk
+# tsg_tar_walk_stats.fallback: why the GPU walk's result was discarded and the host walk ran
+TAR_WALK_FALLBACKS = ("", "size field", "PAX record", "PAX size form", "cap", "non-candidate header", "truncation",
+                      "too many blocks")
+
+
 def _declare(L):
     if getattr(L, "_tsg_analyzer_declared", False):
         return
+    if hasattr(L, "tsg_analyzer_set_tar_walk"):  # (absent from an older build of the library: TSG_LIB)
+        L.tsg_analyzer_set_tar_walk.argtypes = [c.c_void_p, c.c_int]
+        L.tsg_analyzer_get_tar_walk.argtypes = [c.c_void_p, c.POINTER(c.c_int)]
+        L.tsg_tar_index_walk_stats.argtypes = [c.c_void_p, c.POINTER(_CTarWalkStats)]
+        L.tsg_debug_tar_walk_last_fallback.argtypes = [c.c_void_p]
     L.tsg_analyzer_classify_device.argtypes = [c.c_void_p, c.POINTER(_CDeviceFiles), c.c_void_p, c.c_void_p,
                                                c.POINTER(_CDeviceClassifyStats)]
     L.tsg_analyzer_submit_device.argtypes = [c.c_void_p, c.POINTER(_CDeviceFiles), c.POINTER(c.c_void_p)]
@@ -387,6 +410,18 @@ class DeviceTarIndex:
             self._an._L.tsg_tar_index_free(self._h)
             self._h = None
 
+    @property
+    def walk_stats(self) -> dict:
+        """How the index was made (tsg_tar_index_walk_stats): the walk mode, the fallback reason (0: none),
+        what the GPU walk handed over and its stage times."""
+        ws = _CTarWalkStats()
+        ws.struct_size = TAR_WALK_STATS_SIZE_V1
+        if not hasattr(self._an._L, "tsg_tar_index_walk_stats"):  # an older build: the host walk, nothing to report
+            return ws.to_dict()
+        if self._an._L.tsg_tar_index_walk_stats(self._h, c.byref(ws)) != 0:
+            raise RuntimeError("tsg_tar_index_walk_stats failed: %s" % _lib.last_error(self._an._L))
+        return ws.to_dict()
+
     def path(self, i: int) -> str:
         pp, pl = c.c_void_p(), c.c_uint64()
         if self._an._L.tsg_tar_index_file(self._h, i, c.byref(pp), c.byref(pl), None, None) != 0:
@@ -669,6 +704,26 @@ class SecretAnalyzer:
                              % (t.numel(), n + 64))
         return t.data_ptr(), n, t
 
+    def set_tar_walk(self, mode):
+        """Where IndexDevice / IndexLayerDevice / AnalyzeLayerDevice walk the header chain
+        (tsg_analyzer_set_tar_walk): "host" (the default: the GPU finds the header candidates, the host walks
+        the chain over their records) or "gpu" (the GPU walks the chain and hands over one record and the
+        name per entry; the same index, and a layer it does not complete is indexed by "host")."""
+        if mode not in TAR_WALK_MODES:
+            raise ValueError("set_tar_walk: mode must be one of %s" % (TAR_WALK_MODES,))
+        if self._L.tsg_analyzer_set_tar_walk(self._h, TAR_WALK_MODES.index(mode)) != 0:
+            raise ValueError("tsg_analyzer_set_tar_walk failed: %s" % _lib.last_error(self._L))
+
+    def tar_walk(self) -> str:
+        m = c.c_int(0)
+        if self._L.tsg_analyzer_get_tar_walk(self._h, c.byref(m)) != 0:
+            raise RuntimeError("tsg_analyzer_get_tar_walk failed: %s" % _lib.last_error(self._L))
+        return TAR_WALK_MODES[m.value]
+
+    def last_tar_fallback(self) -> int:
+        """tsg_tar_walk_stats.fallback of the last "gpu"-mode index call, also of one that raised."""
+        return int(self._L.tsg_debug_tar_walk_last_fallback(self._h))
+
     def IndexDevice(self, dev_layer, nbytes=None, stats=None) -> DeviceTarIndex:
         """The DeviceTarIndex of a layer resident in HBM (tsg_analyzer_index_device_tar)."""
         ptr, n, keep = self._device_layer(dev_layer, nbytes)
@@ -727,6 +782,7 @@ class SecretAnalyzer:
                 inflight.popleft().__del__()
         if stats is not None:
             stats.update(ix.stats)
+            stats["walk"] = ix.walk_stats
             stats.update({"scan_" + k2: v for k2, v in scan_tot.items()})
             stats.update({"files": ix.n, "scan_s": time.perf_counter() - t0})
         return result

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <mutex>
@@ -43,6 +44,10 @@ struct tsg_analyzer {
   // tsg_analyzer_index_device_tar: made on first use
   std::mutex tar_index_mu;
   tsg::TarIndexPool* tar_index = nullptr;
+  // tsg_analyzer_set_tar_walk: 0 the chain walk on the host over the candidate
+  // records, 1 on the GPU (TSG_TAR_WALK=gpu at creation).  Read once per index call.
+  std::atomic<int> tar_walk{0};
+  std::atomic<uint32_t> tar_fallback_last{0};  // tsg_debug_tar_walk_last_fallback: the last mode-1 call's
   ~tsg_analyzer() {
     tsg::FreeTarWalkCache(walk);
     tsg::FreeClassifyPool(classify);

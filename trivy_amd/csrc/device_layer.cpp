@@ -4,7 +4,10 @@
 // the plan of a batch whose arena is the layer itself, and the kinds are the
 // host half (tar_index_host.h, plain C++); this file is the glue: argument
 // checks, the pooled stream and buffers of an index pass, the copies of single
-// blocks and ranges the walk asks for, and the pending of a submit.
+// blocks and ranges the walk asks for, and the pending of a submit.  In walk
+// mode 1 (tsg_analyzer_set_tar_walk) the GPU walks the chain as well
+// (tarchain.hip) and the host half starts from its entry records
+// (IndexTarEntries); a layer that walk does not complete takes the path above.
 #include <hip/hip_runtime_api.h>
 #include <pthread.h>
 
@@ -29,6 +32,7 @@ struct tsg_tar_index {
   const uint8_t* dev_tar = nullptr;  // NULL: made from given records (tsg_debug_index_tar_records)
   uint64_t n_bytes = 0;
   tsg::TarIndexData d;
+  tsg_tar_walk_stats ws{};  // tsg_tar_index_walk_stats
 };
 
 namespace tsg {
@@ -44,7 +48,21 @@ struct TarIndexCtx {
   uint8_t* h_rec = nullptr;      // pinned
   uint32_t* h_count = nullptr;   // pinned
   uint64_t cap_rec = 0, cap_h = 0;  // records
+  // the GPU walk (tsg_analyzer_set_tar_walk mode 1): its stage events, its work buffer, the entry
+  // records and names on the device and page-locked on the host, the head the host reads
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  uint8_t* d_work = nullptr;
+  uint8_t* d_out = nullptr;
+  uint8_t* h_out = nullptr;        // pinned
+  TarChainHead* h_head = nullptr;  // pinned
+  uint64_t cap_work = 0, cap_out = 0, cap_hout = 0;  // bytes
   ~TarIndexCtx() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (d_work) (void)hipFree(d_work);
+    if (d_out) (void)hipFree(d_out);
+    if (h_out) (void)hipHostFree(h_out);
+    if (h_head) (void)hipHostFree(h_head);
     if (d_rec) (void)hipFree(d_rec);
     if (d_count) (void)hipFree(d_count);
     if (h_rec) (void)hipHostFree(h_rec);
@@ -103,6 +121,22 @@ void GiveCtx(tsg_analyzer* a, std::unique_ptr<TarIndexCtx> c) {
     c->h_rec = nullptr;
     c->cap_h = 0;
   }
+  constexpr uint64_t kKeepBytes = uint64_t(16) << 20;
+  if (c->cap_work > kKeepBytes) {
+    (void)hipFree(c->d_work);
+    c->d_work = nullptr;
+    c->cap_work = 0;
+  }
+  if (c->cap_out > kKeepBytes) {
+    (void)hipFree(c->d_out);
+    c->d_out = nullptr;
+    c->cap_out = 0;
+  }
+  if (c->cap_hout > kKeepBytes) {
+    (void)hipHostFree(c->h_out);
+    c->h_out = nullptr;
+    c->cap_hout = 0;
+  }
   std::lock_guard<std::mutex> g(a->tar_index->mu);
   if (a->tar_index->free.size() < 2) a->tar_index->free.push_back(std::move(c));  // (else freed here)
 }
@@ -128,15 +162,140 @@ bool StatsSizeOk(const tsg_device_tar_stats* st, const char* who) {
   return false;
 }
 
+// Required and the per-entry path work of an index, 1,024 entries a task on the host pool.
+auto ChunkedPar() {
+  return [](size_t n, const std::function<void(size_t)>& fn) {
+    const size_t blocks = (n + 1023) / 1024;
+    ParallelFor(blocks, 16, [&](size_t b) {
+      for (size_t i = b * 1024; i < std::min(n, (b + 1) * 1024); i++) fn(i);
+    });
+  };
+}
+// The same for the host half of the GPU walk, whose first pass has one item per 64 entries: at most
+// 1,024 items a task, and at least 128 tasks where there are that many items.
+auto EntriesPar() {
+  return [](size_t n, const std::function<void(size_t)>& fn) {
+    const size_t per = std::max<size_t>(1, std::min<size_t>(1024, n / 128));
+    const size_t blocks = (n + per - 1) / per;
+    ParallelFor(blocks, 16, [&](size_t b) {
+      for (size_t i = b * per; i < std::min(n, (b + 1) * per); i++) fn(i);
+    });
+  };
+}
+
 int WalkRecords(tsg_analyzer* a, const IndexedTarSrc& src, uint64_t n_bytes, TarIndexData* d) {
   return WalkTarIndex(
       src, n_bytes, [a](const char* p, uint64_t len, int64_t size) { return RequiredPath(a, p, len, size); }, d,
-      [](size_t n, const std::function<void(size_t)>& fn) {
-        const size_t blocks = (n + 1023) / 1024;
-        ParallelFor(blocks, 16, [&](size_t b) {
-          for (size_t i = b * 1024; i < std::min(n, (b + 1) * 1024); i++) fn(i);
-        });
-      });
+      ChunkedPar());
+}
+
+// ---- the chain walk on the GPU (tarchain.h) ----------------------------------
+// The host half over given records: the index, and the V1 stats of mode 1.
+int EntriesToIndex(tsg_analyzer* a, const tsg_tar_entry_rec* recs, uint64_t n, const uint8_t* names, uint64_t name_bytes,
+                   const tsg_tar_stop& stop, uint64_t n_bytes, uint64_t candidates, TarIndexData* d,
+                   tsg_device_tar_stats* st, double* ms = nullptr) {
+  if (IndexTarEntries(
+          recs, n, names, name_bytes,
+          [a](const char* p, uint64_t len, int64_t size) { return RequiredPath(a, p, len, size); }, d, EntriesPar(),
+          ms) < 0)
+    return -1;
+  if (st) {
+    uint64_t on_chain = stop.ext_visited;  // every header of every entry, as the host walk's records visited
+    for (uint64_t i = 0; i < n; i++) on_chain += uint64_t(recs[i].n_ext) + 1;
+    st->tar = d->tar;
+    st->blocks = n_bytes / 512;
+    st->candidates = candidates;
+    st->off_chain = candidates > on_chain ? candidates - on_chain : 0;
+    st->block_fetches = 0;
+    st->ext_bytes = 0;
+  }
+  return 0;
+}
+
+bool Grow(uint8_t** p, uint64_t* cap, uint64_t want, bool pinned, hipError_t* e) {
+  if (*cap >= want) return true;
+  if (*p) (void)(pinned ? hipHostFree(*p) : hipFree(*p));
+  *p = nullptr;
+  *cap = 0;
+  *e = pinned ? hipHostMalloc(reinterpret_cast<void**>(p), want, hipHostMallocDefault)
+              : hipMalloc(reinterpret_cast<void**>(p), want);
+  if (*e != hipSuccess) return false;
+  *cap = want;
+  return true;
+}
+
+// The GPU half on the context's stream: 0 with *recs / *names (in c->h_out) and
+// *head filled; 1 the chain is INCOMPLETE (or the pass does not take the layer):
+// ws->fallback says why; -2 a HIP error, its text set.  n_bytes >= 512.
+int ChainOnGpu(TarIndexCtx* c, const uint8_t* dev_tar, uint64_t n_bytes, uint32_t segment_blocks, uint32_t grid_cap,
+               const std::string& who, TarChainHead* head, const tsg_tar_entry_rec** recs, const uint8_t** names,
+               tsg_tar_walk_stats* ws) {
+  TarChainLayout L;
+  if (!TarChainPlan(n_bytes, segment_blocks, &L)) {
+    if (segment_blocks) {
+      SetError(who + ": segment_blocks must be a power of two from 8 to 8192");
+      return -2;
+    }
+    ws->fallback = kTarTooLarge;
+    return 1;
+  }
+  hipError_t e = hipSuccess;
+  auto ok = [&](hipError_t r) {
+    if (e == hipSuccess) e = r;
+    return e == hipSuccess;
+  };
+  for (hipEvent_t& v : c->ev)
+    if (!v) ok(hipEventCreate(&v));
+  if (ok(e) && !c->h_head) ok(hipHostMalloc(reinterpret_cast<void**>(&c->h_head), sizeof(TarChainHead), hipHostMallocDefault));
+  if (ok(e)) Grow(&c->d_work, &c->cap_work, L.bytes, false, &e);
+  ws->segments = L.n_segments;
+  ws->device_bytes = L.bytes;
+  uint64_t rec_bytes = 0, out_bytes = 0;
+  bool incomplete = false;
+  if (ok(e) && ok(TarChainWalk(dev_tar, n_bytes, L, c->d_work, grid_cap, c->s, c->ev)) &&
+      ok(hipMemcpyAsync(c->h_head, c->d_work + L.head, sizeof(TarChainHead), hipMemcpyDeviceToHost, c->s)) &&
+      ok(hipStreamSynchronize(c->s))) {
+    *head = *c->h_head;
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) ws->ms_candidates = ms;
+    if (hipEventElapsedTime(&ms, c->ev[1], c->ev[2]) == hipSuccess) ws->ms_entries = ms;
+    if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) ws->ms_mark = ms;
+    incomplete = head->stop.kind != kTarStopEnd;
+    if (incomplete) ws->fallback = head->stop.reason ? head->stop.reason : uint32_t(kTarNotCandidate);
+    rec_bytes = (head->entries * sizeof(tsg_tar_entry_rec) + 255) & ~uint64_t(255);
+    out_bytes = rec_bytes + head->name_bytes + 256;
+  }
+  if (ok(e) && !incomplete) {
+    ws->chain_entries = head->entries;
+    ws->name_bytes = head->name_bytes;
+    ws->device_bytes = L.bytes + out_bytes;
+    // (ev[0] again: the allocations above the kernel are not its time)
+    if (Grow(&c->d_out, &c->cap_out, out_bytes, false, &e) && Grow(&c->h_out, &c->cap_hout, out_bytes, true, &e) &&
+        ok(hipEventRecord(c->ev[0], c->s)) &&
+        ok(TarChainCompact(dev_tar, n_bytes, L, c->d_work, head->entries, head->name_bytes, c->d_out,
+                           c->d_out + rec_bytes, grid_cap, c->s)) &&
+        ok(hipEventRecord(c->ev[4], c->s)) && ok(hipStreamSynchronize(c->s))) {
+      float ms = 0;
+      if (hipEventElapsedTime(&ms, c->ev[0], c->ev[4]) == hipSuccess) ws->ms_compact = ms;
+      const double t1 = NowMs();
+      // one copy of the records, one of the names
+      if ((head->entries == 0 || ok(hipMemcpyAsync(c->h_out, c->d_out, head->entries * sizeof(tsg_tar_entry_rec),
+                                                   hipMemcpyDeviceToHost, c->s))) &&
+          (head->name_bytes == 0 || ok(hipMemcpyAsync(c->h_out + rec_bytes, c->d_out + rec_bytes, head->name_bytes,
+                                                      hipMemcpyDeviceToHost, c->s))))
+        ok(hipStreamSynchronize(c->s));
+      ws->ms_copy = NowMs() - t1;
+    }
+  }
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(c->s);  // nothing of a failed pass is left queued on a pooled stream
+    SetError(who + ": " + hipGetErrorString(e));
+    return -2;
+  }
+  if (incomplete) return 1;
+  *recs = reinterpret_cast<const tsg_tar_entry_rec*>(c->h_out);
+  *names = c->h_out + rec_bytes;
+  return 0;
 }
 
 }  // namespace
@@ -189,6 +348,54 @@ int tsg_analyzer_index_device_tar(tsg_analyzer* a, const tsg_device_tar* t, tsg_
     if (e == hipSuccess) e = r;
     return e == hipSuccess;
   };
+  tsg_tar_walk_stats ws{};
+  ws.walk = uint32_t(a->tar_walk.load());
+  if (ws.walk == 1) {
+    // The chain walk on the GPU.  A layer it does not complete falls through to the host walk below,
+    // from scratch: that path alone words what is wrong with a malformed archive.
+    std::unique_ptr<tsg_tar_index> ix(new tsg_tar_index());
+    ix->dev_tar = dev_tar;
+    ix->n_bytes = n_bytes;
+    TarChainHead head{};
+    const tsg_tar_entry_rec* recs = nullptr;
+    const uint8_t* names = nullptr;
+    int rc = 0;
+    if (n_bytes < 512) {  // no complete block: the empty archive, or a truncated header
+      rc = n_bytes ? 1 : 0;
+      if (rc) ws.fallback = kTarTruncated;
+    } else {
+      rc = ChainOnGpu(c.get(), dev_tar, n_bytes, 0, 0, who, &head, &recs, &names, &ws);
+    }
+    a->tar_fallback_last.store(ws.fallback);
+    if (rc < 0) {
+      GiveCtx(a, std::move(c));
+      return -2;
+    }
+    if (rc == 0) {
+      const double th = NowMs();
+      tsg_device_tar_stats tmp{};
+      double hm[3] = {0, 0, 0};
+      rc = EntriesToIndex(a, recs, head.entries, names, head.name_bytes, head.stop, n_bytes, head.candidates, &ix->d,
+                          st ? st : &tmp, hm);
+      ws.ms_host = NowMs() - th;
+      GiveCtx(a, std::move(c));
+      if (rc < 0) return -2;  // (records that contradict the name blob: the layer changed under the pass)
+      if (st) {
+        st->kernel_runs = 1;
+        st->ms_kernel = ws.ms_candidates + ws.ms_entries + ws.ms_mark + ws.ms_compact;
+        st->ms_total = NowMs() - t0;
+      }
+      if (std::getenv("TSG_WALK_DEBUG"))
+        std::fprintf(stderr, "device tar index (gpu walk): candidates %.2f ms, entries %.2f ms, mark %.2f ms, compact %.2f ms, "
+                     "copy %.2f ms, host %.2f ms (classify %.1f, join %.1f, Required + index %.1f), total %.1f ms (%llu entries)\n",
+                     ws.ms_candidates, ws.ms_entries, ws.ms_mark, ws.ms_compact, ws.ms_copy, ws.ms_host, hm[0], hm[1],
+                     hm[2], NowMs() - t0,
+                     static_cast<unsigned long long>(head.entries));
+      ix->ws = ws;
+      *out = ix.release();
+      return 0;
+    }
+  }
   uint64_t capacity = g_tar_capacity.load() ? g_tar_capacity.load() : n_bytes / 4096 + 1024;
   uint64_t count = 0, runs = 0;
   double ms_kernel = 0;
@@ -251,7 +458,46 @@ int tsg_analyzer_index_device_tar(tsg_analyzer* a, const tsg_device_tar* t, tsg_
                  static_cast<unsigned long long>(count), t_sort - t_back, NowMs() - t_sort);
   if (rc < 0) return copy_failed ? -2 : -3;
   FillStats(st, ix->d, src, n_bytes, count, runs, ms_kernel, NowMs() - t0);
+  ix->ws = ws;
   *out = ix.release();
+  return 0;
+}
+
+int tsg_analyzer_set_tar_walk(tsg_analyzer* a, int mode) {
+  if (!a) {
+    tsg::SetError("tsg_analyzer_set_tar_walk: NULL analyzer");
+    return -1;
+  }
+  if (mode != 0 && mode != 1) {
+    tsg::SetError("tsg_analyzer_set_tar_walk: mode " + std::to_string(mode) + " is not 0 (host) or 1 (gpu)");
+    return -1;
+  }
+  a->tar_walk.store(mode);
+  return 0;
+}
+
+int tsg_analyzer_get_tar_walk(const tsg_analyzer* a, int* mode) {
+  if (!a || !mode) {
+    tsg::SetError("tsg_analyzer_get_tar_walk: NULL argument");
+    return -1;
+  }
+  *mode = a->tar_walk.load();
+  return 0;
+}
+
+int tsg_tar_index_walk_stats(const tsg_tar_index* ix, tsg_tar_walk_stats* out) {
+  if (!ix || !out) {
+    tsg::SetError("tsg_tar_index_walk_stats: NULL argument");
+    return -1;
+  }
+  if (out->struct_size != TSG_TAR_WALK_STATS_SIZE_V1) {
+    tsg::SetError("tsg_tar_index_walk_stats: tsg_tar_walk_stats.struct_size " + std::to_string(out->struct_size) +
+                  " is not a size this library knows (v1 = " + std::to_string(TSG_TAR_WALK_STATS_SIZE_V1) + ")");
+    return -1;
+  }
+  *out = ix->ws;
+  out->struct_size = TSG_TAR_WALK_STATS_SIZE_V1;
+  out->reserved = 0;
   return 0;
 }
 
@@ -417,6 +663,105 @@ int tsg_debug_index_tar_records(tsg_analyzer* a, const uint8_t* host_tar, uint64
   ix->n_bytes = n_bytes;
   if (WalkRecords(a, src, n_bytes, &ix->d) < 0) return src.failed() ? -2 : -3;
   FillStats(st, ix->d, src, n_bytes, n_records, 0, 0, NowMs() - t0);
+  *out = ix.release();
+  return 0;
+}
+
+int tsg_debug_tar_chain(int device, const void* dev_tar, uint64_t n_bytes, uint32_t segment_blocks, uint32_t grid_cap,
+                        void* records_out, uint64_t rec_cap, uint64_t* n_records, uint8_t* names_out,
+                        uint64_t name_cap, uint64_t* name_bytes, uint64_t* stop_out, uint64_t* candidates_out) {
+  using namespace tsg;
+  const std::string who = "tsg_debug_tar_chain";
+  if (!n_records || !name_bytes || !stop_out || !candidates_out || (n_bytes >= 512 && !dev_tar) ||
+      (rec_cap && !records_out) || (name_cap && !names_out) || reinterpret_cast<uintptr_t>(dev_tar) % 16 != 0) {
+    SetError(who + ": NULL or misaligned pointer");
+    return -2;
+  }
+  *n_records = *name_bytes = *candidates_out = 0;
+  stop_out[0] = stop_out[1] = stop_out[2] = stop_out[3] = 0;
+  if (n_bytes < 512) {  // no complete block: END at 0, or a truncated header
+    if (n_bytes) {
+      stop_out[0] = kTarStopIncomplete;
+      stop_out[1] = kTarTruncated;
+    }
+    return 0;
+  }
+  TarIndexCtx c;
+  hipError_t e = hipSetDevice(device);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&c.s, hipStreamNonBlocking);
+  if (e != hipSuccess) {
+    SetError(who + ": " + hipGetErrorString(e));
+    return -2;
+  }
+  TarChainHead head{};
+  const tsg_tar_entry_rec* recs = nullptr;
+  const uint8_t* names = nullptr;
+  tsg_tar_walk_stats ws{};
+  const int rc = ChainOnGpu(&c, static_cast<const uint8_t*>(dev_tar), n_bytes, segment_blocks, grid_cap, who, &head, &recs,
+                            &names, &ws);
+  if (rc < 0) return -2;
+  if (rc == 1 && ws.fallback == kTarTooLarge) {
+    SetError(who + ": the layer has too many blocks");
+    return -2;
+  }
+  stop_out[0] = head.stop.kind;
+  stop_out[1] = head.stop.reason;
+  stop_out[2] = head.stop.offset;
+  stop_out[3] = head.stop.ext_visited;
+  *candidates_out = head.candidates;
+  if (rc == 1) return 0;
+  *n_records = head.entries;
+  *name_bytes = head.name_bytes;
+  if (head.entries > rec_cap || head.name_bytes > name_cap) {
+    SetError(who + ": the output buffers are too small");
+    return -3;
+  }
+  if (head.entries) std::memcpy(records_out, recs, size_t(head.entries) * sizeof(tsg_tar_entry_rec));
+  if (head.name_bytes) std::memcpy(names_out, names, size_t(head.name_bytes));
+  return 0;
+}
+
+int tsg_debug_tar_walk_last_fallback(const tsg_analyzer* a) { return a ? int(a->tar_fallback_last.load()) : -1; }
+
+int tsg_debug_index_tar_entries(tsg_analyzer* a, const void* records, uint64_t n_records, const uint8_t* names,
+                                uint64_t name_bytes, const uint64_t* stop, uint64_t n_bytes, uint64_t candidates_given,
+                                tsg_tar_index** out, tsg_device_tar_stats* st) {
+  using namespace tsg;
+  const char* who = "tsg_debug_index_tar_entries";
+  if (out) *out = nullptr;
+  if (!a || !out || !stop || (n_records && !records) || (name_bytes && !names)) {
+    SetError(std::string(who) + ": NULL argument");
+    return -1;
+  }
+  if (!StatsSizeOk(st, who)) return -1;
+  if (stop[0] != kTarStopEnd) {
+    SetError(std::string(who) + ": the stop is not END (an INCOMPLETE chain is walked by the host walk)");
+    return -1;
+  }
+  const double t0 = NowMs();
+  tsg_tar_stop sp{};
+  sp.kind = uint32_t(stop[0]);
+  sp.reason = uint32_t(stop[1]);
+  sp.offset = stop[2];
+  sp.ext_visited = stop[3];
+  std::unique_ptr<tsg_tar_index> ix(new tsg_tar_index());
+  ix->n_bytes = n_bytes;
+  tsg_device_tar_stats tmp{};
+  double hm[3] = {0, 0, 0};
+  if (EntriesToIndex(a, static_cast<const tsg_tar_entry_rec*>(records), n_records, names, name_bytes, sp, n_bytes,
+                     candidates_given, &ix->d, st ? st : &tmp, hm) < 0)
+    return -1;
+  if (std::getenv("TSG_WALK_DEBUG"))
+    std::fprintf(stderr, "tar entries host half: classify %.1f ms, join %.1f ms, Required + index %.1f ms\n", hm[0], hm[1],
+                 hm[2]);
+  if (st) {
+    st->kernel_runs = 0;
+    st->ms_kernel = 0;
+    st->ms_total = NowMs() - t0;
+  }
+  ix->ws.walk = 1;
+  ix->ws.chain_entries = n_records;
+  ix->ws.name_bytes = name_bytes;
   *out = ix.release();
   return 0;
 }

@@ -17,6 +17,7 @@
 #include <immintrin.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -28,6 +29,7 @@
 #include <string_view>
 #include <vector>
 
+#include "tarchain.h"
 #include "tsg_analyzer.h"
 
 namespace tsg {
@@ -344,13 +346,11 @@ const uint8_t* ResolveT(const Src& src, TarEntry* e) {
 
 // LayerTar.Walk's per-entry path logic (walker/tar.go:41-84): clean the name,
 // classify whiteout / opaque markers.  `tar`: the layer buffer of a kView
-// source (what TarEntry::path reads), else NULL.
-template <class Src>
-void ClassifyT(const Src& src, const uint8_t* tar, TarEntry* e) {
-  const uint8_t* h = ResolveT(src, e);
-  if (!h) return;
+// source (what TarEntry::path reads), else NULL.  ClassifyPath is the part after
+// the name is resolved (reg_a: the header's typeflag is TypeRegA).
+inline void ClassifyPath(bool reg_a, const uint8_t* tar, TarEntry* e) {
   std::string_view fp = e->path(tar);
-  if (h[156] == '\0' && !fp.empty() && fp.back() == '/') e->what = 0;  // TypeRegA dir
+  if (reg_a && !fp.empty() && fp.back() == '/') e->what = 0;  // TypeRegA dir
   if (!GoPathIsClean(fp.data(), fp.size())) {
     e->own(GoPathClean(std::string(fp)));
     fp = *e->fp_own;
@@ -370,6 +370,12 @@ void ClassifyT(const Src& src, const uint8_t* tar, TarEntry* e) {
   const std::string_view file_name = fp.substr(slash == std::string_view::npos ? 0 : slash + 1);
   if (file_name == ".wh..wh..opq") e->what = 2;
   else if (file_name.substr(0, 4) == ".wh.") e->what = 1;
+}
+template <class Src>
+void ClassifyT(const Src& src, const uint8_t* tar, TarEntry* e) {
+  const uint8_t* h = ResolveT(src, e);
+  if (!h) return;
+  ClassifyPath(h[156] == '\0', tar, e);
 }
 
 // ---- a layer resident in HBM ------------------------------------------------
@@ -479,6 +485,25 @@ struct SerialFor {
     for (size_t i = 0; i < n; i++) fn(i);
   }
 };
+// Required over the regular files through par, then the index of the accepted ones, in order.
+template <class Req, class Par>
+void FinishTarIndex(const std::string& pool, const std::vector<TarIndexFile>& regular, Req&& required,
+                    TarIndexData* out, Par&& par) {
+  std::vector<uint8_t> keep(regular.size(), 0);
+  par(regular.size(), [&](size_t i) {
+    const TarIndexFile& f = regular[i];
+    keep[i] = required(pool.data() + f.path_off, f.path_len, int64_t(f.size)) ? 1 : 0;
+  });
+  for (size_t i = 0; i < regular.size(); i++) {
+    if (!keep[i]) continue;
+    TarIndexFile f = regular[i];
+    const uint64_t at = out->pool.size();
+    out->pool.append(pool, size_t(f.path_off), size_t(f.path_len) + 1);
+    f.path_off = at;
+    out->files.push_back(f);
+    out->tar.required++;
+  }
+}
 template <class Src, class Req, class Par = SerialFor>
 int WalkTarIndex(const Src& src, uint64_t n, Req&& required, TarIndexData* out, Par&& par = Par()) {
   std::string pool;
@@ -507,19 +532,94 @@ int WalkTarIndex(const Src& src, uint64_t n, Req&& required, TarIndexData* out, 
     }
     p = e.next;
   }
-  std::vector<uint8_t> keep(regular.size(), 0);
-  par(regular.size(), [&](size_t i) {
-    const TarIndexFile& f = regular[i];
-    keep[i] = required(pool.data() + f.path_off, f.path_len, int64_t(f.size)) ? 1 : 0;
+  FinishTarIndex(pool, regular, required, out, par);
+  return 0;
+}
+
+// The host half of the walk the GPU made (tarchain.h): n records in walk order and
+// their raw names.  What is left of the walk per entry -- the TypeRegA directory
+// test, path.Clean, the leading-slash strip, whiteouts and opaque dirs
+// (ClassifyPath) -- runs through par in chunks of kTarEntryChunk entries, each
+// with its own path pool and counts (a name that is clean stays a view of the
+// name blob until it is copied there: no allocation per entry); the chunks are
+// then joined in order, Required runs through par as in WalkTarIndex, and the
+// index equals WalkTarIndex's.  ms (optional): classify, join, Required + index.
+// -1: a record points outside the name blob (error set).
+constexpr size_t kTarEntryChunk = 64;
+template <class Req, class Par = SerialFor>
+int IndexTarEntries(const tsg_tar_entry_rec* recs, uint64_t n, const uint8_t* names, uint64_t name_bytes,
+                    Req&& required, TarIndexData* out, Par&& par = Par(), double* ms = nullptr) {
+  auto now = [] {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  };
+  const double t0 = now();
+  struct Chunk {
+    std::string pool;
+    std::vector<TarIndexFile> regular;  // path_off relative to pool
+    uint64_t whiteouts = 0, opaque_dirs = 0;
+    bool bad = false;
+  };
+  const size_t n_chunks = (size_t(n) + kTarEntryChunk - 1) / kTarEntryChunk;
+  std::vector<Chunk> chunks(n_chunks);
+  par(n_chunks, [&](size_t c) {
+    Chunk& k = chunks[c];
+    const size_t i1 = std::min(size_t(n), (c + 1) * kTarEntryChunk);
+    for (size_t i = c * kTarEntryChunk; i < i1; i++) {
+      const tsg_tar_entry_rec& r = recs[i];
+      if (r.name_off > name_bytes || r.name_len > name_bytes - r.name_off) {
+        k.bad = true;
+        return;
+      }
+      TarEntry e;
+      e.what = (r.typeflag == '0' || r.typeflag == '\0') ? 3 : 0;
+      e.fp_off = r.name_off;  // a view of the name blob, which stands in for the layer buffer of a kView source
+      e.fp_len = r.name_len;
+      ClassifyPath(r.typeflag == '\0', names, &e);
+      k.whiteouts += e.what == 1;
+      k.opaque_dirs += e.what == 2;
+      if (e.what == 3) {
+        const std::string_view fp = e.path(names);
+        k.regular.push_back({uint64_t(k.pool.size()), uint64_t(fp.size()), r.start, r.data, r.size});
+        k.pool.append(fp.data(), fp.size());
+        k.pool.push_back('\0');
+      }
+    }
   });
-  for (size_t i = 0; i < regular.size(); i++) {
-    if (!keep[i]) continue;
-    TarIndexFile f = regular[i];
-    const uint64_t at = out->pool.size();
-    out->pool.append(pool, size_t(f.path_off), size_t(f.path_len) + 1);
-    f.path_off = at;
-    out->files.push_back(f);
-    out->tar.required++;
+  const double t1 = now();
+  // where each chunk's paths and files go in the joined pool and list
+  std::vector<size_t> pool_at(n_chunks + 1, 0), reg_at(n_chunks + 1, 0);
+  for (size_t c = 0; c < n_chunks; c++) {
+    const Chunk& k = chunks[c];
+    if (k.bad) {
+      SetError("tar entries: a record has its name outside the name blob");
+      return -1;
+    }
+    pool_at[c + 1] = pool_at[c] + k.pool.size();
+    reg_at[c + 1] = reg_at[c] + k.regular.size();
+    out->tar.whiteouts += k.whiteouts;
+    out->tar.opaque_dirs += k.opaque_dirs;
+  }
+  out->tar.entries += n;
+  out->tar.regular += reg_at[n_chunks];
+  std::string pool(pool_at[n_chunks], '\0');
+  std::vector<TarIndexFile> regular(reg_at[n_chunks]);
+  par(n_chunks, [&](size_t c) {
+    Chunk& k = chunks[c];
+    if (!k.pool.empty()) std::memcpy(&pool[pool_at[c]], k.pool.data(), k.pool.size());
+    for (size_t j = 0; j < k.regular.size(); j++) {
+      TarIndexFile f = k.regular[j];
+      f.path_off += pool_at[c];
+      regular[reg_at[c] + j] = f;
+    }
+    k = Chunk();
+  });
+  chunks.clear();
+  const double t2 = now();
+  FinishTarIndex(pool, regular, required, out, par);
+  if (ms) {
+    ms[0] = t1 - t0;
+    ms[1] = t2 - t1;
+    ms[2] = now() - t2;
   }
   return 0;
 }

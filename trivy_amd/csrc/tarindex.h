@@ -2,11 +2,15 @@
 // over the layer's complete 512-B blocks that appends every block which parses
 // as a tar header -- analyzer.cpp's ChecksumOK(block) && !AllZero(block) -- to a
 // record buffer.  The chain walk over those records stays on the host
-// (tar_index_host.h).
+// (tar_index_host.h) -- or, in the analyzer's walk mode 1, the same verdict is
+// kept as one bit per block and the chain is walked on the GPU too
+// (tarchain.hip; declared below).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
+
+#include "tarchain.h"
 
 namespace tsg {
 
@@ -21,5 +25,45 @@ constexpr uint64_t kTarRecordBytes = 528;  // u64 block index, 8 B of zero paddi
 // over everything); otherwise the grid is a function of n_bytes alone.
 hipError_t TarHeaders(const uint8_t* dev_tar, uint64_t n_bytes, uint8_t* d_records, uint32_t capacity,
                       uint32_t* d_count, uint32_t grid_cap, hipStream_t s);
+
+// The same verdict as one bit per block: word g of d_bitmap (8-B aligned,
+// (n_bytes / 512 + 63) / 64 words, all written) holds blocks 64 g .. 64 g + 63,
+// bit i block 64 g + i.  No counter, no capacity.
+hipError_t TarBitmap(const uint8_t* dev_tar, uint64_t n_bytes, uint64_t* d_bitmap, uint32_t grid_cap, hipStream_t s);
+
+// ---- the chain walk on the GPU (tarchain.hip; the contract: tarchain.h) ----
+// What the pass leaves at the start of its work buffer for the host to copy.
+struct TarChainHead {
+  tsg_tar_stop stop;
+  uint64_t entries, name_bytes;  // on the chain, up to the stop
+  uint64_t candidates;
+  uint64_t pad;
+};
+static_assert(sizeof(TarChainHead) == 64, "");
+
+// The one device buffer of a pass over n_blocks blocks in segments of `segment`
+// blocks: byte offsets of its parts (256-B aligned) and its size.
+struct TarChainLayout {
+  uint64_t n_blocks = 0, n_segments = 0;
+  uint32_t segment = 0;
+  uint64_t head = 0, cand = 0, chain = 0, seg_entry = 0, succ = 0, nlen = 0, rank = 0, noff = 0, temp = 0;
+  uint64_t temp_bytes = 0, bytes = 0;
+};
+// segment_blocks: 0 = kTarDefaultSegment, else a power of two >= kTarMinSegment whose
+// words fit a workgroup's LDS; false: it is neither.  n_bytes / 512 < kTarMaxBlocks - 2.
+bool TarChainPlan(uint64_t n_bytes, uint32_t segment_blocks, TarChainLayout* L);
+
+// Stage times are taken between these events, recorded on s when ev != NULL:
+// ev[0] start, [1] after the bitmap, [2] after the entries, [3] after the marking
+// (exits, stitch, marks, ranks, totals).
+// After it the head (d_work + L.head) is complete.  n_bytes >= 512.
+hipError_t TarChainWalk(const uint8_t* dev_tar, uint64_t n_bytes, const TarChainLayout& L, uint8_t* d_work,
+                        uint32_t grid_cap, hipStream_t s, hipEvent_t* ev);
+// The records (64 B each, 16-B aligned, n_entries = head.entries of them) and the
+// name blob (name_bytes = head.name_bytes) of the entries TarChainWalk marked, in
+// walk order; nothing is written past either.
+hipError_t TarChainCompact(const uint8_t* dev_tar, uint64_t n_bytes, const TarChainLayout& L, const uint8_t* d_work,
+                           uint64_t n_entries, uint64_t name_bytes, uint8_t* d_records, uint8_t* d_names,
+                           uint32_t grid_cap, hipStream_t s);
 
 }  // namespace tsg

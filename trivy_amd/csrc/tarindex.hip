@@ -80,6 +80,53 @@ __device__ __forceinline__ uint32_t row_ror_add(uint32_t p) {  // p + (p rotated
   return p + uint32_t(__builtin_amdgcn_update_dpp(0, int(p), kCtrl, 0xF, 0xF, false));
 }
 
+// The verdict on the 64 blocks from g0 on, one bit each (bit i: block g0 + i is a candidate), wave-uniform:
+// what tar_headers_kernel turns into records and tar_bitmap_kernel stores as it is.
+__device__ __forceinline__ uint64_t group_mask(const uint8_t* __restrict__ tar, uint64_t n_blocks, uint64_t g0,
+                                               uint32_t l, uint32_t half) {
+  uint64_t mask = 0;  // bit i: block g0 + i is a candidate (wave-uniform)
+  for (uint32_t k = 0; k < kGroupTiles; k++) {
+    const uint64_t b0 = g0 + k * kTileBlocks;
+    if (b0 >= n_blocks) break;  // (wave-uniform)
+    uint4 v[4];
+#pragma unroll
+    for (uint32_t u = 0; u < 4; u++) {
+      // no branch around a load (it would wait for each before the next is issued): a block past the
+      // end reads the last block instead (n_blocks >= 1 here) and is no candidate, whatever it holds
+      const uint64_t blk = min(b0 + 2u * u + half, n_blocks - 1);
+      v[u] = *reinterpret_cast<const uint4*>(tar + blk * 512u + l * 16u);  // (ends at or before 512 n_blocks)
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < 4; u++) {
+      uint32_t su = __builtin_amdgcn_sad_u8(v[u].x, 0u, __builtin_amdgcn_sad_u8(v[u].w, 0u, 0u));
+      uint32_t hb = high_bytes(v[u].x) + high_bytes(v[u].w);
+      int32_t want = kNoWant;
+      if (l == 9) {  // bytes 148..155 are this lane's y and z: eight spaces in the sums
+        su += 8u * 0x20u;
+        want = parse_field(uint64_t(v[u].y) | (uint64_t(v[u].z) << 32));
+      } else {
+        su = __builtin_amdgcn_sad_u8(v[u].y, 0u, __builtin_amdgcn_sad_u8(v[u].z, 0u, su));
+        hb += high_bytes(v[u].y) + high_bytes(v[u].z);
+      }
+      uint32_t p = su | (hb << 20);  // su <= 512 x 255 < 2^17, hb <= 512: no carry between them
+      p = row_ror_add<0x128>(p);
+      p = row_ror_add<0x124>(p);
+      p = row_ror_add<0x122>(p);
+      p = row_ror_add<0x121>(p);
+#pragma unroll
+      for (uint32_t h = 0; h < 2; h++) {
+        const uint32_t s = uint32_t(__builtin_amdgcn_readlane(int(p), int(32 * h))) +
+                           uint32_t(__builtin_amdgcn_readlane(int(p), int(32 * h + 16)));
+        const int32_t w = __builtin_amdgcn_readlane(want, int(32 * h + 9));
+        const int32_t uns = int32_t(s & 0xFFFFFu), sgn = uns - 256 * int32_t(s >> 20);
+        const bool cand = w != kNoWant && (w == uns || w == sgn) && b0 + 2u * u + h < n_blocks;
+        if (cand) mask |= uint64_t(1) << (k * kTileBlocks + 2u * u + h);
+      }
+    }
+  }
+  return mask;
+}
+
 __global__ __launch_bounds__(kTThreads) void tar_headers_kernel(const uint8_t* __restrict__ tar, uint64_t n_blocks,
                                                                 uint8_t* __restrict__ records, uint32_t capacity,
                                                                 uint32_t* __restrict__ count) {
@@ -89,46 +136,7 @@ __global__ __launch_bounds__(kTThreads) void tar_headers_kernel(const uint8_t* _
   const uint64_t n_groups = (n_blocks + kGroupBlocks - 1) / kGroupBlocks;
   for (uint64_t g = uint64_t(blockIdx.x) * 4u + wave; g < n_groups; g += uint64_t(gridDim.x) * 4u) {
     const uint64_t g0 = g * kGroupBlocks;
-    uint64_t mask = 0;  // bit i: block g0 + i is a candidate (wave-uniform)
-    for (uint32_t k = 0; k < kGroupTiles; k++) {
-      const uint64_t b0 = g0 + k * kTileBlocks;
-      if (b0 >= n_blocks) break;  // (wave-uniform)
-      uint4 v[4];
-#pragma unroll
-      for (uint32_t u = 0; u < 4; u++) {
-        // no branch around a load (it would wait for each before the next is issued): a block past the
-        // end reads the last block instead (n_blocks >= 1 here) and is no candidate, whatever it holds
-        const uint64_t blk = min(b0 + 2u * u + half, n_blocks - 1);
-        v[u] = *reinterpret_cast<const uint4*>(tar + blk * 512u + l * 16u);  // (ends at or before 512 n_blocks)
-      }
-#pragma unroll
-      for (uint32_t u = 0; u < 4; u++) {
-        uint32_t su = __builtin_amdgcn_sad_u8(v[u].x, 0u, __builtin_amdgcn_sad_u8(v[u].w, 0u, 0u));
-        uint32_t hb = high_bytes(v[u].x) + high_bytes(v[u].w);
-        int32_t want = kNoWant;
-        if (l == 9) {  // bytes 148..155 are this lane's y and z: eight spaces in the sums
-          su += 8u * 0x20u;
-          want = parse_field(uint64_t(v[u].y) | (uint64_t(v[u].z) << 32));
-        } else {
-          su = __builtin_amdgcn_sad_u8(v[u].y, 0u, __builtin_amdgcn_sad_u8(v[u].z, 0u, su));
-          hb += high_bytes(v[u].y) + high_bytes(v[u].z);
-        }
-        uint32_t p = su | (hb << 20);  // su <= 512 x 255 < 2^17, hb <= 512: no carry between them
-        p = row_ror_add<0x128>(p);
-        p = row_ror_add<0x124>(p);
-        p = row_ror_add<0x122>(p);
-        p = row_ror_add<0x121>(p);
-#pragma unroll
-        for (uint32_t h = 0; h < 2; h++) {
-          const uint32_t s = uint32_t(__builtin_amdgcn_readlane(int(p), int(32 * h))) +
-                             uint32_t(__builtin_amdgcn_readlane(int(p), int(32 * h + 16)));
-          const int32_t w = __builtin_amdgcn_readlane(want, int(32 * h + 9));
-          const int32_t uns = int32_t(s & 0xFFFFFu), sgn = uns - 256 * int32_t(s >> 20);
-          const bool cand = w != kNoWant && (w == uns || w == sgn) && b0 + 2u * u + h < n_blocks;
-          if (cand) mask |= uint64_t(1) << (k * kTileBlocks + 2u * u + h);
-        }
-      }
-    }
+    uint64_t mask = group_mask(tar, n_blocks, g0, l, half);
     if (mask == 0) continue;  // (wave-uniform)
     // One reservation for the group's candidates: every wave adds to the one counter, and a layer of
     // small files has a candidate in most tiles.  The candidates' bytes are then read again (they
@@ -155,6 +163,22 @@ __global__ __launch_bounds__(kTThreads) void tar_headers_kernel(const uint8_t* _
   }
 }
 
+// tar_bitmap : the same pass with the verdict stored as it is, one 64-bit word per group of 64 blocks
+//              (bit i of word g: block 64 g + i), lane 0's vector store: no atomics, no capacity, no
+//              second run.  Every word of the groups below n_blocks is written; the bits of blocks at or
+//              past n_blocks are 0.
+__global__ __launch_bounds__(kTThreads) void tar_bitmap_kernel(const uint8_t* __restrict__ tar, uint64_t n_blocks,
+                                                               uint64_t* __restrict__ bitmap) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t l = lane & 31u, half = lane >> 5;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t n_groups = (n_blocks + kGroupBlocks - 1) / kGroupBlocks;
+  for (uint64_t g = uint64_t(blockIdx.x) * 4u + wave; g < n_groups; g += uint64_t(gridDim.x) * 4u) {
+    const uint64_t mask = group_mask(tar, n_blocks, g * kGroupBlocks, l, half);
+    if (lane == 0) bitmap[g] = mask;
+  }
+}
+
 }  // namespace
 
 hipError_t TarHeaders(const uint8_t* dev_tar, uint64_t n_bytes, uint8_t* d_records, uint32_t capacity,
@@ -166,6 +190,16 @@ hipError_t TarHeaders(const uint8_t* dev_tar, uint64_t n_bytes, uint8_t* d_recor
   uint64_t grid = std::min((n_groups + 3) / 4, kMaxGrid);
   if (grid_cap) grid = std::min<uint64_t>(grid, grid_cap);
   tar_headers_kernel<<<uint32_t(grid), kTThreads, 0, s>>>(dev_tar, n_blocks, d_records, capacity, d_count);
+  return hipGetLastError();
+}
+
+hipError_t TarBitmap(const uint8_t* dev_tar, uint64_t n_bytes, uint64_t* d_bitmap, uint32_t grid_cap, hipStream_t s) {
+  const uint64_t n_blocks = n_bytes / 512;
+  if (n_blocks == 0) return hipSuccess;
+  const uint64_t n_groups = (n_blocks + kGroupBlocks - 1) / kGroupBlocks;
+  uint64_t grid = std::min((n_groups + 3) / 4, kMaxGrid);
+  if (grid_cap) grid = std::min<uint64_t>(grid, grid_cap);
+  tar_bitmap_kernel<<<uint32_t(grid), kTThreads, 0, s>>>(dev_tar, n_blocks, d_bitmap);
   return hipGetLastError();
 }
 

@@ -17,6 +17,7 @@
  *   tsg_collector_submit       the Scan calls of a batch           secret.go:137-141 -> scanner.go:377
  *   tsg_collector_add_tar      LayerTar.Walk + AnalyzeFile's       pkg/fanal/walker/tar.go:35-103,
  *                              Required gate for this analyzer     pkg/fanal/analyzer/analyzer.go:403-455
+ *   tsg_analyzer_set_tar_skip  NewLayerTar's skipFiles / skipDirs  pkg/fanal/walker/tar.go:23-33, 64-81, 105-116
  *
  * Results: tsg_scan_wait gives a tsg_result whose file i is the collector's
  * i-th added file; Analyze returns nil unless that file's kind is 2 (findings),
@@ -83,6 +84,50 @@ int tsg_collector_add_tar(tsg_collector* c, const uint8_t* tar, uint64_t n, uint
  * cached window, so a later buffer at the same address starts afresh. */
 int tsg_analyzer_set_walk_ahead(tsg_analyzer* a, int on);
 int tsg_analyzer_walk_end(tsg_analyzer* a);
+
+/* LayerTar's options (walker/tar.go:23-33): skip_dirs / skip_files as utils.SkipPath
+ * doublestar patterns, already cleaned (the caller applies utils.CleanSkipPaths as
+ * NewLayerTar does; the division of labour of tsg_fs_walk_new).  They hold for every
+ * layer walk of this analyzer made afterwards: tsg_collector_add_tar in copy and in
+ * gather mode, tsg_analyzer_index_device_tar in both walk modes.  Per entry, in
+ * chain order and on the cleaned path without leading '/' (tar.go:46-81): whiteout
+ * and opaque markers are counted first, as without options; a directory (typeflag
+ * '5', or '\0' with a resolved name that ends in '/') that skip_dirs matches is
+ * recorded and dropped; a regular file that skip_files matches is dropped; a file
+ * that survives is dropped when underSkippedDir holds against the directories
+ * recorded so far (filepath.Rel: below one, equal to one, or the direct parent of
+ * one; a Rel failure ends the test with false).  The test depends on the order of
+ * the archive: a file before its directory's entry is kept.  A skipped subtree of a
+ * resident layer lies in the gaps between the index's files and is dropped where it
+ * lies.  tsg_tar_stats.regular still counts every regular entry; .required only
+ * those not skipped that Required accepts.
+ * The call ends the tar walk in progress (as tsg_analyzer_walk_end) and drops its
+ * cached window, and resets the analyzer's skip counts; zero patterns restore the
+ * walk without options.  A walk resumed by cursor continues its list of recorded
+ * directories when the cursor continues the walk in progress on the same buffer
+ * (it is where the last call stopped, or lies inside what that walk has read);
+ * cursor 0 starts a fresh list, and any other cursor -- another buffer, a position
+ * past what was read, a walk ended by tsg_analyzer_walk_end -- starts with an
+ * empty one.  Index calls running on other threads keep the options they began with.
+ * -1 (before any work): NULL analyzer, a NULL array with a non-zero count, a NULL
+ * pattern.  A malformed pattern is no error: SkipPath stops at it with false. */
+int tsg_analyzer_set_tar_skip(tsg_analyzer* a, const char* const* skip_dirs, uint32_t n_dirs,
+                              const char* const* skip_files, uint32_t n_files);
+/* How many patterns are set. */
+int tsg_analyzer_get_tar_skip(const tsg_analyzer* a, uint32_t* n_dirs, uint32_t* n_files);
+
+/* What the options dropped (versioned, struct_size first): skipped_dirs, directory
+ * entries recorded; skipped_files, regular files skip_files matched;
+ * under_skipped_dir, regular files (only) dropped by underSkippedDir. */
+typedef struct tsg_tar_skip_stats {
+  uint32_t struct_size, reserved;
+  uint64_t skipped_dirs, skipped_files, under_skipped_dir;
+} tsg_tar_skip_stats;
+#define TSG_TAR_SKIP_STATS_SIZE_V1 ((uint32_t)(offsetof(tsg_tar_skip_stats, under_skipped_dir) + sizeof(uint64_t)))
+/* The host walks (tsg_collector_add_tar) of this analyzer, cumulative since the last
+ * tsg_analyzer_set_tar_skip; an entry counts when a batch takes it or passes it.
+ * -1: NULL argument or an unknown struct_size. */
+int tsg_analyzer_tar_skip_stats(tsg_analyzer* a, tsg_tar_skip_stats* out);
 
 /* GPU pre-transform mode (empty collector only): files go into the arena as
  * read, and the CR strip / printable extraction runs on the GPU at scan time
@@ -304,6 +349,9 @@ typedef struct tsg_tar_walk_stats {
 #define TSG_TAR_WALK_STATS_SIZE_V1 ((uint32_t)(offsetof(tsg_tar_walk_stats, ms_host) + sizeof(double)))
 /* -1: NULL argument or an unknown struct_size. */
 int tsg_tar_index_walk_stats(const tsg_tar_index* ix, tsg_tar_walk_stats* out);
+/* What tsg_analyzer_set_tar_skip's options dropped from this index (all zero without
+ * options).  -1: NULL argument or an unknown struct_size. */
+int tsg_tar_index_skip_stats(const tsg_tar_index* ix, tsg_tar_skip_stats* out);
 
 #ifdef __cplusplus
 }

@@ -80,6 +80,9 @@ def main():
     ap.add_argument("--layer-format", choices=("ustar", "pax"), default="ustar",
                     help="--layer: pax rewrites the generated layer with a PAX x header (path, mtime) before every entry")
     ap.add_argument("--index-only", action="store_true", help="--layer: time IndexDevice alone, no scans, no host leg")
+    ap.add_argument("--skip-dirs", default="", help="--layer: LayerTar skipDirs patterns, comma-separated; every mode "
+                    "then also runs with the options set (mode name + \"+skip\"), in the same interleaved blocks")
+    ap.add_argument("--skip-files", default="", help="--layer: LayerTar skipFiles patterns, comma-separated")
     ap.add_argument("--fwd", type=int, default=None)
     ap.add_argument("--fwd-cap", type=int, default=None)
     ap.add_argument("--back", type=int, default=None)
@@ -492,8 +495,17 @@ def layer_leg(args):
     walks = ("host", "gpu") if args.walk == "both" else (args.walk,)
     dev_modes = tuple("device" if w == "host" else "device-gpu-walk" for w in walks)
     modes = dev_modes if args.index_only else dev_modes + ("host",)
+    walker = None
+    if args.skip_dirs or args.skip_files:
+        from trivy_amd.walker import NewLayerTar, Option
+        walker = NewLayerTar(Option(SkipFiles=[p for p in args.skip_files.split(",") if p],
+                                    SkipDirs=[p for p in args.skip_dirs.split(",") if p]))
+        modes = tuple(m + v for m in modes for v in ("", "+skip"))
 
     def step(mode):
+        if walker is not None:
+            an.set_layer_walker(walker if mode.endswith("+skip") else None)
+            mode = mode.split("+")[0]
         st = {}
         if mode != "host" and (mode == "device-gpu-walk" or hasattr(an._L, "tsg_analyzer_set_tar_walk")):
             an.set_tar_walk("gpu" if mode == "device-gpu-walk" else "host")
@@ -534,12 +546,14 @@ def layer_leg(args):
         unregister()
     if not args.index_only:
         findings = {m: res[m][-1]["scan_findings"] for m in modes}
-        assert len(set(findings.values())) == 1, findings
+        for v in ("", "+skip"):  # every mode finds the same, with the options and without
+            assert len({f for m, f in findings.items() if m.endswith("+skip") == bool(v)}) <= 1, findings
 
     def med(xs):
         return float(statistics.median(xs))
 
     claim = {m: max(per[m]) < min(per["host"]) for m in dev_modes} if not args.index_only else {}
+    skip_keys = ("skipped_dirs", "skipped_files", "under_skipped_dir")
     for m in modes:
         last = res[m][-1]
         out = {"tool": "device_only_bench --layer", "mode": m, "fetch": args.fetch, "resident": args.resident,
@@ -549,8 +563,10 @@ def layer_leg(args):
                "gbps": n_bytes / 1e6 / med(per[m]), "host_cpus": med(cpus[m])}
         if not args.index_only:
             out["findings"] = int(findings[m])
-        if m != "host":
-            if not args.index_only:
+        if walker is not None:
+            out["skip"] = {k: int(last.get(k, 0)) for k in skip_keys}
+        if m.split("+")[0] != "host":
+            if not args.index_only and m in claim:
                 out["device_slowest_below_host_fastest"] = claim[m]
             keys = ("ms_kernel", "ms_total", "blocks", "candidates", "off_chain", "block_fetches", "ext_bytes",
                     "kernel_runs", "entries", "regular", "required", "files")

@@ -5,6 +5,8 @@ Generates a C4-style layer (--gb of file data), walks it into 256-MiB batches
 with a host-only scanner from the oracle library (no GPU needed) and prints
 seconds per full walk.  By default the arena gets the bytes as read (the bench's
 C4 GPU pre-transform mode); --host-transform packs them transformed.  TSG_WALK_DEBUG=1 adds the per-phase split.
+--skip-dirs / --skip-files (comma-separated LayerTar patterns): every rep walks the layer without options and
+then with them, and prints the second walk's time and skip counts next to the first's.
 """
 import argparse
 import os
@@ -23,6 +25,8 @@ def main():
     ap.add_argument("--arena-mb", type=int, default=256)
     ap.add_argument("--host-transform", action="store_true",
                     help="CR strip / printable extraction while packing (default: bytes as read, as C4's GPU mode)")
+    ap.add_argument("--skip-dirs", default="", help="LayerTar skipDirs patterns, comma-separated")
+    ap.add_argument("--skip-files", default="", help="LayerTar skipFiles patterns, comma-separated")
     a = ap.parse_args()
     layer = corpus.generate_layer(int(a.gb * 1e9))
     from trivy_amd.analyzer import AnalyzerOptions, SecretAnalyzer, SecretScannerOption
@@ -35,7 +39,13 @@ def main():
         import ctypes
         sp = ctypes.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "sprof", "sprof.so"))
         sp.sprof_start(4000)
-    for rep in range(a.reps):
+    walker = None
+    if a.skip_dirs or a.skip_files:
+        from trivy_amd.walker import NewLayerTar, Option
+        walker = NewLayerTar(Option(SkipFiles=[p for p in a.skip_files.split(",") if p],
+                                    SkipDirs=[p for p in a.skip_dirs.split(",") if p]))
+
+    def walk():
         t0 = time.time()
         cur, files, st = 0, 0, _CTarStats()
         while True:
@@ -44,8 +54,19 @@ def main():
             col.reset()
             if r == 0:
                 break
-        dt = time.time() - t0
+        return time.time() - t0, files, st
+
+    for rep in range(a.reps):
+        dt, files, st = walk()
         print("walk %.3f s  %.2f GB/s layer  files %d" % (dt, layer.size / dt / 1e9, files))
+        if walker is not None:
+            an.set_layer_walker(walker)
+            dt, files, st = walk()
+            sk = an.tar_skip_stats()
+            an.set_layer_walker(None)
+            print("walk with options %.3f s  %.2f GB/s layer  files %d  entries %d  skipped_dirs %d  skipped_files %d"
+                  "  under_skipped_dir %d" % (dt, layer.size / dt / 1e9, files, st.entries, sk["skipped_dirs"],
+                                             sk["skipped_files"], sk["under_skipped_dir"]))
     if sp is not None:
         print("sprof samples", sp.sprof_stop(os.environ["SPROF"].encode()))
 

@@ -104,9 +104,27 @@ TAR_WALK_FALLBACKS = ("", "size field", "PAX record", "PAX size form", "cap", "n
                       "too many blocks")
 
 
+class _CTarSkipStats(c.Structure):  # tsg_tar_skip_stats (versioned)
+    _fields_ = [("struct_size", c.c_uint32), ("reserved", c.c_uint32)] + \
+               [(n, c.c_uint64) for n in ("skipped_dirs", "skipped_files", "under_skipped_dir")]
+
+    def to_dict(self):
+        return {n: getattr(self, n) for n in TAR_SKIP_KEYS}
+
+
+TAR_SKIP_KEYS = ("skipped_dirs", "skipped_files", "under_skipped_dir")
+TAR_SKIP_STATS_SIZE_V1 = _CTarSkipStats.under_skipped_dir.offset + c.sizeof(c.c_uint64)
+
+
 def _declare(L):
     if getattr(L, "_tsg_analyzer_declared", False):
         return
+    if hasattr(L, "tsg_analyzer_set_tar_skip"):  # (absent from an older build of the library: TSG_LIB)
+        L.tsg_analyzer_set_tar_skip.argtypes = [c.c_void_p, c.POINTER(c.c_char_p), c.c_uint32, c.POINTER(c.c_char_p),
+                                                c.c_uint32]
+        L.tsg_analyzer_get_tar_skip.argtypes = [c.c_void_p, c.POINTER(c.c_uint32), c.POINTER(c.c_uint32)]
+        L.tsg_analyzer_tar_skip_stats.argtypes = [c.c_void_p, c.POINTER(_CTarSkipStats)]
+        L.tsg_tar_index_skip_stats.argtypes = [c.c_void_p, c.POINTER(_CTarSkipStats)]
     if hasattr(L, "tsg_analyzer_set_tar_walk"):  # (absent from an older build of the library: TSG_LIB)
         L.tsg_analyzer_set_tar_walk.argtypes = [c.c_void_p, c.c_int]
         L.tsg_analyzer_get_tar_walk.argtypes = [c.c_void_p, c.POINTER(c.c_int)]
@@ -422,6 +440,17 @@ class DeviceTarIndex:
             raise RuntimeError("tsg_tar_index_walk_stats failed: %s" % _lib.last_error(self._an._L))
         return ws.to_dict()
 
+    @property
+    def skip_stats(self) -> dict:
+        """What the layer walker's skip options dropped from this index (tsg_tar_index_skip_stats)."""
+        st = _CTarSkipStats()
+        st.struct_size = TAR_SKIP_STATS_SIZE_V1
+        if not hasattr(self._an._L, "tsg_tar_index_skip_stats"):  # an older build: no options, nothing dropped
+            return st.to_dict()
+        if self._an._L.tsg_tar_index_skip_stats(self._h, c.byref(st)) != 0:
+            raise RuntimeError("tsg_tar_index_skip_stats failed: %s" % _lib.last_error(self._an._L))
+        return st.to_dict()
+
     def path(self, i: int) -> str:
         pp, pl = c.c_void_p(), c.c_uint64()
         if self._an._L.tsg_tar_index_file(self._h, i, c.byref(pp), c.byref(pl), None, None) != 0:
@@ -533,6 +562,7 @@ class SecretAnalyzer:
         self._host_only = host_only
         self._h = None
         self._walk_buf = None  # the layer buffer of a walk in progress (Collector.add_tar)
+        self._layer_walker = None  # walker.LayerTar (set_layer_walker)
         self.scanner = None
         self.configPath = configPath
         if scanner is not None:
@@ -551,6 +581,8 @@ class SecretAnalyzer:
         self._h = h
         # walk-ahead: this object keeps the layer buffer alive until the walk ends
         self._L.tsg_analyzer_set_walk_ahead(h, 1)
+        if self._layer_walker is not None:  # a new native analyzer: the options go with this object
+            self.set_layer_walker(self._layer_walker)
 
     def WalkEnd(self):
         """Ends a tar walk (joins its background index): the layer buffer may go after this."""
@@ -704,6 +736,40 @@ class SecretAnalyzer:
                              % (t.numel(), n + 64))
         return t.data_ptr(), n, t
 
+    def set_layer_walker(self, walker=None):
+        """The layer walker's options (walker.LayerTar, from walker.NewLayerTar(Option(SkipFiles, SkipDirs)):
+        tar.go:23-33) for every layer walk of this analyzer -- AnalyzeLayer in copy and gather mode,
+        AnalyzeLayers and LayerWorkers (the workers' analyzers inherit them), IndexDevice, IndexLayerDevice
+        and AnalyzeLayerDevice in both tar-walk modes (tsg_analyzer_set_tar_skip).  None, or a walker without
+        patterns, restores the walk without options.  Ends a tar walk in progress."""
+        sd = [_b(p) for p in (walker.skipDirs if walker is not None else [])]
+        sf = [_b(p) for p in (walker.skipFiles if walker is not None else [])]
+        if not hasattr(self._L, "tsg_analyzer_set_tar_skip"):
+            if sd or sf:
+                raise RuntimeError("set_layer_walker: this build of the library has no tsg_analyzer_set_tar_skip")
+            self._layer_walker = None
+            return
+        if self._h:
+            ad = (c.c_char_p * max(1, len(sd)))(*sd)
+            af = (c.c_char_p * max(1, len(sf)))(*sf)
+            if self._L.tsg_analyzer_set_tar_skip(self._h, ad, len(sd), af, len(sf)) != 0:
+                raise ValueError("tsg_analyzer_set_tar_skip failed: %s" % _lib.last_error(self._L))
+            self._walk_buf = None
+        self._layer_walker = walker if (sd or sf) else None
+
+    def layer_walker(self):
+        return self._layer_walker
+
+    def tar_skip_stats(self) -> dict:
+        """What the options dropped in this analyzer's host walks (AnalyzeLayer), summed since
+        set_layer_walker (tsg_analyzer_tar_skip_stats)."""
+        st = _CTarSkipStats()
+        st.struct_size = TAR_SKIP_STATS_SIZE_V1
+        if self._h and hasattr(self._L, "tsg_analyzer_tar_skip_stats"):
+            if self._L.tsg_analyzer_tar_skip_stats(self._h, c.byref(st)) != 0:
+                raise RuntimeError("tsg_analyzer_tar_skip_stats failed: %s" % _lib.last_error(self._L))
+        return st.to_dict()
+
     def set_tar_walk(self, mode):
         """Where IndexDevice / IndexLayerDevice / AnalyzeLayerDevice walk the header chain
         (tsg_analyzer_set_tar_walk): "host" (the default: the GPU finds the header candidates, the host walks
@@ -739,9 +805,11 @@ class SecretAnalyzer:
         if rc != 0:
             raise RuntimeError("tsg_analyzer_index_device_tar failed: %s" % _lib.last_error(self._L))
         d = st.to_dict()
+        ix = DeviceTarIndex(self, h, keep, d)
+        d.update(ix.skip_stats)
         if stats is not None:
             stats.update(d)
-        return DeviceTarIndex(self, h, keep, d)
+        return ix
 
     def IndexLayerDevice(self, dev_layer, nbytes=None, stats=None):
         """Where the files of an uncompressed tar layer resident in HBM are: ([(path, data_off, size)] of
@@ -845,6 +913,7 @@ class SecretAnalyzer:
                 for k2, v in out.items():
                     scan_tot[k2] = scan_tot.get(k2, 0) + v
         st = _CTarStats()
+        skip0 = self.tar_skip_stats()
         colls = colls or [Collector(self, arena_bytes, gpu_transform or gather, gather) for _ in range(2)]
         cursor = 0
         unregister = None
@@ -868,6 +937,7 @@ class SecretAnalyzer:
                 unregister()
         if stats is not None:
             stats.update({n: getattr(st, n) for n, _ in st._fields_})
+            stats.update({k2: v - skip0[k2] for k2, v in self.tar_skip_stats().items()})  # this layer's
             stats.update({"scan_" + k2: v for k2, v in scan_tot.items()})
             stats.update({"walk_s": t_walk, "wait_s": t_wait})
         return result
@@ -882,6 +952,7 @@ class SecretAnalyzer:
         for _ in range(max(1, parallel)):
             sub = SecretAnalyzer(self.scanner, self.configPath, device=self.device, lib=self._L,
                                  host_only=self._host_only)
+            sub.set_layer_walker(self._layer_walker)
             out.append((sub, [Collector(sub, arena_bytes, gpu_transform or gather, gather)
                               for _ in range(max(1, collectors))]))
         return out
@@ -921,6 +992,10 @@ class SecretAnalyzer:
         if workers is None:
             workers = self.LayerWorkers(min(parallel, max(1, len(todo))), arena_bytes, collectors, gpu_transform,
                                         gather)
+
+        for sub, _ in workers:  # (workers made before the options were set: they inherit them now)
+            if sub._layer_walker != self._layer_walker:
+                sub.set_layer_walker(self._layer_walker)
 
         def worker(sub, colls):
             while True:

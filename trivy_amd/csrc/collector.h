@@ -6,10 +6,12 @@
 #include <atomic>
 #include <cstdint>
 #include <cstdlib>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
+#include "tar_skip.h"
 #include "tsg_analyzer.h"
 
 namespace tsg {
@@ -48,6 +50,16 @@ struct tsg_analyzer {
   // records, 1 on the GPU (TSG_TAR_WALK=gpu at creation).  Read once per index call.
   std::atomic<int> tar_walk{0};
   std::atomic<uint32_t> tar_fallback_last{0};  // tsg_debug_tar_walk_last_fallback: the last mode-1 call's
+  // tsg_analyzer_set_tar_skip: LayerTar's skipDirs / skipFiles for every layer walk
+  // (NULL: none).  Replaced under walk_mu and tar_skip_mu; a walk or an index call
+  // takes a reference of its own (TarSkip()), so a background index keeps its patterns.
+  mutable std::mutex tar_skip_mu;
+  std::shared_ptr<const tsg::TarSkipOpts> tar_skip;
+  tsg::TarSkipCounts tar_skip_counts;  // the host walks', cumulative since the setter (under walk_mu)
+  std::shared_ptr<const tsg::TarSkipOpts> TarSkip() const {
+    std::lock_guard<std::mutex> g(tar_skip_mu);
+    return tar_skip;
+  }
   ~tsg_analyzer() {
     tsg::FreeTarWalkCache(walk);
     tsg::FreeClassifyPool(classify);

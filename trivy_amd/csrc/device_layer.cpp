@@ -183,10 +183,12 @@ auto EntriesPar() {
   };
 }
 
+// (the analyzer's skip options, tsg_analyzer_set_tar_skip, as they are when the walk begins)
 int WalkRecords(tsg_analyzer* a, const IndexedTarSrc& src, uint64_t n_bytes, TarIndexData* d) {
+  const std::shared_ptr<const TarSkipOpts> skip = a->TarSkip();
   return WalkTarIndex(
       src, n_bytes, [a](const char* p, uint64_t len, int64_t size) { return RequiredPath(a, p, len, size); }, d,
-      ChunkedPar());
+      ChunkedPar(), skip.get());
 }
 
 // ---- the chain walk on the GPU (tarchain.h) ----------------------------------
@@ -194,10 +196,11 @@ int WalkRecords(tsg_analyzer* a, const IndexedTarSrc& src, uint64_t n_bytes, Tar
 int EntriesToIndex(tsg_analyzer* a, const tsg_tar_entry_rec* recs, uint64_t n, const uint8_t* names, uint64_t name_bytes,
                    const tsg_tar_stop& stop, uint64_t n_bytes, uint64_t candidates, TarIndexData* d,
                    tsg_device_tar_stats* st, double* ms = nullptr) {
+  const std::shared_ptr<const TarSkipOpts> skip = a->TarSkip();
   if (IndexTarEntries(
           recs, n, names, name_bytes,
           [a](const char* p, uint64_t len, int64_t size) { return RequiredPath(a, p, len, size); }, d, EntriesPar(),
-          ms) < 0)
+          ms, skip.get()) < 0)
     return -1;
   if (st) {
     uint64_t on_chain = stop.ext_visited;  // every header of every entry, as the host walk's records visited
@@ -498,6 +501,23 @@ int tsg_tar_index_walk_stats(const tsg_tar_index* ix, tsg_tar_walk_stats* out) {
   *out = ix->ws;
   out->struct_size = TSG_TAR_WALK_STATS_SIZE_V1;
   out->reserved = 0;
+  return 0;
+}
+
+int tsg_tar_index_skip_stats(const tsg_tar_index* ix, tsg_tar_skip_stats* out) {
+  if (!ix || !out) {
+    tsg::SetError("tsg_tar_index_skip_stats: NULL argument");
+    return -1;
+  }
+  if (out->struct_size != TSG_TAR_SKIP_STATS_SIZE_V1) {
+    tsg::SetError("tsg_tar_index_skip_stats: tsg_tar_skip_stats.struct_size " + std::to_string(out->struct_size) +
+                  " is not a size this library knows (v1 = " + std::to_string(TSG_TAR_SKIP_STATS_SIZE_V1) + ")");
+    return -1;
+  }
+  out->reserved = 0;
+  out->skipped_dirs = ix->d.skip.skipped_dirs;
+  out->skipped_files = ix->d.skip.skipped_files;
+  out->under_skipped_dir = ix->d.skip.under_skipped_dir;
   return 0;
 }
 

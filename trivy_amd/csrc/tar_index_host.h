@@ -29,6 +29,7 @@
 #include <string_view>
 #include <vector>
 
+#include "tar_skip.h"
 #include "tarchain.h"
 #include "tsg_analyzer.h"
 
@@ -195,6 +196,8 @@ struct TarEntry {
   uint8_t what;          // 0 other, 1 whiteout, 2 opaque dir, 3 regular file
   uint8_t has_pax_path;
   uint8_t bad;           // the entry header's checksum is wrong (checked on the threads)
+  uint8_t dir = 0;       // TypeDir (typeflag '5', or TypeRegA with a resolved name ending in '/'), no marker
+  uint8_t skip = 0;      // kTarSkip*: LayerTar's skipDirs / skipFiles (tar_skip.h)
   // The cleaned path (walker/tar.go:46-48): a view of the header's name field
   // in the archive itself when that is already the answer (a ustar name with
   // no prefix, clean; sources with kView only), else an owned string (PAX /
@@ -347,10 +350,15 @@ const uint8_t* ResolveT(const Src& src, TarEntry* e) {
 // LayerTar.Walk's per-entry path logic (walker/tar.go:41-84): clean the name,
 // classify whiteout / opaque markers.  `tar`: the layer buffer of a kView
 // source (what TarEntry::path reads), else NULL.  ClassifyPath is the part after
-// the name is resolved (reg_a: the header's typeflag is TypeRegA).
-inline void ClassifyPath(bool reg_a, const uint8_t* tar, TarEntry* e) {
+// the name is resolved (typeflag: the header's).
+inline void ClassifyPath(uint8_t typeflag, const uint8_t* tar, TarEntry* e) {
   std::string_view fp = e->path(tar);
-  if (reg_a && !fp.empty() && fp.back() == '/') e->what = 0;  // TypeRegA dir
+  e->dir = typeflag == '5';
+  e->skip = 0;
+  if (typeflag == '\0' && !fp.empty() && fp.back() == '/') {  // TypeRegA dir
+    e->what = 0;
+    e->dir = 1;
+  }
   if (!GoPathIsClean(fp.data(), fp.size())) {
     e->own(GoPathClean(std::string(fp)));
     fp = *e->fp_own;
@@ -370,12 +378,13 @@ inline void ClassifyPath(bool reg_a, const uint8_t* tar, TarEntry* e) {
   const std::string_view file_name = fp.substr(slash == std::string_view::npos ? 0 : slash + 1);
   if (file_name == ".wh..wh..opq") e->what = 2;
   else if (file_name.substr(0, 4) == ".wh.") e->what = 1;
+  if (e->what == 1 || e->what == 2) e->dir = 0;  // markers come first (tar.go:51-62)
 }
 template <class Src>
 void ClassifyT(const Src& src, const uint8_t* tar, TarEntry* e) {
   const uint8_t* h = ResolveT(src, e);
   if (!h) return;
-  ClassifyPath(h[156] == '\0', tar, e);
+  ClassifyPath(h[156], tar, e);
 }
 
 // ---- a layer resident in HBM ------------------------------------------------
@@ -471,6 +480,7 @@ struct TarIndexData {
   std::string pool;
   std::vector<TarIndexFile> files;
   tsg_tar_stats tar{};  // entries, regular, required, whiteouts, opaque_dirs as the host walk counts them
+  TarSkipCounts skip;   // what LayerTar's skip options dropped (all zero without them)
 };
 
 // The walk (tsg_collector_add_tar's rules, entry by entry): 0, or <0 with the
@@ -504,10 +514,15 @@ void FinishTarIndex(const std::string& pool, const std::vector<TarIndexFile>& re
     out->tar.required++;
   }
 }
+// skip (optional): LayerTar's skipDirs / skipFiles, applied entry by entry in
+// chain order as tar.go:64-81 does; a dropped file is in `regular`, not in the index.
 template <class Src, class Req, class Par = SerialFor>
-int WalkTarIndex(const Src& src, uint64_t n, Req&& required, TarIndexData* out, Par&& par = Par()) {
+int WalkTarIndex(const Src& src, uint64_t n, Req&& required, TarIndexData* out, Par&& par = Par(),
+                 const TarSkipOpts* skip = nullptr) {
   std::string pool;
   std::vector<TarIndexFile> regular;
+  TarSkipDirs skipped;
+  const bool skips = skip && skip->any();
   uint64_t p = 0;
   for (;;) {
     TarEntry e;
@@ -524,7 +539,9 @@ int WalkTarIndex(const Src& src, uint64_t n, Req&& required, TarIndexData* out, 
     out->tar.whiteouts += e.what == 1;
     out->tar.opaque_dirs += e.what == 2;
     out->tar.regular += e.what == 3;
-    if (e.what == 3) {
+    if (__builtin_expect(skips, 0) && (e.dir || e.what == 3))
+      e.skip = TarSkipStep(*skip, e.dir, e.what == 3, e.path(src.base()), e.start, &skipped, &out->skip);
+    if (e.what == 3 && !e.skip) {
       const std::string_view fp = e.path(src.base());
       regular.push_back({uint64_t(pool.size()), uint64_t(fp.size()), e.start, e.data, e.size});
       pool.append(fp.data(), fp.size());
@@ -545,10 +562,18 @@ int WalkTarIndex(const Src& src, uint64_t n, Req&& required, TarIndexData* out, 
 // then joined in order, Required runs through par as in WalkTarIndex, and the
 // index equals WalkTarIndex's.  ms (optional): classify, join, Required + index.
 // -1: a record points outside the name blob (error set).
+// skip (optional): LayerTar's skipDirs / skipFiles.  What an entry is by itself
+// (TarSkipEval) is decided in its chunk; the skipped directories of all chunks
+// are then recorded in walk order with the rank of their entry, and every
+// surviving regular file is tested -- through par again -- against the
+// directories recorded at a lower rank than its own, which is what the
+// sequential walk's list held when it reached the file.
 constexpr size_t kTarEntryChunk = 64;
 template <class Req, class Par = SerialFor>
 int IndexTarEntries(const tsg_tar_entry_rec* recs, uint64_t n, const uint8_t* names, uint64_t name_bytes,
-                    Req&& required, TarIndexData* out, Par&& par = Par(), double* ms = nullptr) {
+                    Req&& required, TarIndexData* out, Par&& par = Par(), double* ms = nullptr,
+                    const TarSkipOpts* skip = nullptr) {
+  const bool skips = skip && skip->any();
   auto now = [] {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
   };
@@ -558,6 +583,9 @@ int IndexTarEntries(const tsg_tar_entry_rec* recs, uint64_t n, const uint8_t* na
     std::vector<TarIndexFile> regular;  // path_off relative to pool
     uint64_t whiteouts = 0, opaque_dirs = 0;
     bool bad = false;
+    // with skip options: kTarSkip* per regular file, and the skipped directories (rank, path)
+    std::vector<uint8_t> reg_skip;
+    std::vector<std::pair<uint64_t, std::string>> skipped_dirs;
   };
   const size_t n_chunks = (size_t(n) + kTarEntryChunk - 1) / kTarEntryChunk;
   std::vector<Chunk> chunks(n_chunks);
@@ -574,9 +602,15 @@ int IndexTarEntries(const tsg_tar_entry_rec* recs, uint64_t n, const uint8_t* na
       e.what = (r.typeflag == '0' || r.typeflag == '\0') ? 3 : 0;
       e.fp_off = r.name_off;  // a view of the name blob, which stands in for the layer buffer of a kView source
       e.fp_len = r.name_len;
-      ClassifyPath(r.typeflag == '\0', names, &e);
+      ClassifyPath(r.typeflag, names, &e);
       k.whiteouts += e.what == 1;
       k.opaque_dirs += e.what == 2;
+      if (__builtin_expect(skips, 0) && (e.dir || e.what == 3)) {
+        const std::string_view fp = e.path(names);
+        e.skip = TarSkipEval(*skip, e.dir, e.what == 3, fp);
+        if (e.skip == kTarSkipDir) k.skipped_dirs.emplace_back(r.start, std::string(fp));
+        if (e.what == 3) k.reg_skip.push_back(e.skip);
+      }
       if (e.what == 3) {
         const std::string_view fp = e.path(names);
         k.regular.push_back({uint64_t(k.pool.size()), uint64_t(fp.size()), r.start, r.data, r.size});
@@ -603,6 +637,11 @@ int IndexTarEntries(const tsg_tar_entry_rec* recs, uint64_t n, const uint8_t* na
   out->tar.regular += reg_at[n_chunks];
   std::string pool(pool_at[n_chunks], '\0');
   std::vector<TarIndexFile> regular(reg_at[n_chunks]);
+  std::vector<uint8_t> reg_skip(skips ? reg_at[n_chunks] : 0);
+  TarSkipDirs skipped;
+  if (skips)
+    for (const Chunk& k : chunks)  // in walk order: the ranks ascend
+      for (const auto& d : k.skipped_dirs) skipped.Record(d.second, d.first);
   par(n_chunks, [&](size_t c) {
     Chunk& k = chunks[c];
     if (!k.pool.empty()) std::memcpy(&pool[pool_at[c]], k.pool.data(), k.pool.size());
@@ -610,10 +649,26 @@ int IndexTarEntries(const tsg_tar_entry_rec* recs, uint64_t n, const uint8_t* na
       TarIndexFile f = k.regular[j];
       f.path_off += pool_at[c];
       regular[reg_at[c] + j] = f;
+      if (skips) {
+        uint8_t sk = k.reg_skip[j];
+        if (!sk && skipped.Under(std::string_view(pool.data() + f.path_off, size_t(f.path_len)), f.start))
+          sk = kTarSkipUnder;
+        reg_skip[reg_at[c] + j] = sk;
+      }
     }
     k = Chunk();
   });
   chunks.clear();
+  if (skips) {  // the dropped files leave the list Required sees
+    out->skip.skipped_dirs += skipped.size();
+    size_t w = 0;
+    for (size_t i = 0; i < regular.size(); i++) {
+      out->skip.skipped_files += reg_skip[i] == kTarSkipFile;
+      out->skip.under_skipped_dir += reg_skip[i] == kTarSkipUnder;
+      if (!reg_skip[i]) regular[w++] = regular[i];
+    }
+    regular.resize(w);
+  }
   const double t2 = now();
   FinishTarIndex(pool, regular, required, out, par);
   if (ms) {

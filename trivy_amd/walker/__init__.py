@@ -3,6 +3,8 @@
 * ``Option``                       -- walk.go:18-21 (SkipFiles, SkipDirs)
 * ``FS().BuildSkipPaths(base, p)`` -- fs.go:102-155: CLI skip paths -> paths relative to the root
 * ``CleanSkipPaths`` / ``SkipPath`` -- pkg/fanal/utils/utils.go:105-126 (doublestar.Match natively)
+* ``LayerTar`` / ``NewLayerTar(opt)`` -- tar.go:23-33: the layer walker's cleaned skip patterns, honoured
+  by every layer walk of a SecretAnalyzer (``SecretAnalyzer.set_layer_walker``)
 * ``FS().Walk(root, opt)``         -- fs.go:25-39 + WalkDirFunc :41-78 as a native handle that
   feeds batch collectors (SecretAnalyzer.AnalyzeFS); ``FS().Files(root, opt)`` lists the
   (FilePath, size) pairs the walk yields, in WalkDir order.
@@ -52,6 +54,17 @@ class Option:  # walk.go:18-21
 
 def CleanSkipPaths(skipPaths: List[str]) -> List[str]:  # utils.go:105-110
     return [posixpath.normpath(p.replace(os.sep, "/")).lstrip("/") if p else "." for p in skipPaths]
+
+
+@dataclass
+class LayerTar:  # tar.go:23-26
+    """The layer walker's options, cleaned: what SecretAnalyzer.set_layer_walker takes."""
+    skipFiles: List[str] = field(default_factory=list)
+    skipDirs: List[str] = field(default_factory=list)
+
+
+def NewLayerTar(opt: Option) -> LayerTar:  # tar.go:28-33
+    return LayerTar(skipFiles=CleanSkipPaths(opt.SkipFiles), skipDirs=CleanSkipPaths(opt.SkipDirs))
 
 
 def Match(pattern: str, path: str, lib=None) -> int:

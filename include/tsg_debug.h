@@ -228,8 +228,19 @@ int tsg_debug_result_k0(const struct tsg_result* r, double* ms_k0);
  *   nl, chunk_file   one entry per 1-KiB chunk of the arena
  *   recs        flagged 16-B block indices (arena byte / 16)
  *   cands       64-B Candidate records, kCandDrop ones included
- * counters: the engine's 16 counters; caps: {hit, record, candidate} capacity
- * of the device lists in this scan. */
+ * caps: {hit, record, candidate} capacity of the device lists in this scan.
+ * counters: the engine's 16 scan counters (trivy_amd/csrc/scan_layout.h; a slot
+ * keeps its number).  A count may exceed its list's capacity; a flag is 0 or 1:
+ *   kCtHits 0        anchor hits past the follow requirements + fold-kernel hits
+ *   kCtCands 1       candidates            kCtSpecial 2     files with fold runes
+ *   kCtHitOvf 3      flag: hit list overflowed
+ *   kCtCandOvf 4     flag: candidate list overflowed
+ *   kCtFsOvf 6       flag: a full-scan list overflowed
+ *   kCtRecs 7        flagged-block records  kCtRecOvf 8     flag: record list overflowed
+ *   kCtFolds 9       fold-rune sites        kCtFoldOvf 10   flag: fold-site list overflowed
+ *   kCtAnchorHits 11 exact anchor-item matches
+ *   kCtOpenPairs 13  open (file, full-scan rule) pairs
+ *   5, 12, 14, 15    unused */
 typedef struct tsg_debug_stage_dump {
   uint32_t struct_size;  /* sizeof(tsg_debug_stage_dump) */
   uint32_t kw_words;
@@ -247,6 +258,14 @@ typedef struct tsg_debug_stage_dump {
 int tsg_debug_engine_stages(const tsg_compiled* c, int device, const uint8_t* arena, uint64_t n_bytes,
                             const uint64_t* offsets, uint32_t n_files, const uint8_t tail[64],
                             tsg_debug_stage_dump* out);
+/* What the engine grows after a scan that overflowed a list (scan_layout.h
+ * GrowOverflowed), without a GPU.  counters: the 16 scan counters above;
+ * fs_counters: the 6 full-scan list counters {pairs, tasks per NFA width x 4,
+ * wave pairs}, read only when kCtFsOvf is set; caps, in and out: {hit, candidate,
+ * record, fold site, full-scan pair, full-scan task capacity, full-scan lane
+ * task bytes}.  Exactly one list grows per call.  Returns which: 0 none (no
+ * flag set), 1 records, 2 full-scan lists, 3 fold sites, 4 hits, 5 candidates. */
+int tsg_debug_scan_grow(const uint32_t counters[16], const uint32_t fs_counters[6], uint32_t caps[7]);
 
 /* ---- layers resident in HBM (trivy_amd/csrc/tarindex.hip, tar_index_host.h) ----
  * tar_headers_kernel alone on HIP device `device`: dev_tar and records_out are

@@ -25,6 +25,11 @@ TILE = 4096           # engine.hip kFTile
 NL_NONE, NL_UNKNOWN = 0xFFFFFFFE, 0xFFFFFFFF
 NL_REACH = 1 << 20    # engine.h kNlReach
 GATE_OPEN, FOLD_FILE, GATE_VALID, DROP = 1, 2, 4, 8  # engine.h kCand*
+# The scan counters' slots (trivy_amd/csrc/scan_layout.h kCt*; tsg_debug_stage_dump.counters).
+CTR_WORDS = 16
+CT_HITS, CT_CANDS, CT_SPECIAL, CT_HIT_OVF, CT_CAND_OVF = 0, 1, 2, 3, 4
+CT_FS_OVF, CT_RECS, CT_REC_OVF, CT_FOLDS, CT_FOLD_OVF = 6, 7, 8, 9, 10
+CT_ANCHOR_HITS, CT_OPEN_PAIRS = 11, 13
 RUNE_I, RUNE_K, RUNE_S = b"\xc4\xb0", b"\xe2\x84\xaa", b"\xc5\xbf"  # U+0130, U+212A, U+017F
 
 CAND = np.dtype([("file", "<u4"), ("rule", "<u4"), ("wlo", "<i8"), ("whi", "<i8"), ("nl_before", "<i8"),
@@ -66,7 +71,7 @@ class Dump:
 
 
 class _CStageDump(c.Structure):  # tsg_debug_stage_dump (include/tsg_debug.h)
-    _fields_ = [("struct_size", c.c_uint32), ("kw_words", c.c_uint32), ("counters", c.c_uint32 * 16),
+    _fields_ = [("struct_size", c.c_uint32), ("kw_words", c.c_uint32), ("counters", c.c_uint32 * CTR_WORDS),
                 ("caps", c.c_uint32 * 3), ("reserved_", c.c_uint32)] + \
                [(n, t) for name in ("hits", "kw", "flags", "nl", "chunk_file", "recs", "cands")
                 for n, t in ((name, c.c_void_p), (name + "_cap", c.c_uint64), ("n_" + name, c.c_uint64))]
@@ -318,9 +323,9 @@ class StageModel:
             fl = self.cand_flags(r, f, e.flags, e.kw_fold, lambda ff, k: (ff, k) in e.kw_bits)
             enc = lambda v: [NL_NONE if x is None else x for x in v]  # noqa: E731
             cands += [(f, r, wlo, whi, nlb, fl, enc(back), enc(fwd), 0)] * n
-        counters = [0] * 16
-        counters[0], counters[1], counters[7] = len(e.hits_required), len(cands), len(e.blocks)
-        counters[2] = int(np.count_nonzero(e.flags))
+        counters = [0] * CTR_WORDS
+        counters[CT_HITS], counters[CT_CANDS], counters[CT_RECS] = len(e.hits_required), len(cands), len(e.blocks)
+        counters[CT_SPECIAL] = int(np.count_nonzero(e.flags))
         return Dump(counters, self.kw_words, e.hits_required, kw, e.flags, e.nl, e.blocks, e.chunk_file, cands)
 
     # ---- the oracle -------------------------------------------------------------------------------
@@ -386,9 +391,10 @@ def _fail(what, *detail):
 
 def check_overflow(d):
     """No list overflowed: a comparison must not pass on truncated lists."""
-    if any(d.counters[i] for i in (3, 4, 8, 10)):
+    if any(d.counters[i] for i in (CT_HIT_OVF, CT_CAND_OVF, CT_REC_OVF, CT_FOLD_OVF)):
         _fail("overflow counters set", d.counters)
-    if d.counters[0] != len(d.hits) or d.counters[1] != len(d.cands) or d.counters[7] != len(d.recs):
+    if d.counters[CT_HITS] != len(d.hits) or d.counters[CT_CANDS] != len(d.cands) or \
+            d.counters[CT_RECS] != len(d.recs):
         _fail("list lengths differ from the counters", d.counters, len(d.hits), len(d.cands), len(d.recs))
 
 
@@ -435,8 +441,8 @@ def check_flags(d, e, b):
     """Invariant 4: the per-file fold flags and their count."""
     if not np.array_equal(d.flags, e.flags):
         _fail("file flags", [(f, int(d.flags[f]), int(e.flags[f])) for f in np.nonzero(d.flags != e.flags)[0][:8]])
-    if d.counters[2] != int(np.count_nonzero(e.flags)):
-        _fail("special-file count", d.counters[2], int(np.count_nonzero(e.flags)))
+    if d.counters[CT_SPECIAL] != int(np.count_nonzero(e.flags)):
+        _fail("special-file count", d.counters[CT_SPECIAL], int(np.count_nonzero(e.flags)))
     for f, x in enumerate(b.contents):
         if not x and (int(d.flags[f]) or d.kw[f].any()):
             _fail("an empty file has a flag or a keyword bit", f)

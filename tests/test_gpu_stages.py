@@ -127,7 +127,7 @@ def test_fold_files(monkeypatch, variant):
     p = _prepared("fold", sc.case_fold, monkeypatch)
     assert p[1].kw_fold
     d = _run("fold", p, monkeypatch, VARIANTS[variant])
-    assert d.counters[9] > 30 and d.counters[2] > 20  # fold sites, special files
+    assert d.counters[sm.CT_FOLDS] > 30 and d.counters[sm.CT_SPECIAL] > 20  # fold sites, special files
 
 
 def test_fold_files_without_kwfold(monkeypatch):
@@ -145,7 +145,7 @@ def test_fullscan_rules(monkeypatch):
     p = _prepared("fullscan", sc.case_fullscan, monkeypatch)
     sc.check_case_shape("fullscan", p[0], p[2], p[1])
     d = _run("fullscan", p, monkeypatch)
-    assert d.counters[13] >= 8  # open (file, rule) pairs
+    assert d.counters[sm.CT_OPEN_PAIRS] >= 8  # open (file, rule) pairs
 
 
 def test_gates(monkeypatch):

@@ -175,7 +175,7 @@ def _cand_of(d, model, rule_id):
 
 def _drop_hit(d, model):
     d.hits.pop(1)
-    d.counters[0] -= 1
+    d.counters[sm.CT_HITS] -= 1
 
 
 def _move_hit(d, model):
@@ -209,7 +209,7 @@ def _field(name, index, delta=None, value=None):
 
 def _remove_cand(d, model):
     d.cands = np.delete(d.cands, _cand_of(d, model, "slack-web-hook"))
-    d.counters[1] -= 1
+    d.counters[sm.CT_CANDS] -= 1
 
 
 def _narrow(d, model):
@@ -234,16 +234,16 @@ def _bump(attr, index, delta):
 
 def _drop_block(d, model):
     d.recs = d.recs[1:]
-    d.counters[7] -= 1
+    d.counters[sm.CT_RECS] -= 1
 
 
 def _dup_block(d, model):
     d.recs = np.concatenate([d.recs, d.recs[:1]])
-    d.counters[7] += 1
+    d.counters[sm.CT_RECS] += 1
 
 
 def _overflow(d, model):
-    d.counters[3] = 1
+    d.counters[sm.CT_HIT_OVF] = 1
 
 
 CORRUPTIONS = {

@@ -508,6 +508,7 @@ int tsg_debug_engine_stages(const tsg_compiled* c, int device, const uint8_t* ar
     return -1;
   }
   out->kw_words = d.kw_words;
+  static_assert(sizeof(out->counters) == tsg::kScanCtrBytes, "tsg_debug_stage_dump hands out the scan counters whole");
   std::memcpy(out->counters, d.counters, sizeof(out->counters));
   out->caps[0] = d.hit_cap;
   out->caps[1] = d.rec_cap;
@@ -531,6 +532,16 @@ int tsg_debug_engine_stages(const tsg_compiled* c, int device, const uint8_t* ar
   put(out->recs, out->recs_cap, &out->n_recs, d.recs.data(), d.recs.size(), 4);
   put(out->cands, out->cands_cap, &out->n_cands, d.cands.data(), d.cands.size(), sizeof(tsg::Candidate));
   return 0;
+}
+
+int tsg_debug_scan_grow(const uint32_t* counters, const uint32_t* fs_counters, uint32_t caps[7]) {
+  static_assert(tsg::kScanCtrWords == 16 && tsg::kNFsCtr == 6, "the sizes tsg_debug.h states");
+  tsg::ScanCaps c;
+  uint32_t* const field[7] = {&c.hit, &c.cand, &c.rec, &c.fold, &c.fs_pair, &c.fs_task, &c.fs_task_bytes};
+  for (int i = 0; i < 7; i++) *field[i] = caps[i];
+  const int which = tsg::GrowOverflowed(counters, fs_counters, &c);
+  for (int i = 0; i < 7; i++) caps[i] = *field[i];
+  return which;
 }
 
 int tsg_debug_pool_budget(void) { return tsg::PoolBudget(); }

@@ -14,6 +14,7 @@
 
 #include "fetch_layout.h"
 #include "rules.h"
+#include "scan_layout.h"
 
 namespace tsg {
 
@@ -131,15 +132,24 @@ struct StageHit {
   uint64_t end;        // the literal's end, file-relative
 };
 struct StageDump {
-  uint32_t counters[16] = {};
+  uint32_t counters[kScanCtrWords] = {};  // scan_layout.h kCt*
   uint32_t kw_words = 0, hit_cap = 0, rec_cap = 0, cand_cap = 0;
-  std::vector<StageHit> hits;        // min(counters[0], hit_cap)
+  std::vector<StageHit> hits;        // min(counters[kCtHits], hit_cap)
   std::vector<uint32_t> kw;          // n_files x kw_words
   std::vector<uint32_t> flags;       // n_files
   std::vector<uint16_t> nl;          // '\n' per 1-KiB chunk, ceil(n_bytes / kChunk)
-  std::vector<uint32_t> recs;        // min(counters[7], rec_cap) flagged 16-B block indices
+  std::vector<uint32_t> recs;        // min(counters[kCtRecs], rec_cap) flagged 16-B block indices
   std::vector<uint32_t> chunk_file;  // ceil(n_bytes / kChunk)
-  std::vector<Candidate> cands;      // all counters[1], kCandDrop ones included
+  std::vector<Candidate> cands;      // all counters[kCtCands], kCandDrop ones included
+};
+
+// The timing events of one scan's GPU phase (EnqueuePhase records them).
+struct PhaseEvents {
+  hipEvent_t ev[kNScanEv] = {};  // on the engine stream (scan_layout.h kEv*)
+  hipEvent_t ev_fs = nullptr;    // before the full scan (scans with full-scan rules)
+  hipEvent_t ev_k0[2] = {};      // the K0 phase's span on the stream it ran on
+  bool Create();
+  void Destroy();
 };
 
 // Files whose bytes the result does not need: d_skip[f] != 0
@@ -253,10 +263,6 @@ class GpuEngine {
   void* TakeFetchBuf(size_t need, size_t* cap);
   void GiveFetchBuf(void* p, size_t cap);
 
-  // Device buffers of the last run (for tests / bench).
-  hipEvent_t ev_scan0() const { return ev_[1]; }
-  hipEvent_t ev_scan1() const { return ev_[2]; }
-
  private:
   bool Ensure(void** p, size_t* cap, size_t need);
   // The buffers a scan's K0 phase writes before its K1 may start, or the
@@ -269,19 +275,15 @@ class GpuEngine {
   struct WorkSet {
     void* chunk_file = nullptr; size_t cap_chunk_file = 0;
     // scans with a skip list: the kept-tile bitmap, the runs of kept tiles (begin tile, kept tiles before),
-    // and 16 counters: [0] runs [1] kept tiles [2] last tile kept [3] files marked [4,5] their bytes (u64)
-    // [6] most runs walked by a K1 wave [7] tiles
+    // and the skip-list counters (scan_layout.h kSk*)
     void* keep_bits = nullptr; size_t cap_keep_bits = 0;
     void* runs = nullptr; size_t cap_runs = 0;
     uint32_t* skip_info = nullptr;
     void* kw = nullptr; size_t cap_kw = 0;
     void* flags = nullptr; size_t cap_flags = 0;
     void* cands = nullptr; size_t cap_cands = 0;
-    uint32_t* counters = nullptr;  // [0] hits [1] cands [2] special files [3] hit overflow [4] cand overflow
-                                   // [7] flagged-block records [8] record overflow
-                                   // [9] fold sites [10] fold-site overflow
-                                   // [6] full-scan list overflow [11] anchor-item matches [13] open pairs
-    uint32_t* fs_ctr = nullptr;    // [0] pairs [1..4] tasks [5] wave pairs
+    uint32_t* counters = nullptr;  // the scan counters (scan_layout.h kCt*)
+    uint32_t* fs_ctr = nullptr;    // the full-scan list counters (scan_layout.h kFs*)
     // free_ev: the last read of the set by the scan that used it (recorded beside Slot::done);
     // k0_done: the last K0 phase that filled it on aux_stream_.  *_rec: recorded at least once.
     hipEvent_t free_ev = nullptr, k0_done = nullptr;
@@ -293,22 +295,20 @@ class GpuEngine {
   hipStream_t aux_stream_ = nullptr;     // K0 phases of Enqueue'd scans (highest priority; TSG_OVERLAP_K0=0: unused)
   hipStream_t rb_stream_ = nullptr;      // counter / candidate read-back of Enqueue'd scans (TSG_READBACK_STREAM=0: unused)
   bool overlap_k0_ = true, readback_stream_ = true;
-  hipEvent_t ev_k0_[2] = {};             // Run's K0 span (Slot::ev_k0 for Enqueue'd scans)
   // The end of the last K2 enqueued on stream_: a K0 phase on aux_stream_ starts behind it, beside the
   // latency-bound fold / verify / finalize kernels, never beside K1 or K2 (§4.10: launched together with
   // a K1, K0's workgroups take wave slots first and leave K1's two workgroups per CU unevenly placed for
   // the whole kernel; beside K2 it costs K2 what it saves).
   hipEvent_t k2_done_ = nullptr;
   bool k2_rec_ = false;
+  struct KernelArgs;  // fills the kernels' parameter structs for EnqueuePhase (engine.hip, with their types)
   bool EnsureSets(uint64_t n_chunks, uint32_t n_files, uint64_t f_tiles, bool skip);
   bool EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
-                    uint64_t n_chunks, WorkSet& W, bool k0_aux, hipEvent_t* ev, hipEvent_t ev_fs, hipEvent_t* ev_k0,
-                    const SkipIn* skip = nullptr);
+                    uint64_t n_chunks, WorkSet& W, bool k0_aux, PhaseEvents& E, const SkipIn* skip = nullptr);
   void InitCaps(uint64_t n_bytes);
   struct Slot {  // one in-flight Enqueue: its phase events and pinned read-back buffers
-    hipEvent_t ev[7] = {};
-    hipEvent_t ev_fs = nullptr, done = nullptr;
-    hipEvent_t ev_k0[2] = {};    // the K0 phase's span on the stream it ran on
+    PhaseEvents ev;
+    hipEvent_t done = nullptr;
     hipEvent_t fin = nullptr, rb_done = nullptr;  // finalize done (stream_) / read-back done (rb_stream_)
     uint32_t* h_cnt = nullptr;
     uint32_t* h_skip = nullptr;  // pinned copy of the skip counters (WorkSet::skip_info), scans with a skip list
@@ -402,7 +402,7 @@ class GpuEngine {
   std::string err_;
   int device_ = 0;
   hipStream_t stream_ = nullptr;
-  hipEvent_t ev_[7] = {};  // K0 | K1 | confirm | fold | verify+fullscan | finalize
+  PhaseEvents run_ev_;  // Run's (Slot::ev for Enqueue'd scans)
   // tables
   uint32_t diag_mode_ = 0, diag_confirm_ = 0;
   AnchorInfo* d_anchors_ = nullptr;
@@ -444,7 +444,7 @@ class GpuEngine {
   size_t fold_stage_bytes_ = 0;
   uint32_t n_fclasses_ = 0;
   void* d_recs_ = nullptr; size_t cap_recs_ = 0;
-  uint32_t rec_cap_ = 0, fold_cap_ = 0, n_fitems_ = 0;
+  uint32_t n_fitems_ = 0;
   // per-batch buffers
   void* d_nl_ = nullptr; size_t cap_nl_ = 0;
   uint32_t* h_run_skip_ = nullptr;  // pinned skip counters (Run)
@@ -509,14 +509,11 @@ class GpuEngine {
   void* d_gbuf_ = nullptr; size_t cap_gbuf_ = 0;
   hipEvent_t ev_x_[2] = {};
   uint64_t chunk_bytes_ = uint64_t(1) << 30;             // TSG_INGEST_CHUNK_MB
-  uint32_t hit_cap_ = 0, cand_cap_ = 0;
+  ScanCaps caps_;                     // the list capacities (InitCaps; Run grows them after an overflow)
   uint32_t fs_chunk_ = 65536;         // TSG_FULLSCAN_CHUNK: full-scan bytes per lane (min, wave-wide pairs)
-  uint32_t fs_task_bytes_ = 4096;     // TSG_FS_TASK_BYTES: full-scan lane task size (min; >= 8 x max_len)
-  uint32_t fs_pair_cap_ = 0, fs_task_cap_ = 0;
   void* d_fs_pairs_ = nullptr; size_t cap_fs_pairs_ = 0;  // FsPair list
   void* d_fs_tasks_ = nullptr; size_t cap_fs_tasks_ = 0;  // 4 x FsTask lists (by NFA width)
   void* d_fs_wave_ = nullptr; size_t cap_fs_wave_ = 0;    // pairs run wave-wide
-  hipEvent_t ev_fs_ = nullptr;
   hipEvent_t ev_sync_ = nullptr;  // blocking-sync: the host waits asleep, not spinning
   bool blocking_sync_ = true;
   uint32_t verify_blocks_ = 4096;  // a lane per deferred hit (0.59 -> 0.51 ms vs 2048 on C2)

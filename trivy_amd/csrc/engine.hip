@@ -76,9 +76,9 @@ struct ClearParams {
   uint32_t* flags;     // n_files
   uint32_t* kw;        // n_files x kw_words
   uint64_t n_kw;       // words of kw
-  uint32_t* counters;  // 16
-  uint32_t* fs_ctr;    // 16, or null
-  uint32_t* skip_info; // 16, or null (scans with a skip list)
+  uint32_t* counters;  // kScanCtrWords
+  uint32_t* fs_ctr;    // kScanCtrWords, or null
+  uint32_t* skip_info; // kScanCtrWords, or null (scans with a skip list)
 };
 __device__ __forceinline__ void clear_words(uint32_t* p, uint64_t n, uint64_t tid, uint64_t nthr) {
   // hipMalloc'd buffers are 256-B aligned: 16-B stores, the last n % 4 words singly
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) void chunk_map_kernel(const uint64_t* __restri
     const uint64_t tid = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x, nthr = uint64_t(gridDim.x) * blockDim.x;
     clear_words(Z.flags, n_files, tid, nthr);
     clear_words(Z.kw, Z.n_kw, tid, nthr);
-    if (tid < 16) {
+    if (tid < kScanCtrWords) {
       Z.counters[tid] = 0;
       if (Z.fs_ctr) Z.fs_ctr[tid] = 0;
       if (Z.skip_info) Z.skip_info[tid] = 0;
@@ -174,9 +174,7 @@ static_assert(kFChunks * kChunk == kFTile && kFChunks == 4, "a tile's newline co
 // ---------------------------------------------------------------------------
 // Scans with a skip list: the tiles K1 streams
 // ---------------------------------------------------------------------------
-// Counters of such a scan (engine.h WorkSet::skip_info), cleared by K0.
-constexpr uint32_t kSkRuns = 0, kSkKept = 1, kSkTailKept = 2, kSkFiles = 3, kSkBytes = 4 /* u64: 4, 5 */,
-                   kSkWaveRuns = 6, kSkTiles = 7;
+// Counters of such a scan: WorkSet::skip_info, slots kSk* (scan_layout.h), cleared by K0.
 
 // The bitmap's words, rounded up to whole 64-B groups (tile_runs_kernel reads a group per step).
 constexpr uint32_t kRunWords = 8;
@@ -471,11 +469,11 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
   };
   auto flush = [&]() {  // wave-uniform
     uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(&P.counters[7], qn);
+    if (lane == 0) base = atomicAdd(&P.counters[kCtRecs], qn);
     base = __builtin_amdgcn_readfirstlane(base);
     for (uint32_t i = lane; i < qn; i += 64) {
       if (base + i < P.rec_cap) P.recs[base + i] = Q[i];
-      else P.counters[8] = 1;
+      else P.counters[kCtRecOvf] = 1;
     }
     qn = 0;
   };
@@ -519,13 +517,13 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
         qn += total;
       } else {  // a group denser than the queue: straight to the global list
         uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&P.counters[7], total);
+        if (lane == 0) base = atomicAdd(&P.counters[kCtRecs], total);
         uint32_t at = __builtin_amdgcn_readfirstlane(base) + incl - cnt;
         while (m) {
           const uint32_t b = uint32_t(__builtin_ctz(m));
           m &= m - 1;
           if (at < P.rec_cap) P.recs[at] = rec0 + ((b >> 2) << 8) + (b & 3u);
-          else P.counters[8] = 1;
+          else P.counters[kCtRecOvf] = 1;
           at++;
         }
       }
@@ -775,7 +773,7 @@ struct NfaParams {
 // (then a closed gate is not MatchKeywords == false): files holding them,
 // unless kwfold_kernel covered every fold site.
 __device__ __forceinline__ bool kw_bits_inexact(const NfaParams& P, uint32_t f) {
-  return (P.flags[f] & 4u) && !(P.kw_fold && P.counters[10] == 0);
+  return (P.flags[f] & 4u) && !(P.kw_fold && P.counters[kCtFoldOvf] == 0);
 }
 
 
@@ -854,13 +852,13 @@ __device__ __forceinline__ void stage_hit(uint32_t* hbuf, uint32_t* hcnt, uint32
     hbuf[3 * k + 2] = hit_aid_word(aid, end);
     return;
   }
-  const uint32_t g = atomicAdd(&counters[0], 1u);
+  const uint32_t g = atomicAdd(&counters[kCtHits], 1u);
   if (g < cap) {
     hits[3ull * g + 0] = f;
     hits[3ull * g + 1] = uint32_t(end);
     hits[3ull * g + 2] = hit_aid_word(aid, end);
   } else {
-    counters[3] = 1;
+    counters[kCtHitOvf] = 1;
   }
 }
 
@@ -872,7 +870,7 @@ __device__ __forceinline__ void flush_staged(uint32_t* hbuf, uint32_t* hcnt, uin
   const uint32_t n = n_all < kCWaveHits ? n_all : kCWaveHits;
   if (n) {
     uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(&counters[0], n);
+    if (lane == 0) base = atomicAdd(&counters[kCtHits], n);
     base = __builtin_amdgcn_readfirstlane(base);
     for (uint32_t i = lane; i < n; i += 64) {
       if (base + i < cap) {
@@ -880,7 +878,7 @@ __device__ __forceinline__ void flush_staged(uint32_t* hbuf, uint32_t* hcnt, uin
         hits[3ull * (base + i) + 1] = hbuf[3 * i + 1];
         hits[3ull * (base + i) + 2] = hbuf[3 * i + 2];
       } else {
-        counters[3] = 1;
+        counters[kCtHitOvf] = 1;
       }
     }
   }
@@ -891,13 +889,13 @@ __device__ __forceinline__ void flush_staged(uint32_t* hbuf, uint32_t* hcnt, uin
 
 __device__ __forceinline__ void put_hit(uint32_t* hits, uint32_t cap, uint32_t* counters, uint32_t f, uint64_t end,
                                         uint32_t aid) {
-  const uint32_t g = wave_slot(&counters[0]);
+  const uint32_t g = wave_slot(&counters[kCtHits]);
   if (g < cap) {
     hits[3ull * g + 0] = f;
     hits[3ull * g + 1] = uint32_t(end);
     hits[3ull * g + 2] = hit_aid_word(aid, end);
   } else {
-    counters[3] = 1;
+    counters[kCtHitOvf] = 1;
   }
 }
 // Follow requirements of an anchor hit (rules.h FollowLut), on registers.
@@ -1090,7 +1088,7 @@ __device__ int nfa_dispatch_abs(int words, const uint8_t* arena, uint64_t fs, in
 // filled by the finalize kernel once the keyword bits are final.
 __device__ __forceinline__ void put_candidate(Candidate* cands, uint32_t cap, uint32_t* counters, uint32_t f,
                                               uint32_t r, int64_t wlo, int64_t whi) {
-  const uint32_t k = atomicAdd(&counters[1], 1u);
+  const uint32_t k = atomicAdd(&counters[kCtCands], 1u);
   if (k < cap) {
     Candidate c;
     c.file = f;
@@ -1104,7 +1102,7 @@ __device__ __forceinline__ void put_candidate(Candidate* cands, uint32_t cap, ui
     c.pad_ = 0;
     cands[k] = c;
   } else {
-    counters[4] = 1;
+    counters[kCtCandOvf] = 1;
   }
 }
 
@@ -1226,7 +1224,7 @@ __global__ __launch_bounds__(ConfirmThreads<kLdsTabs>(), TSG_C_MINW) void confir
   uint32_t* q1 = s_q1 + wave * kCQ1;
   uint32_t* q2 = s_q2 + wave * kCQ2;
   uint32_t* hbuf = s_hbuf + wave * kCWaveHits * 3;
-  const uint32_t n_recs = P.counters[7] < P.rec_cap ? P.counters[7] : P.rec_cap;
+  const uint32_t n_recs = P.counters[kCtRecs] < P.rec_cap ? P.counters[kCtRecs] : P.rec_cap;
   uint32_t n_anchor = 0;  // anchor-item matches of this lane (stats; summed once per wave at the end)
   // phase C for one queued candidate: item `ix` whose window ends at lane l's block + k
   auto check_item = [&](uint32_t l, uint32_t k, uint32_t ix, uint32_t full) {
@@ -1299,10 +1297,10 @@ __global__ __launch_bounds__(ConfirmThreads<kLdsTabs>(), TSG_C_MINW) void confir
     if (it.kind == kItemFold) {
       // bit0: widen anchor offsets; bit1: U+017F; bit2: U+0130 / U+212A (lower into ASCII)
       const uint32_t fl = item_ids[it.ids_off] == 2 ? 3u : 5u;
-      if (atomicOr(&P.flags[f], fl) == 0) atomicAdd(&P.counters[2], 1u);  // files with fold runes
-      const uint32_t q = atomicAdd(&P.counters[9], 1u);
+      if (atomicOr(&P.flags[f], fl) == 0) atomicAdd(&P.counters[kCtSpecial], 1u);  // files with fold runes
+      const uint32_t q = atomicAdd(&P.counters[kCtFolds], 1u);
       if (q < P.fold_cap) P.folds[q] = FoldSite{s0, f, it.n};
-      else P.counters[10] = 1;
+      else P.counters[kCtFoldOvf] = 1;
       return;
     }
     if (P.item_diag) atomicAdd(&P.item_diag[2 * ix], 1u);
@@ -1530,7 +1528,7 @@ __global__ __launch_bounds__(ConfirmThreads<kLdsTabs>(), TSG_C_MINW) void confir
   flush_staged(hbuf, &cnt[0], P.hits, P.hit_cap, P.counters, lane);
 #pragma unroll
   for (int x = 32; x >= 1; x >>= 1) n_anchor += __shfl_xor(n_anchor, x);
-  if (lane == 0 && n_anchor) atomicAdd(&P.counters[11], n_anchor);  // anchor-item matches (stats)
+  if (lane == 0 && n_anchor) atomicAdd(&P.counters[kCtAnchorHits], n_anchor);  // anchor-item matches (stats)
 }
 
 // TSG_K2_PACK experiment: the 48-B window of every flagged
@@ -1542,7 +1540,7 @@ __global__ __launch_bounds__(256) void pack_windows_kernel(const uint8_t* __rest
                                                            const uint32_t* __restrict__ recs, uint32_t rec_cap,
                                                            const uint32_t* __restrict__ counters,
                                                            uint8_t* __restrict__ wins) {
-  const uint32_t n_recs = counters[7] < rec_cap ? counters[7] : rec_cap;
+  const uint32_t n_recs = counters[kCtRecs] < rec_cap ? counters[kCtRecs] : rec_cap;
   for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n_recs; r += gridDim.x * blockDim.x) {
     const uint64_t base = uint64_t(recs[r]) * 16;
     const uint64_t w0 = base >= 16 ? base - 16 : 0;
@@ -1719,7 +1717,7 @@ void fold_kernel(FoldParams P) {
   __shared__ uint32_t s_coop[kWaves];     // per wave: 0, or 1 | (U+212A ? 2 : 0) | (capable tasks ? 4 : 0) for a cooperative site
   __shared__ uint32_t s_coop_f[kWaves];   // its file
   __shared__ uint32_t s_total[kWaves];    // a heavy capable-task site's indexed task count (| 4 in s_coop)
-  const uint32_t n_folds = P.counters[9] < P.fold_cap ? P.counters[9] : P.fold_cap;
+  const uint32_t n_folds = P.counters[kCtFolds] < P.fold_cap ? P.counters[kCtFolds] : P.fold_cap;
   for (uint32_t base = blockIdx.x * kWaves; base < n_folds; base += gridDim.x * kWaves) {
     const uint32_t si = base + wave;
     uint32_t coop = 0;  // wave-uniform
@@ -1903,7 +1901,7 @@ __global__ __launch_bounds__(64 * kFoldWaves) void kwfold_kernel(KwFoldParams P)
   auto in_cls = [&](uint32_t c, uint32_t b) { return (classes[c * 8 + (b >> 5)] >> (b & 31)) & 1u; };
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   uint8_t* wb = s_win[wave];
-  const uint32_t n_folds = P.counters[9] < P.fold_cap ? P.counters[9] : P.fold_cap;
+  const uint32_t n_folds = P.counters[kCtFolds] < P.fold_cap ? P.counters[kCtFolds] : P.fold_cap;
   for (uint32_t si = blockIdx.x * kFoldWaves + wave; si < n_folds; si += gridDim.x * kFoldWaves) {
     const FoldSite fsite = P.folds[si];
     const uint64_t fs = P.off[fsite.f], fe = P.off[fsite.f + 1];
@@ -1984,7 +1982,7 @@ __device__ uint32_t gate_flags(const NfaParams& P, const RuleGpu& rg, uint32_t f
 // from wlo with injection up to whi, reading the arena 16 B at a time; an
 // accept emits the candidate with the line count before wlo.
 __global__ __launch_bounds__(256, 6) void verify_hits_kernel(NfaParams P) {
-  const uint32_t n = P.counters[0] < P.hit_cap ? P.counters[0] : P.hit_cap;
+  const uint32_t n = P.counters[kCtHits] < P.hit_cap ? P.counters[kCtHits] : P.hit_cap;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     uint32_t f, aid;
     uint64_t end;
@@ -2199,13 +2197,14 @@ struct FsPair {
 struct FsTask {
   uint32_t pair, chunk;
 };
+static_assert(sizeof(FsTask) == kFsTaskRecBytes, "scan_layout.h sizes the task lists' growth by it");
 struct FsLists {
   FsPair* pairs;
   uint32_t pair_cap;
   FsTask* tasks;  // list w (NFA words w + 1) at tasks + w * task_cap
   uint32_t task_cap;
   uint32_t* wave_pairs;  // pair indices run wave-wide (pair_cap entries)
-  uint32_t* ctr;         // [0] pairs [1..4] tasks per NFA width [5] wave pairs
+  uint32_t* ctr;         // scan_layout.h kFs*
   uint32_t task_min;     // TSG_FS_TASK_BYTES
 };
 constexpr uint32_t kFsLaneMaxLen = 8192;  // longer bounded matches: the wave path (a lane would own >= 64 KiB)
@@ -2223,14 +2222,14 @@ __global__ __launch_bounds__(256) void fs_pairs_kernel(NfaParams P, FsLists Q) {
                 (gate_flags(P, rg, f) & kCandGateOpen);
     const uint64_t len = P.off[f + 1] - P.off[f];
     if (!open || len == 0) continue;
-    atomicAdd(&P.counters[13], 1u);  // open pairs (stats)
+    atomicAdd(&P.counters[kCtOpenPairs], 1u);  // open pairs (stats)
     if (rg.nfa_words == 0) {  // the relaxed NFA accepts at once: the whole file
       put_candidate(P.cands, P.cand_cap, P.counters, f, r, 0, int64_t(len));
       continue;
     }
-    const uint32_t p = atomicAdd(&Q.ctr[0], 1u);
+    const uint32_t p = atomicAdd(&Q.ctr[kFsPairs], 1u);
     if (p >= Q.pair_cap) {
-      P.counters[6] = 1;  // grow and rescan (GpuEngine::Run)
+      P.counters[kCtFsOvf] = 1;  // grow and rescan (GpuEngine::Run)
       continue;
     }
     uint32_t tb = 0;
@@ -2239,13 +2238,13 @@ __global__ __launch_bounds__(256) void fs_pairs_kernel(NfaParams P, FsLists Q) {
       tb = (tb + 15u) & ~15u;
       const uint32_t n = uint32_t((len + tb - 1) / tb);
       const uint32_t w = rg.nfa_words - 1u;
-      const uint32_t base = atomicAdd(&Q.ctr[1 + w], n);
+      const uint32_t base = atomicAdd(&Q.ctr[kFsTasks + w], n);
       for (uint32_t i = 0; i < n; i++) {
         if (base + i < Q.task_cap) Q.tasks[uint64_t(w) * Q.task_cap + base + i] = FsTask{p, i};
-        else P.counters[6] = 1;
+        else P.counters[kCtFsOvf] = 1;
       }
     } else {
-      Q.wave_pairs[atomicAdd(&Q.ctr[5], 1u)] = p;  // <= pairs <= pair_cap
+      Q.wave_pairs[atomicAdd(&Q.ctr[kFsWavePairs], 1u)] = p;  // <= pairs <= pair_cap
     }
     Q.pairs[p] = FsPair{f, r, tb, 0};
   }
@@ -2357,7 +2356,7 @@ __global__ __launch_bounds__(256) void fs_task_kernel(NfaParams P, FsLists Q) {
   uint32_t n[4], total = 0;
 #pragma unroll
   for (int w = 0; w < 4; w++) {
-    n[w] = Q.ctr[1 + w] < Q.task_cap ? Q.ctr[1 + w] : Q.task_cap;
+    n[w] = Q.ctr[kFsTasks + w] < Q.task_cap ? Q.ctr[kFsTasks + w] : Q.task_cap;
     total += n[w];
   }
   const uint32_t stride = gridDim.x * blockDim.x;
@@ -2390,7 +2389,7 @@ __global__ __launch_bounds__(256) void fs_task_kernel(NfaParams P, FsLists Q) {
 __global__ __launch_bounds__(256) void fs_wave_kernel(NfaParams P, FsLists Q) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t n_waves = gridDim.x * (blockDim.x / 64);
-  const uint32_t n = Q.ctr[5] < Q.pair_cap ? Q.ctr[5] : Q.pair_cap;
+  const uint32_t n = Q.ctr[kFsWavePairs] < Q.pair_cap ? Q.ctr[kFsWavePairs] : Q.pair_cap;
   for (uint32_t k = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); k < n; k += n_waves) {
     const FsPair pr = Q.pairs[Q.wave_pairs[k]];
     const RuleGpu rg = P.rules[pr.r];
@@ -2416,7 +2415,7 @@ __global__ __launch_bounds__(256) void fs_wave_kernel(NfaParams P, FsLists Q) {
 // window deep in a 10-MiB file spans ~10^4 chunks), lanes 0 / 1 the partial
 // chunks at either end.
 __global__ __launch_bounds__(256) void finalize_kernel(NfaParams P) {
-  const uint32_t n = P.counters[1] < P.cand_cap ? P.counters[1] : P.cand_cap;
+  const uint32_t n = P.counters[kCtCands] < P.cand_cap ? P.counters[kCtCands] : P.cand_cap;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t n_waves = gridDim.x * (blockDim.x / 64);
   for (uint32_t i = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); i < n; i += n_waves) {
@@ -2589,7 +2588,7 @@ GpuEngine::GpuEngine(const CompiledRules& cr, int device) : device_(device) {
     for (WorkSet& W : sets_)
       ok = ok && hipEventCreateWithFlags(&W.free_ev, hipEventDisableTiming) == hipSuccess &&
            hipEventCreateWithFlags(&W.k0_done, hipEventDisableTiming) == hipSuccess;
-    for (auto& e : ev_k0_) ok = ok && hipEventCreate(&e) == hipSuccess;
+    ok = ok && run_ev_.Create();
     ok = ok && hipEventCreateWithFlags(&k2_done_, hipEventDisableTiming) == hipSuccess;
     if (!ok) {
       err_ = "hipStreamCreate / hipEventCreate failed (K0 and read-back streams)";
@@ -2608,15 +2607,13 @@ GpuEngine::GpuEngine(const CompiledRules& cr, int device) : device_(device) {
       SetFetchSizes(sm ? uint64_t(std::max(1ll, std::atoll(sm))) << 20 : fetch_stage_bytes_.load(),
                     dm ? uint64_t(std::max(1ll, std::atoll(dm))) << 20 : fetch_direct_bytes_.load());
   }
-  for (auto& e : ev_) hipEventCreate(&e);
   if (const char* dm = std::getenv("TSG_DIAG_SCAN")) diag_mode_ = uint32_t(std::atoi(dm));
   if (const char* dc = std::getenv("TSG_DIAG_CONFIRM")) diag_confirm_ = uint32_t(std::atoi(dc));
   if (const char* kg = std::getenv("TSG_DIAG_K1_GRID")) k1_grid_cap_ = uint32_t(std::max(0, std::atoi(kg)));
   if (const char* di = std::getenv("TSG_DIAG_ITEMS")) item_diag_path_ = di;
   if (const char* fc = std::getenv("TSG_FULLSCAN_CHUNK")) fs_chunk_ = uint32_t(std::atoi(fc));
   if (fs_chunk_ < 64) fs_chunk_ = 64;
-  if (const char* tb = std::getenv("TSG_FS_TASK_BYTES")) fs_task_bytes_ = uint32_t(std::max(16, std::atoi(tb)));
-  hipEventCreate(&ev_fs_);
+  if (const char* tb = std::getenv("TSG_FS_TASK_BYTES")) caps_.fs_task_bytes = uint32_t(std::max(16, std::atoi(tb)));
   // the kernels of one scan run ~10 ms: a thread spinning on the stream for
   // that long takes a core from the host pool scanning the previous batch
   hipEventCreateWithFlags(&ev_sync_, hipEventBlockingSync | hipEventDisableTiming);
@@ -2642,7 +2639,7 @@ GpuEngine::GpuEngine(const CompiledRules& cr, int device) : device_(device) {
       !Upload(&err_, &d_fullscan_rules_, fullscan_rules_.data(), fullscan_rules_.size()))
     return;
   for (WorkSet& W : sets_)
-    if (hipMalloc(&W.counters, 64) != hipSuccess || hipMalloc(&W.fs_ctr, 64) != hipSuccess) {
+    if (hipMalloc(&W.counters, kScanCtrBytes) != hipSuccess || hipMalloc(&W.fs_ctr, kScanCtrBytes) != hipSuccess) {
       err_ = "hipMalloc counters";
       return;
     }
@@ -2956,8 +2953,7 @@ GpuEngine::~GpuEngine() {
     if (W.free_ev) hipEventDestroy(W.free_ev);
     if (W.k0_done) hipEventDestroy(W.k0_done);
   }
-  for (auto& e : ev_k0_)
-    if (e) hipEventDestroy(e);
+  run_ev_.Destroy();
   if (k2_done_) hipEventDestroy(k2_done_);
   for (int b = 0; b < kNStage; b++)
   {
@@ -2965,18 +2961,12 @@ GpuEngine::~GpuEngine() {
       if (p) hipFree(p);
     if (h_gsrc_[b]) hipHostFree(h_gsrc_[b]);
   }
-  for (auto& e : ev_)
-    if (e) hipEventDestroy(e);
   for (auto& e : ev_copied_)
     if (e) hipEventDestroy(e);
-  if (ev_fs_) hipEventDestroy(ev_fs_);
   if (ev_sync_) hipEventDestroy(ev_sync_);
   for (auto& S : slots_) {
-    for (auto& e : S.ev)
-      if (e) hipEventDestroy(e);
-    if (S.ev_fs) hipEventDestroy(S.ev_fs);
-    if (S.done) hipEventDestroy(S.done);
-    for (hipEvent_t e : {S.ev_k0[0], S.ev_k0[1], S.fin, S.rb_done})
+    S.ev.Destroy();
+    for (hipEvent_t e : {S.done, S.fin, S.rb_done})
       if (e) hipEventDestroy(e);
     if (S.h_cnt) hipHostFree(S.h_cnt);
     if (S.h_skip) hipHostFree(S.h_skip);
@@ -3082,7 +3072,7 @@ void GpuEngine::ReaperLoop() {
 }
 
 GpuEngine::HostMemInfo GpuEngine::host_mem_info() {
-  HostMemInfo m{retired_pending_.load(), retired_freed_.load(), cand_cap_, 0};
+  HostMemInfo m{retired_pending_.load(), retired_freed_.load(), caps_.cand, 0};
   std::lock_guard<std::mutex> g(slot_mu_);
   for (const auto& S : slots_) m.slot_bytes += uint64_t(S.h_cap) * sizeof(Candidate);
   return m;
@@ -3554,12 +3544,51 @@ hipError_t GpuEngine::WaitStream() {
 }
 
 void GpuEngine::InitCaps(uint64_t n_bytes) {
-  if (hit_cap_ == 0) hit_cap_ = uint32_t(std::min<uint64_t>(std::max<uint64_t>(n_bytes / 512, 1 << 16), 1u << 28));
-  if (cand_cap_ == 0) cand_cap_ = 1 << 16;
-  if (rec_cap_ == 0) rec_cap_ = uint32_t(std::min<uint64_t>(std::max<uint64_t>(n_bytes / 128, 1 << 16), 1u << 30));
-  if (fold_cap_ == 0) fold_cap_ = 1 << 16;
-  if (fs_pair_cap_ == 0) fs_pair_cap_ = 1 << 14;
-  if (fs_task_cap_ == 0) fs_task_cap_ = 1 << 16;
+  if (caps_.hit == 0) caps_.hit = uint32_t(std::min<uint64_t>(std::max<uint64_t>(n_bytes / 512, 1 << 16), 1u << 28));
+  if (caps_.cand == 0) caps_.cand = 1 << 16;
+  if (caps_.rec == 0) caps_.rec = uint32_t(std::min<uint64_t>(std::max<uint64_t>(n_bytes / 128, 1 << 16), 1u << 30));
+  if (caps_.fold == 0) caps_.fold = 1 << 16;
+  if (caps_.fs_pair == 0) caps_.fs_pair = 1 << 14;
+  if (caps_.fs_task == 0) caps_.fs_task = 1 << 16;
+}
+
+bool PhaseEvents::Create() {
+  bool ok = hipEventCreate(&ev_fs) == hipSuccess;
+  for (auto& e : ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+  for (auto& e : ev_k0) ok = ok && hipEventCreate(&e) == hipSuccess;
+  return ok;
+}
+
+void PhaseEvents::Destroy() {
+  for (hipEvent_t e : ev)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : {ev_fs, ev_k0[0], ev_k0[1]})
+    if (e) (void)hipEventDestroy(e);
+}
+
+// What Run and Collect report of a finished scan: the statistics its counters
+// hold, and the spans between its phase events.
+static void NoteCounters(const uint32_t* cnt, BatchStats* st) {
+  st->hits = cnt[kCtAnchorHits];
+  st->follow_hits = cnt[kCtHits];  // the verify kernel's input
+  st->special_files = cnt[kCtSpecial];
+  st->flagged_blocks = cnt[kCtRecs];
+  st->fullscan_tasks = cnt[kCtOpenPairs];
+  st->fold_sites = cnt[kCtFolds];
+  st->hit_overflow = cnt[kCtHitOvf] != 0;
+  st->cand_overflow = cnt[kCtCandOvf] != 0;
+}
+
+static void NotePhaseTimes(const PhaseEvents& E, bool has_fs, BatchStats* st) {
+  hipEventElapsedTime(&st->ms_scan, E.ev[kEvK1], E.ev[kEvK2]);
+  hipEventElapsedTime(&st->ms_confirm, E.ev[kEvK2], E.ev[kEvFold]);
+  hipEventElapsedTime(&st->ms_careful, E.ev[kEvFold], E.ev[kEvVerify]);     // fold kernels
+  hipEventElapsedTime(&st->ms_verify, E.ev[kEvVerify], E.ev[kEvFinalize]);  // verify (deferred hits) + full scan
+  hipEventElapsedTime(&st->ms_finalize, E.ev[kEvFinalize], E.ev[kEvEnd]);
+  if (has_fs) hipEventElapsedTime(&st->ms_fullscan, E.ev_fs, E.ev[kEvFinalize]);
+  hipEventElapsedTime(&st->ms_chunkmap, E.ev[kEvStart], E.ev[kEvK1]);
+  hipEventElapsedTime(&st->ms_total, E.ev[kEvStart], E.ev[kEvEnd]);
+  hipEventElapsedTime(&st->ms_k0, E.ev_k0[0], E.ev_k0[1]);
 }
 
 bool GpuEngine::Enqueue(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
@@ -3597,24 +3626,22 @@ bool GpuEngine::Enqueue(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t
   InitCaps(n_bytes);
   if (!S.done) {
     bool ok = hipEventCreateWithFlags(&S.done, hipEventBlockingSync | hipEventDisableTiming) == hipSuccess &&
-              hipEventCreate(&S.ev_fs) == hipSuccess &&
+              S.ev.Create() &&
               hipEventCreateWithFlags(&S.fin, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&S.rb_done, hipEventDisableTiming) == hipSuccess &&
-              hipHostMalloc(reinterpret_cast<void**>(&S.h_cnt), 64, hipHostMallocDefault) == hipSuccess;
-    for (auto& e : S.ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-    for (auto& e : S.ev_k0) ok = ok && hipEventCreate(&e) == hipSuccess;
+              hipHostMalloc(reinterpret_cast<void**>(&S.h_cnt), kScanCtrBytes, hipHostMallocDefault) == hipSuccess;
     if (!ok) {
       err_ = "ticket events / pinned counters";
       return fail();
     }
   }
-  const uint32_t n_copy = uint32_t(std::min<uint64_t>(cand_cap_, 2 * uint64_t(cand_recent_.load()) + 65536));
+  const uint32_t n_copy = uint32_t(std::min<uint64_t>(caps_.cand, 2 * uint64_t(cand_recent_.load()) + 65536));
   if (S.h_cap < n_copy) {
     // Sized to the device list's capacity (not to the copy, which follows the
     // recent counts): hipHostFree waits for the whole device, so a slot regrown
     // in a running pipeline stalled its submitting thread -- holding the GPU
     // lock -- for 11-19 ms and left the GPU idle 1.7 ms per regrowth
-    // (tools/drain_trace.py, profiles/r04h2).  It regrows only with cand_cap_,
+    // (tools/drain_trace.py, profiles/r04h2).  It regrows only with caps_.cand,
     // and the old buffer goes to the reaper thread (RetireHost), which frees it
     // outside the engine's locks.
     if (S.h_cands) RetireHost(S.h_cands);
@@ -3624,14 +3651,14 @@ bool GpuEngine::Enqueue(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t
       S.h_cap = 0;
     }
     Candidate* hc = nullptr;
-    if (hipHostMalloc(reinterpret_cast<void**>(&hc), size_t(cand_cap_) * sizeof(Candidate), hipHostMallocDefault) !=
+    if (hipHostMalloc(reinterpret_cast<void**>(&hc), size_t(caps_.cand) * sizeof(Candidate), hipHostMallocDefault) !=
         hipSuccess) {
       err_ = "hipHostMalloc failed for the candidate read-back";
       return fail();
     }
     std::lock_guard<std::mutex> g(slot_mu_);
     S.h_cands = hc;
-    S.h_cap = cand_cap_;
+    S.h_cap = caps_.cand;
   }
   uint64_t n_chunks = (n_bytes + kChunk - 1) / kChunk;
   if (n_chunks == 0) n_chunks = 1;
@@ -3671,15 +3698,14 @@ bool GpuEngine::Enqueue(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t
   }
   S.has_skip = skip && skip->d_skip && n_bytes > 0;
   if (S.has_skip && !S.h_skip &&
-      hipHostMalloc(reinterpret_cast<void**>(&S.h_skip), 64, hipHostMallocDefault) != hipSuccess) {
+      hipHostMalloc(reinterpret_cast<void**>(&S.h_skip), kScanCtrBytes, hipHostMallocDefault) != hipSuccess) {
     err_ = "pinned skip counters";
     return fail();
   }
   WorkSet& W = sets_[set_turn_];  // (4 slots, 2 sets: a slot and a set do not stay paired)
   set_turn_ = (set_turn_ + 1) % kSets;
   auto enqueue = [&]() -> bool {
-    if (!EnqueuePhase(d_arena, n_bytes, d_offsets, n_files, n_chunks, W, overlap_k0_, S.ev, S.ev_fs, S.ev_k0, skip))
-      return false;
+    if (!EnqueuePhase(d_arena, n_bytes, d_offsets, n_files, n_chunks, W, overlap_k0_, S.ev, skip)) return false;
     // The read-back, behind finalize: on a stream of its own, so the next scan's
     // K1 does not queue behind 64 B x n_copy of copies (TSG_READBACK_STREAM=0: on
     // the engine stream).  Not copy_stream_: the staging ring's H2D copies must
@@ -3690,8 +3716,8 @@ bool GpuEngine::Enqueue(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t
       HIP_OK(hipStreamWaitEvent(rb_stream_, S.fin, 0));
       rs = rb_stream_;
     }
-    HIP_OK(hipMemcpyAsync(S.h_cnt, W.counters, 64, hipMemcpyDeviceToHost, rs));
-    if (S.has_skip) HIP_OK(hipMemcpyAsync(S.h_skip, W.skip_info, 64, hipMemcpyDeviceToHost, rs));
+    HIP_OK(hipMemcpyAsync(S.h_cnt, W.counters, kScanCtrBytes, hipMemcpyDeviceToHost, rs));
+    if (S.has_skip) HIP_OK(hipMemcpyAsync(S.h_skip, W.skip_info, kScanCtrBytes, hipMemcpyDeviceToHost, rs));
     HIP_OK(hipMemcpyAsync(S.h_cands, W.cands, size_t(n_copy) * sizeof(Candidate), hipMemcpyDeviceToHost, rs));
     hipStream_t ds = rs;  // the stream whose tail ends the scan's last read of its set
     if (fetch) {
@@ -3757,23 +3783,19 @@ bool GpuEngine::Collect(Ticket* t, std::vector<Candidate>* cands, BatchStats* st
   st->bytes = S.n_bytes;
   st->files = S.n_files;
   const uint32_t* cnt = S.h_cnt;
-  for (uint32_t seen = cand_recent_.load(); cnt[1] > seen && !cand_recent_.compare_exchange_weak(seen, cnt[1]);) {
+  const uint32_t n_cands = cnt[kCtCands];
+  for (uint32_t seen = cand_recent_.load(); n_cands > seen && !cand_recent_.compare_exchange_weak(seen, n_cands);) {
   }
-  if (cnt[8] || cnt[10] || cnt[3] || cnt[4] || cnt[6] || cnt[1] > t->cand_copy) {  // an overflow: Run grows and rescans
+  if (OverflowedList(cnt) != kListNone || n_cands > t->cand_copy) {  // Run grows the list and rescans
     *rerun = true;
     release();
     return true;
   }
-  st->hits = cnt[11];
-  st->follow_hits = cnt[0];
-  st->special_files = cnt[2];
-  st->flagged_blocks = cnt[7];
-  st->fullscan_tasks = cnt[13];
-  st->fold_sites = cnt[9];
+  NoteCounters(cnt, st);
   if (S.has_skip) NoteSkip(S.h_skip, st);
   cands->clear();
-  cands->reserve(cnt[1]);
-  for (uint32_t i = 0; i < cnt[1]; i++)  // closed keyword gates (finalize_kernel) never reach the host
+  cands->reserve(n_cands);
+  for (uint32_t i = 0; i < n_cands; i++)  // closed keyword gates (finalize_kernel) never reach the host
     if (!(S.h_cands[i].flags & kCandDrop)) cands->push_back(S.h_cands[i]);
   st->candidates = cands->size();
   if (S.has_fetch && S.win) {  // the windows fetch: the plan restated from the candidates, checked, handed over
@@ -3871,15 +3893,7 @@ bool GpuEngine::Collect(Ticket* t, std::vector<Candidate>* cands, BatchStats* st
       return false;
     }
   }
-  hipEventElapsedTime(&st->ms_scan, S.ev[1], S.ev[2]);
-  hipEventElapsedTime(&st->ms_confirm, S.ev[2], S.ev[3]);
-  hipEventElapsedTime(&st->ms_careful, S.ev[3], S.ev[4]);
-  hipEventElapsedTime(&st->ms_verify, S.ev[4], S.ev[5]);
-  hipEventElapsedTime(&st->ms_finalize, S.ev[5], S.ev[6]);
-  if (S.has_fs) hipEventElapsedTime(&st->ms_fullscan, S.ev_fs, S.ev[5]);
-  hipEventElapsedTime(&st->ms_chunkmap, S.ev[0], S.ev[1]);
-  hipEventElapsedTime(&st->ms_total, S.ev[0], S.ev[6]);
-  hipEventElapsedTime(&st->ms_k0, S.ev_k0[0], S.ev_k0[1]);
+  NotePhaseTimes(S.ev, S.has_fs, st);
   release();
   return true;
 }
@@ -3894,22 +3908,189 @@ bool GpuEngine::EnsureSets(uint64_t n_chunks, uint32_t n_files, uint64_t f_tiles
           !Ensure(&W.runs, &W.cap_runs, (f_tiles / 2 + 2) * sizeof(uint2)))
         return false;
       if (!W.skip_info) {
-        HIP_OK(hipMalloc(reinterpret_cast<void**>(&W.skip_info), 64));
-        HIP_OK(hipMemset(W.skip_info, 0, 64));
+        HIP_OK(hipMalloc(reinterpret_cast<void**>(&W.skip_info), kScanCtrBytes));
+        HIP_OK(hipMemset(W.skip_info, 0, kScanCtrBytes));
       }
     }
     if (!Ensure(&W.chunk_file, &W.cap_chunk_file, n_chunks * 4) ||
         !Ensure(&W.kw, &W.cap_kw, size_t(n_files) * kw_words_ * 4) ||
         !Ensure(&W.flags, &W.cap_flags, size_t(n_files) * 4) ||
-        !Ensure(&W.cands, &W.cap_cands, size_t(cand_cap_) * sizeof(Candidate)))
+        !Ensure(&W.cands, &W.cap_cands, size_t(caps_.cand) * sizeof(Candidate)))
       return false;
   }
   return true;
 }
 
+// The kernels' parameter structs, filled from the engine's tables and buffers, the
+// scan's work set and its arena (their types live in this file, so the helpers do too).
+struct GpuEngine::KernelArgs {
+  static FilterParams Filter(const GpuEngine& e, const WorkSet& W, const uint8_t* d_arena, uint64_t n_bytes,
+                             const SkipIn* skip) {
+    FilterParams fp;
+    fp.arena = d_arena;
+    fp.n_bytes = n_bytes;
+    fp.reach = e.d_reach_;
+    fp.diag_mode = e.diag_mode_;
+    fp.nl = static_cast<uint16_t*>(e.d_nl_);
+    fp.recs = static_cast<uint32_t*>(e.d_recs_);
+    fp.rec_cap = e.caps_.rec;
+    fp.counters = W.counters;
+    fp.runs = skip ? static_cast<const uint2*>(W.runs) : nullptr;
+    fp.run_info = skip ? W.skip_info : nullptr;
+    return fp;
+  }
+  static ConfirmParams Confirm(const GpuEngine& e, const WorkSet& W, const uint8_t* d_arena, uint64_t n_bytes,
+                               const uint64_t* d_offsets) {
+    ConfirmParams cp;
+    cp.arena = d_arena;
+    cp.n_bytes = n_bytes;
+    cp.off = d_offsets;
+    cp.chunk_file = static_cast<const uint32_t*>(W.chunk_file);
+    cp.nl = static_cast<const uint16_t*>(e.d_nl_);
+    cp.reach = e.d_reach_;
+    cp.tabs = e.d_ftabs_;
+    cp.tabs_bytes = e.ftabs_bytes_;
+    cp.t_bucket_off = e.ft_bucket_off_;
+    cp.t_bucket_items = e.ft_bucket_items_;
+    cp.t_items = e.ft_items_;
+    cp.t_item_ids = e.ft_item_ids_;
+    cp.t_item_cls = e.ft_item_cls_;
+    cp.t_classes = e.ft_classes_;
+    cp.anchors = e.d_anchors_;
+    cp.rules = e.d_rules_;
+    cp.nfa = e.d_nfa_;
+    cp.recs = static_cast<const uint32_t*>(e.d_recs_);
+    cp.rec_cap = e.caps_.rec;
+    cp.flags = static_cast<uint32_t*>(W.flags);
+    cp.counters = W.counters;
+    cp.hits = static_cast<uint32_t*>(e.d_hits_);
+    cp.hit_cap = e.caps_.hit;
+    cp.folds = static_cast<FoldSite*>(e.d_folds_);
+    cp.fold_cap = e.caps_.fold;
+    cp.diag = e.diag_confirm_;
+    cp.kwbits = static_cast<uint32_t*>(W.kw);
+    cp.kw_words = e.kw_words_;
+    cp.core = e.d_core_;
+    cp.group_items = e.d_group_items_;
+    cp.bucket_groups = e.d_bucket_groups_;
+    cp.item_diag = e.d_item_diag_;
+    cp.t_luts = e.ft_luts_;
+    cp.t_cmap = e.ft_cmap_;
+    cp.t_ccore = e.ft_ccore_;
+    cp.t_gitems = e.ft_gitems_;
+    cp.t_bgroups = e.ft_bgroups_;
+    cp.n_cls = e.n_core_cls_;
+    cp.t_hkeys = e.ft_hkeys_;
+    cp.t_hitems = e.ft_hitems_;
+    cp.hash_bits = e.hash_bits_;
+    cp.hash_buckets = e.hash_buckets_;
+    cp.n_classes_lds = e.c_stage_classes_ ? e.n_fclasses_ : 0u;
+    cp.wins = nullptr;
+    return cp;
+  }
+  static FoldParams Fold(const GpuEngine& e, const WorkSet& W, const uint8_t* d_arena, const uint64_t* d_offsets) {
+    FoldParams fo;
+    fo.arena = d_arena;
+    fo.off = d_offsets;
+    fo.tabs = e.d_ftabs_;
+    fo.tabs_bytes = e.ftabs_fold_bytes_;
+    fo.t_items = e.ft_items_;
+    fo.t_item_ids = e.ft_item_ids_;
+    fo.t_item_cls = e.ft_item_cls_;
+    fo.t_classes = e.ft_classes_;
+    fo.n_items = e.n_fitems_;
+    fo.stage_items = e.fold_stage_ ? 1u : 0u;
+    fo.n_classes = e.n_fclasses_;
+    fo.check_first = e.fold_check_first_ ? 1u : 0u;
+    static const uint32_t fold_diag =
+        std::getenv("TSG_DIAG_FOLD") ? uint32_t(std::atoi(std::getenv("TSG_DIAG_FOLD"))) : 0u;
+    fo.diag = fold_diag;
+    fo.pairs = static_cast<const FoldPair*>(e.d_fold_pairs_);
+    fo.first = static_cast<const uint32_t*>(e.d_fold_first_);
+    fo.n_pairs_k = e.n_fold_pairs_k_;
+    fo.n_pairs_s = e.n_fold_pairs_s_;
+    fo.n_cap_k = e.n_fold_cap_k_;
+    fo.n_cap_s = e.n_fold_cap_s_;
+    fo.folds = static_cast<const FoldSite*>(e.d_folds_);
+    fo.fold_cap = e.caps_.fold;
+    fo.idx_off = static_cast<const uint32_t*>(e.d_fold_idx_off_);
+    fo.idx_items = static_cast<const uint32_t*>(e.d_fold_idx_items_);
+    fo.use_idx = e.fold_idx_ ? 1u : 0u;
+    fo.n_cap_k_idx = e.n_fold_cap_k_idx_;
+    fo.n_cap_s_idx = e.n_fold_cap_s_idx_;
+    fo.hits = static_cast<uint32_t*>(e.d_hits_);
+    fo.hit_cap = e.caps_.hit;
+    fo.counters = W.counters;
+    return fo;
+  }
+  static KwFoldParams KwFold(const GpuEngine& e, const WorkSet& W, const uint8_t* d_arena,
+                             const uint64_t* d_offsets) {
+    KwFoldParams kf;
+    kf.arena = d_arena;
+    kf.off = d_offsets;
+    kf.tabs = static_cast<const uint8_t*>(e.d_ftabs_);
+    kf.t_items = e.ft_items_;
+    kf.t_item_ids = e.ft_item_ids_;
+    kf.t_item_cls = e.ft_item_cls_;
+    kf.t_classes = e.ft_classes_;
+    kf.pairs = static_cast<const FoldPair*>(e.d_kwfold_pairs_);
+    kf.n_rng_i = e.n_kwf_ri_;
+    kf.n_rng_k = e.n_kwf_rk_;
+    kf.n_cap_i = e.n_kwf_ci_;
+    kf.n_cap_k = e.n_kwf_ck_;
+    kf.folds = static_cast<const FoldSite*>(e.d_folds_);
+    kf.fold_cap = e.caps_.fold;
+    kf.counters = W.counters;
+    kf.kwbits = static_cast<uint32_t*>(W.kw);
+    kf.kw_words = e.kw_words_;
+    return kf;
+  }
+  static NfaParams Nfa(const GpuEngine& e, const WorkSet& W, const uint8_t* d_arena, const uint64_t* d_offsets,
+                       uint32_t n_files, const SkipIn* skip) {
+    NfaParams np;
+    np.arena = d_arena;
+    np.off = d_offsets;
+    np.n_files = n_files;
+    np.nl = static_cast<const uint16_t*>(e.d_nl_);
+    np.anchors = e.d_anchors_;
+    np.rules = e.d_rules_;
+    np.rule_kw = e.d_rule_kw_;
+    np.kwbits = static_cast<const uint32_t*>(W.kw);
+    np.kw_words = e.kw_words_;
+    np.flags = static_cast<const uint32_t*>(W.flags);
+    np.nfa = e.d_nfa_;
+    np.hits = static_cast<const uint32_t*>(e.d_hits_);
+    np.hit_cap = e.caps_.hit;
+    np.counters = W.counters;
+    static const uint32_t verify_diag =
+        std::getenv("TSG_DIAG_VERIFY") ? uint32_t(std::atoi(std::getenv("TSG_DIAG_VERIFY"))) : 0u;
+    np.diag = verify_diag;
+    np.cands = static_cast<Candidate*>(W.cands);
+    np.cand_cap = e.caps_.cand;
+    np.fullscan_rules = e.d_fullscan_rules_;
+    np.n_fullscan_rules = e.n_fullscan_rules_;
+    np.fs_chunk = e.fs_chunk_;
+    np.skip = skip ? skip->d_skip : nullptr;
+    np.drop_marked = skip && skip->drop_marked ? 1u : 0u;
+    np.kw_fold = e.kw_fold_ ? 1u : 0u;  // no keyword takes 'i' / 'k': the bits are exact without the kernel
+    return np;
+  }
+  static FsLists FullScanLists(const GpuEngine& e, const WorkSet& W) {
+    FsLists fq;
+    fq.pairs = static_cast<FsPair*>(e.d_fs_pairs_);
+    fq.pair_cap = e.caps_.fs_pair;
+    fq.tasks = static_cast<FsTask*>(e.d_fs_tasks_);
+    fq.task_cap = e.caps_.fs_task;
+    fq.wave_pairs = static_cast<uint32_t*>(e.d_fs_wave_);
+    fq.ctr = W.fs_ctr;
+    fq.task_min = e.caps_.fs_task_bytes;
+    return fq;
+  }
+};
+
 // The GPU phase of one scan: clears, K0 .. finalize, with the phase events
-// recorded into ev[0..6] (ev_fs before the full scan) and the K0 phase's own
-// span into ev_k0[0..1].  K1 .. finalize run on stream_; the K0 phase -- it
+// recorded into E.ev (scan_layout.h kEv*; E.ev_fs before the full scan) and the
+// K0 phase's own span into E.ev_k0.  K1 .. finalize run on stream_; the K0 phase -- it
 // needs only the offsets and the skip marks, which exist when the scan is
 // submitted -- on aux_stream_ (k0_aux) beside the kernels of the scan before,
 // or on stream_ too.  What the K0 phase writes, and what is read after
@@ -3920,7 +4101,7 @@ bool GpuEngine::EnsureSets(uint64_t n_chunks, uint32_t n_files, uint64_t f_tiles
 //     W.free_ev, recorded beside that scan's Slot::done: behind its read-back
 //     and, for a device-only batch, its fetch (kernels and copies).  Slots and
 //     sets are not paired (4 slots, 2 sets): the event belongs to the set.
-//  2. K1 ordering.  stream_ waits for this scan's own k0_done before ev[1].
+//  2. K1 ordering.  stream_ waits for this scan's own k0_done before kEvK1.
 //  3. Synchronous paths.  Run (and with it RunHost, the gather path and the
 //     rerun after Collect) and the fetches it issues use sets_[0] with
 //     everything on stream_ (k0_aux false).  stream_ then waits for W.free_ev
@@ -3937,20 +4118,19 @@ bool GpuEngine::EnsureSets(uint64_t n_chunks, uint32_t n_files, uint64_t f_tiles
 //     set's candidates and counter besides the arena; materialize.hip and
 //     classify.hip read the arena and the offsets alone.
 bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_offsets, uint32_t n_files,
-                             uint64_t n_chunks, WorkSet& W, bool k0_aux, hipEvent_t* ev, hipEvent_t ev_fs,
-                             hipEvent_t* ev_k0, const SkipIn* skip) {
+                             uint64_t n_chunks, WorkSet& W, bool k0_aux, PhaseEvents& E, const SkipIn* skip) {
   const uint64_t f_tiles = (n_bytes + kFTile - 1) / kFTile;
   if (skip && (!skip->d_skip || f_tiles == 0)) skip = nullptr;
   if (!EnsureSets(n_chunks, n_files, f_tiles, skip != nullptr)) return false;
   if (!Ensure(&d_nl_, &cap_nl_, (n_chunks + 8) * 2) ||
-      !Ensure(&d_folds_, &cap_folds_, size_t(fold_cap_) * sizeof(FoldSite)) ||
-      !Ensure(&d_recs_, &cap_recs_, size_t(rec_cap_) * 4) ||
-      !Ensure(&d_hits_, &cap_hits_, size_t(hit_cap_) * 12))
+      !Ensure(&d_folds_, &cap_folds_, size_t(caps_.fold) * sizeof(FoldSite)) ||
+      !Ensure(&d_recs_, &cap_recs_, size_t(caps_.rec) * 4) ||
+      !Ensure(&d_hits_, &cap_hits_, size_t(caps_.hit) * 12))
     return false;
   if (n_fullscan_rules_ > 0 &&
-      (!Ensure(&d_fs_pairs_, &cap_fs_pairs_, size_t(fs_pair_cap_) * sizeof(FsPair)) ||
-       !Ensure(&d_fs_wave_, &cap_fs_wave_, size_t(fs_pair_cap_) * 4) ||
-       !Ensure(&d_fs_tasks_, &cap_fs_tasks_, size_t(fs_task_cap_) * 4 * sizeof(FsTask))))
+      (!Ensure(&d_fs_pairs_, &cap_fs_pairs_, size_t(caps_.fs_pair) * sizeof(FsPair)) ||
+       !Ensure(&d_fs_wave_, &cap_fs_wave_, size_t(caps_.fs_pair) * 4) ||
+       !Ensure(&d_fs_tasks_, &cap_fs_tasks_, size_t(caps_.fs_task) * 4 * sizeof(FsTask))))
     return false;
   const hipStream_t k0s = k0_aux ? aux_stream_ : stream_;
   // the marks are written by the path kernel on a stream of its own
@@ -3962,10 +4142,10 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
   // on C2); beside K2 it slows K2 by 0.1 ms
   if (k0_aux && k2_rec_) HIP_OK(hipStreamWaitEvent(aux_stream_, k2_done_, 0));
   if (!k0_aux) {
-    HIP_OK(hipEventRecord(ev[0], stream_));  // the GPU phase: K0 (with the clears) .. finalize
+    HIP_OK(hipEventRecord(E.ev[kEvStart], stream_));  // the GPU phase: K0 (with the clears) .. finalize
     if (d_item_diag_) HIP_OK(hipMemsetAsync(d_item_diag_, 0, 8 * std::max<size_t>(n_fitems_, 1), stream_));
   }
-  HIP_OK(hipEventRecord(ev_k0[0], k0s));
+  HIP_OK(hipEventRecord(E.ev_k0[0], k0s));
   {  // every chunk below n_bytes gets its file (no clear needed)
     const uint64_t used = (n_bytes + kChunk - 1) / kChunk;
     const uint64_t runs = (used + kK0Run - 1) / kK0Run;
@@ -3993,87 +4173,34 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
                                                  static_cast<uint2*>(W.runs), W.skip_info);
     HIP_OK(hipGetLastError());
   }
-  HIP_OK(hipEventRecord(ev_k0[1], k0s));
-  if (k0_aux) {  // rule 2: K1 starts behind the scan's own K0; ev[0] -> ev[1] is what it still waits for
+  HIP_OK(hipEventRecord(E.ev_k0[1], k0s));
+  if (k0_aux) {  // rule 2: K1 starts behind the scan's own K0; kEvStart -> kEvK1 is what it still waits for
     HIP_OK(hipEventRecord(W.k0_done, aux_stream_));
     W.k0_rec = true;
-    HIP_OK(hipEventRecord(ev[0], stream_));
+    HIP_OK(hipEventRecord(E.ev[kEvStart], stream_));
     if (d_item_diag_) HIP_OK(hipMemsetAsync(d_item_diag_, 0, 8 * std::max<size_t>(n_fitems_, 1), stream_));
     HIP_OK(hipStreamWaitEvent(stream_, W.k0_done, 0));
   }
   // K1: streaming filter -> flagged block records
-  FilterParams fp;
-  fp.arena = d_arena;
-  fp.n_bytes = n_bytes;
-  fp.reach = d_reach_;
-  fp.diag_mode = diag_mode_;
-  fp.nl = static_cast<uint16_t*>(d_nl_);
-  fp.recs = static_cast<uint32_t*>(d_recs_);
-  fp.rec_cap = rec_cap_;
-  fp.counters = W.counters;
-  fp.runs = skip ? static_cast<const uint2*>(W.runs) : nullptr;
-  fp.run_info = skip ? W.skip_info : nullptr;
+  const FilterParams fp = KernelArgs::Filter(*this, W, d_arena, n_bytes, skip);
   uint32_t f_grid =
       uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((f_tiles + kScanWaves - 1) / kScanWaves, 256 * kFWgPerCu)));
   if (k1_grid_cap_) f_grid = std::min(f_grid, k1_grid_cap_);
-  HIP_OK(hipEventRecord(ev[1], stream_));
+  HIP_OK(hipEventRecord(E.ev[kEvK1], stream_));
   if (skip) filter_kernel<true><<<f_grid, kScanThreads, 0, stream_>>>(fp);
   else filter_kernel<false><<<f_grid, kScanThreads, 0, stream_>>>(fp);
   HIP_OK(hipGetLastError());
-  HIP_OK(hipEventRecord(ev[2], stream_));
+  HIP_OK(hipEventRecord(E.ev[kEvK2], stream_));
   // K2: confirm + verify
-  ConfirmParams cp;
-  cp.arena = d_arena;
-  cp.n_bytes = n_bytes;
-  cp.off = d_offsets;
-  cp.chunk_file = static_cast<const uint32_t*>(W.chunk_file);
-  cp.nl = static_cast<const uint16_t*>(d_nl_);
-  cp.reach = d_reach_;
-  cp.tabs = d_ftabs_;
-  cp.tabs_bytes = ftabs_bytes_;
-  cp.t_bucket_off = ft_bucket_off_;
-  cp.t_bucket_items = ft_bucket_items_;
-  cp.t_items = ft_items_;
-  cp.t_item_ids = ft_item_ids_;
-  cp.t_item_cls = ft_item_cls_;
-  cp.t_classes = ft_classes_;
-  cp.anchors = d_anchors_;
-  cp.rules = d_rules_;
-  cp.nfa = d_nfa_;
-  cp.recs = static_cast<const uint32_t*>(d_recs_);
-  cp.rec_cap = rec_cap_;
-  cp.flags = static_cast<uint32_t*>(W.flags);
-  cp.counters = W.counters;
-  cp.hits = static_cast<uint32_t*>(d_hits_);
-  cp.hit_cap = hit_cap_;
-  cp.folds = static_cast<FoldSite*>(d_folds_);
-  cp.fold_cap = fold_cap_;
-  cp.diag = diag_confirm_;
-  cp.kwbits = static_cast<uint32_t*>(W.kw);
-  cp.kw_words = kw_words_;
-  cp.core = d_core_;
-  cp.group_items = d_group_items_;
-  cp.bucket_groups = d_bucket_groups_;
-  cp.item_diag = d_item_diag_;
-  cp.t_luts = ft_luts_;
-  cp.t_cmap = ft_cmap_;
-  cp.t_ccore = ft_ccore_;
-  cp.t_gitems = ft_gitems_;
-  cp.t_bgroups = ft_bgroups_;
-  cp.n_cls = n_core_cls_;
-  cp.t_hkeys = ft_hkeys_;
-  cp.t_hitems = ft_hitems_;
-  cp.hash_bits = hash_bits_;
-  cp.hash_buckets = hash_buckets_;
-  cp.n_classes_lds = c_stage_classes_ ? n_fclasses_ : 0u;
-  cp.wins = nullptr;
+  ConfirmParams cp = KernelArgs::Confirm(*this, W, d_arena, n_bytes, d_offsets);
   static const bool k2_pack = std::getenv("TSG_K2_PACK") && std::atoi(std::getenv("TSG_K2_PACK")) != 0;
   if (k2_pack && diag_mode_ == 0) {  // (experiment) the windows packed between K1 and K2, outside K2's events
-    if (!Ensure(&d_wins_, &cap_wins_, size_t(rec_cap_) * 64)) return false;
-    pack_windows_kernel<<<8192, 256, 0, stream_>>>(d_arena, n_bytes, static_cast<const uint32_t*>(d_recs_), rec_cap_,
+    if (!Ensure(&d_wins_, &cap_wins_, size_t(caps_.rec) * 64)) return false;
+    pack_windows_kernel<<<8192, 256, 0, stream_>>>(d_arena, n_bytes, static_cast<const uint32_t*>(d_recs_), caps_.rec,
                                                    W.counters, static_cast<uint8_t*>(d_wins_));
     HIP_OK(hipGetLastError());
-    HIP_OK(hipEventRecord(ev[2], stream_));  // re-recorded: K1 + pack count as the scan phase, K2 alone as confirm
+    // re-recorded: K1 + pack count as the scan phase, K2 alone as confirm
+    HIP_OK(hipEventRecord(E.ev[kEvK2], stream_));
     cp.wins = static_cast<const uint8_t*>(d_wins_);
   }
   if (diag_mode_ == 0) {
@@ -4083,41 +4210,11 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
       confirm_kernel<false><<<2048 * 256 / kCThreadsG, kCThreadsG, c_lds_bytes_, stream_>>>(cp);
   }
   HIP_OK(hipGetLastError());
-  HIP_OK(hipEventRecord(ev[3], stream_));
+  HIP_OK(hipEventRecord(E.ev[kEvFold], stream_));
   HIP_OK(hipEventRecord(k2_done_, stream_));
   k2_rec_ = true;
   // fold runes: fold-tolerant item matching around each one
-  FoldParams fo;
-  fo.arena = d_arena;
-  fo.off = d_offsets;
-  fo.tabs = d_ftabs_;
-  fo.tabs_bytes = ftabs_fold_bytes_;
-  fo.t_items = ft_items_;
-  fo.t_item_ids = ft_item_ids_;
-  fo.t_item_cls = ft_item_cls_;
-  fo.t_classes = ft_classes_;
-  fo.n_items = n_fitems_;
-  fo.stage_items = fold_stage_ ? 1u : 0u;
-  fo.n_classes = n_fclasses_;
-  fo.check_first = fold_check_first_ ? 1u : 0u;
-  static const uint32_t fold_diag = std::getenv("TSG_DIAG_FOLD") ? uint32_t(std::atoi(std::getenv("TSG_DIAG_FOLD"))) : 0u;
-  fo.diag = fold_diag;
-  fo.pairs = static_cast<const FoldPair*>(d_fold_pairs_);
-  fo.first = static_cast<const uint32_t*>(d_fold_first_);
-  fo.n_pairs_k = n_fold_pairs_k_;
-  fo.n_pairs_s = n_fold_pairs_s_;
-  fo.n_cap_k = n_fold_cap_k_;
-  fo.n_cap_s = n_fold_cap_s_;
-  fo.folds = static_cast<const FoldSite*>(d_folds_);
-  fo.fold_cap = fold_cap_;
-  fo.idx_off = static_cast<const uint32_t*>(d_fold_idx_off_);
-  fo.idx_items = static_cast<const uint32_t*>(d_fold_idx_items_);
-  fo.use_idx = fold_idx_ ? 1u : 0u;
-  fo.n_cap_k_idx = n_fold_cap_k_idx_;
-  fo.n_cap_s_idx = n_fold_cap_s_idx_;
-  fo.hits = static_cast<uint32_t*>(d_hits_);
-  fo.hit_cap = hit_cap_;
-  fo.counters = W.counters;
+  const FoldParams fo = KernelArgs::Fold(*this, W, d_arena, d_offsets);
   if (diag_mode_ == 0) {
     if (lds_tabs_)
       fold_kernel<true><<<fold_grid_, 64 * kFoldWaves, ftabs_fold_bytes_ + 32 * n_fitems_, stream_>>>(fo);
@@ -4128,66 +4225,17 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
   }
   HIP_OK(hipGetLastError());
   if (diag_mode_ == 0 && kw_fold_ && n_kwf_ci_ + n_kwf_ck_ > 0) {
-    KwFoldParams kf;
-    kf.arena = d_arena;
-    kf.off = d_offsets;
-    kf.tabs = static_cast<const uint8_t*>(d_ftabs_);
-    kf.t_items = ft_items_;
-    kf.t_item_ids = ft_item_ids_;
-    kf.t_item_cls = ft_item_cls_;
-    kf.t_classes = ft_classes_;
-    kf.pairs = static_cast<const FoldPair*>(d_kwfold_pairs_);
-    kf.n_rng_i = n_kwf_ri_;
-    kf.n_rng_k = n_kwf_rk_;
-    kf.n_cap_i = n_kwf_ci_;
-    kf.n_cap_k = n_kwf_ck_;
-    kf.folds = static_cast<const FoldSite*>(d_folds_);
-    kf.fold_cap = fold_cap_;
-    kf.counters = W.counters;
-    kf.kwbits = static_cast<uint32_t*>(W.kw);
-    kf.kw_words = kw_words_;
+    const KwFoldParams kf = KernelArgs::KwFold(*this, W, d_arena, d_offsets);
     kwfold_kernel<<<1024, 64 * kFoldWaves, 0, stream_>>>(kf);
     HIP_OK(hipGetLastError());
   }
-  HIP_OK(hipEventRecord(ev[4], stream_));
-  NfaParams np;
-  np.arena = d_arena;
-  np.off = d_offsets;
-  np.n_files = n_files;
-  np.nl = static_cast<const uint16_t*>(d_nl_);
-  np.anchors = d_anchors_;
-  np.rules = d_rules_;
-  np.rule_kw = d_rule_kw_;
-  np.kwbits = static_cast<const uint32_t*>(W.kw);
-  np.kw_words = kw_words_;
-  np.flags = static_cast<const uint32_t*>(W.flags);
-  np.nfa = d_nfa_;
-  np.hits = static_cast<const uint32_t*>(d_hits_);
-  np.hit_cap = hit_cap_;
-  np.counters = W.counters;
-  static const uint32_t verify_diag = std::getenv("TSG_DIAG_VERIFY") ? uint32_t(std::atoi(std::getenv("TSG_DIAG_VERIFY"))) : 0u;
-  np.diag = verify_diag;
-  np.cands = static_cast<Candidate*>(W.cands);
-  np.cand_cap = cand_cap_;
-  np.fullscan_rules = d_fullscan_rules_;
-  np.n_fullscan_rules = n_fullscan_rules_;
-  np.fs_chunk = fs_chunk_;
-  np.skip = skip ? skip->d_skip : nullptr;
-  np.drop_marked = skip && skip->drop_marked ? 1u : 0u;
-  np.kw_fold = kw_fold_ ? 1u : 0u;  // no keyword takes 'i' / 'k': the bits are exact without the kernel
-
+  HIP_OK(hipEventRecord(E.ev[kEvVerify], stream_));
+  const NfaParams np = KernelArgs::Nfa(*this, W, d_arena, d_offsets, n_files, skip);
   if (diag_mode_ == 0) verify_hits_kernel<<<verify_blocks_, 256, 0, stream_>>>(np);
   HIP_OK(hipGetLastError());
   if (np.n_fullscan_rules > 0) {
-    HIP_OK(hipEventRecord(ev_fs, stream_));
-    FsLists fq;
-    fq.pairs = static_cast<FsPair*>(d_fs_pairs_);
-    fq.pair_cap = fs_pair_cap_;
-    fq.tasks = static_cast<FsTask*>(d_fs_tasks_);
-    fq.task_cap = fs_task_cap_;
-    fq.wave_pairs = static_cast<uint32_t*>(d_fs_wave_);
-    fq.ctr = W.fs_ctr;
-    fq.task_min = fs_task_bytes_;  // (fq.ctr was cleared by K0)
+    HIP_OK(hipEventRecord(E.ev_fs, stream_));
+    const FsLists fq = KernelArgs::FullScanLists(*this, W);  // (W.fs_ctr was cleared by K0)
     const uint64_t pairs = uint64_t(n_files) * n_fullscan_rules_;
     const uint32_t pb = uint32_t(std::min<uint64_t>(std::max<uint64_t>((pairs + 255) / 256, 1), 4096));
     fs_pairs_kernel<<<pb, 256, 0, stream_>>>(np, fq);
@@ -4197,10 +4245,10 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
     fs_wave_kernel<<<1024, 256, 0, stream_>>>(np, fq);
     HIP_OK(hipGetLastError());
   }
-  HIP_OK(hipEventRecord(ev[5], stream_));
+  HIP_OK(hipEventRecord(E.ev[kEvFinalize], stream_));
   if (diag_mode_ == 0) finalize_kernel<<<finalize_blocks_, 256, 0, stream_>>>(np);
   HIP_OK(hipGetLastError());
-  HIP_OK(hipEventRecord(ev[6], stream_));
+  HIP_OK(hipEventRecord(E.ev[kEvEnd], stream_));
   return true;
 }
 
@@ -4266,8 +4314,8 @@ bool GpuEngine::IssueFetch(const WorkSet& W, const uint8_t* d_arena, const uint6
   if (h_flags)
     HIP_OK(hipMemcpyAsync(FetchFlags(d_fscratch_, n_files), h_flags, size_t(n_files) * 4, hipMemcpyHostToDevice,
                           stream_));
-  HIP_OK(FetchPlan(h_flags ? nullptr : static_cast<const Candidate*>(W.cands), W.counters + 1, cand_cap_, d_offsets,
-                   n_files, direct, d_fscratch_, ctr, stream_));
+  HIP_OK(FetchPlan(h_flags ? nullptr : static_cast<const Candidate*>(W.cands), W.counters + kCtCands, caps_.cand,
+                   d_offsets, n_files, direct, d_fscratch_, ctr, stream_));
   HIP_OK(hipMemcpyAsync(h_ctr, ctr, sizeof(FetchCounters), hipMemcpyDeviceToHost, stream_));
   uint8_t* st = static_cast<uint8_t*>(d_fstage_);
   for (uint64_t w0 = 0; w0 < copy_bytes; w0 += stage) {
@@ -4358,8 +4406,8 @@ bool GpuEngine::IssueFetchWin(const WorkSet& W, const uint8_t* d_arena, uint64_t
     return false;
   FetchWinCounters* ctr = static_cast<FetchWinCounters*>(d_fctr_);
   HIP_OK(hipEventRecord(ev0, stream_));
-  HIP_OK(FetchWinPlan(static_cast<const Candidate*>(W.cands), W.counters + 1, cand_cap_, d_offsets, n_files, n_bytes,
-                      d_rule_max_len_, uint32_t(h_rule_max_len_.size()), prm, d_wscratch_, ctr, stream_));
+  HIP_OK(FetchWinPlan(static_cast<const Candidate*>(W.cands), W.counters + kCtCands, caps_.cand, d_offsets, n_files,
+                      n_bytes, d_rule_max_len_, uint32_t(h_rule_max_len_.size()), prm, d_wscratch_, ctr, stream_));
   HIP_OK(hipMemcpyAsync(h_ctr, ctr, sizeof(FetchWinCounters), hipMemcpyDeviceToHost, stream_));
   uint8_t* st = static_cast<uint8_t*>(d_fstage_);
   for (uint64_t w0 = 0; w0 < copy_bytes; w0 += stage) {
@@ -4446,11 +4494,11 @@ bool GpuEngine::FetchFiles(const uint8_t* d_arena, const uint64_t* d_offsets, ui
 bool GpuEngine::DumpStages(const WorkSet& W, const uint32_t* cnt, uint64_t n_bytes, uint32_t n_files, StageDump* d) {
   std::memcpy(d->counters, cnt, sizeof(d->counters));
   d->kw_words = kw_words_;
-  d->hit_cap = hit_cap_;
-  d->rec_cap = rec_cap_;
-  d->cand_cap = cand_cap_;
+  d->hit_cap = caps_.hit;
+  d->rec_cap = caps_.rec;
+  d->cand_cap = caps_.cand;
   const uint64_t used = (n_bytes + kChunk - 1) / kChunk;
-  const size_t n_hits = std::min(cnt[0], hit_cap_), n_recs = std::min(cnt[7], rec_cap_);
+  const size_t n_hits = std::min(cnt[kCtHits], caps_.hit), n_recs = std::min(cnt[kCtRecs], caps_.rec);
   std::vector<uint32_t> raw(3 * n_hits);
   d->kw.assign(size_t(n_files) * kw_words_, 0);
   d->flags.assign(n_files, 0);
@@ -4492,64 +4540,31 @@ bool GpuEngine::Run(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_
   InitCaps(n_bytes);
   WorkSet& W = sets_[0];  // the synchronous path: one set, everything on stream_ (§4.10 rule 3)
   for (int attempt = 0; attempt < 8; attempt++) {
-    if (!EnqueuePhase(d_arena, n_bytes, d_offsets, n_files, n_chunks, W, false, ev_, ev_fs_, ev_k0_, skip)) return false;
-    uint32_t cnt[16];
-    if (!h_run_cnt_) HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&h_run_cnt_), 64, hipHostMallocDefault));
+    if (!EnqueuePhase(d_arena, n_bytes, d_offsets, n_files, n_chunks, W, false, run_ev_, skip)) return false;
+    uint32_t cnt[kScanCtrWords];
+    if (!h_run_cnt_) HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&h_run_cnt_), sizeof(cnt), hipHostMallocDefault));
     HIP_OK(hipMemcpyAsync(h_run_cnt_, W.counters, sizeof(cnt), hipMemcpyDeviceToHost, stream_));
     const bool has_skip = skip && skip->d_skip && n_bytes > 0;
     if (has_skip) {
-      if (!h_run_skip_) HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&h_run_skip_), 64, hipHostMallocDefault));
-      HIP_OK(hipMemcpyAsync(h_run_skip_, W.skip_info, 64, hipMemcpyDeviceToHost, stream_));
+      if (!h_run_skip_)
+        HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&h_run_skip_), kScanCtrBytes, hipHostMallocDefault));
+      HIP_OK(hipMemcpyAsync(h_run_skip_, W.skip_info, kScanCtrBytes, hipMemcpyDeviceToHost, stream_));
     }
     HIP_OK(WaitStream());
     if (has_skip) NoteSkip(h_run_skip_, st);
     std::memcpy(cnt, h_run_cnt_, sizeof(cnt));
     if (std::getenv("TSG_STATS_DEBUG"))
-      std::fprintf(stderr, "counters: hits %u cands %u special %u recs %u folds %u\n", cnt[0], cnt[1], cnt[2], cnt[7],
-                   cnt[9]);
-    st->hits = cnt[11];  // exact anchor-item matches in the confirm kernel
-    st->follow_hits = cnt[0];  // past the follow requirements (+ fold-kernel hits): the verify kernel's input
-    st->special_files = cnt[2];
-    st->flagged_blocks = cnt[7];
-    if (cnt[8]) {  // record list overflow: grow and rescan
-      rec_cap_ = uint32_t(std::min<uint64_t>(uint64_t(cnt[7]) + cnt[7] / 4 + 4096, 0xFFFFFFF0u / 4));
-      continue;
-    }
-    st->hit_overflow = cnt[3] != 0;
-    st->cand_overflow = cnt[4] != 0;
-    if (cnt[6]) {  // full-scan pair / task list overflow: grow to the counts seen
-      uint32_t fc[16];
-      HIP_OK(hipMemcpy(fc, W.fs_ctr, sizeof(fc), hipMemcpyDeviceToHost));
-      fs_pair_cap_ = std::max<uint32_t>(fs_pair_cap_, fc[0] + fc[0] / 4 + 1024);
-      const uint32_t mt = std::max(std::max(fc[1], fc[2]), std::max(fc[3], fc[4]));
-      constexpr uint64_t kMaxTasks = 0x7FFFFFFFu / sizeof(FsTask) / 4;
-      const uint64_t want = uint64_t(mt) + mt / 4 + 1024;
-      if (want > kMaxTasks) {
-        // the lists cannot grow that far: coarser lane tasks instead (any task
-        // size is exact -- each lane starts max_len bytes before its range), so
-        // the scan degrades instead of failing with an overflow on every attempt
-        uint64_t tb = fs_task_bytes_;
-        while (tb < (uint64_t(1) << 26) && want * fs_task_bytes_ / tb > kMaxTasks) tb *= 2;
-        fs_task_bytes_ = uint32_t(tb);
-      }
-      fs_task_cap_ = uint32_t(std::min<uint64_t>(std::max<uint64_t>(fs_task_cap_, want), kMaxTasks));
-      continue;
-    }
-    if (cnt[10]) {  // fold site list overflow
-      fold_cap_ = uint32_t(std::min<uint64_t>(uint64_t(cnt[9]) + cnt[9] / 4 + 1024, 0xFFFFFFF0u / 16));
-      continue;
-    }
-    if (st->hit_overflow) {  // grow and rescan (correctness first)
-      hit_cap_ = uint32_t(std::min<uint64_t>(uint64_t(cnt[0]) + cnt[0] / 4 + 1024, 0xFFFFFFF0u / 12));
-      continue;
-    }
-    if (st->cand_overflow) {
-      cand_cap_ = uint32_t(std::min<uint64_t>(uint64_t(cnt[1]) + cnt[1] / 4 + 1024, 0xFFFFFFF0u));
-      continue;
-    }
-    cands->resize(cnt[1]);
-    if (cnt[1]) {
-      const size_t nb = size_t(cnt[1]) * sizeof(Candidate);
+      std::fprintf(stderr, "counters: hits %u cands %u special %u recs %u folds %u\n", cnt[kCtHits], cnt[kCtCands],
+                   cnt[kCtSpecial], cnt[kCtRecs], cnt[kCtFolds]);
+    NoteCounters(cnt, st);
+    // a list overflowed: grow it and rescan (correctness first)
+    uint32_t fc[kScanCtrWords] = {};
+    if (OverflowedList(cnt) == kListFullScan) HIP_OK(hipMemcpy(fc, W.fs_ctr, sizeof(fc), hipMemcpyDeviceToHost));
+    if (GrowOverflowed(cnt, fc, &caps_) != kListNone) continue;
+    const uint32_t n_cands = cnt[kCtCands];
+    cands->resize(n_cands);
+    if (n_cands) {
+      const size_t nb = size_t(n_cands) * sizeof(Candidate);
       if (!EnsureHost(&h_run_cands_, &cap_h_run_cands_, nb)) return false;
       HIP_OK(hipMemcpyAsync(h_run_cands_, W.cands, nb, hipMemcpyDeviceToHost, stream_));
       HIP_OK(WaitStream());
@@ -4564,17 +4579,7 @@ bool GpuEngine::Run(const uint8_t* d_arena, uint64_t n_bytes, const uint64_t* d_
                  cands->end());
     st->candidates = cands->size();
     if (d_item_diag_) DumpItemDiag();
-    hipEventElapsedTime(&st->ms_scan, ev_[1], ev_[2]);
-    hipEventElapsedTime(&st->ms_confirm, ev_[2], ev_[3]);
-    hipEventElapsedTime(&st->ms_careful, ev_[3], ev_[4]);  // fold kernel
-    hipEventElapsedTime(&st->ms_verify, ev_[4], ev_[5]);   // verify (deferred hits) + full-scan
-    hipEventElapsedTime(&st->ms_finalize, ev_[5], ev_[6]);
-    if (n_fullscan_rules_ > 0) hipEventElapsedTime(&st->ms_fullscan, ev_fs_, ev_[5]);
-    st->fullscan_tasks = cnt[13];
-    st->fold_sites = cnt[9];
-    hipEventElapsedTime(&st->ms_chunkmap, ev_[0], ev_[1]);
-    hipEventElapsedTime(&st->ms_total, ev_[0], ev_[6]);
-    hipEventElapsedTime(&st->ms_k0, ev_k0_[0], ev_k0_[1]);
+    NotePhaseTimes(run_ev_, n_fullscan_rules_ > 0, st);
     if (fetch) {  // a device-only batch: the candidate files' bytes, sized exactly
       std::vector<uint8_t> want(n_files, 0);
       for (const Candidate& c : *cands)

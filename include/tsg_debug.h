@@ -125,6 +125,19 @@ int tsg_debug_pool_budget(void);
  * scanner without a GPU engine.  (Bookkeeping for tests; call it between scans.) */
 struct tsg_scanner;
 int tsg_debug_scanner_engine(struct tsg_scanner* s, uint64_t out[4]);
+/* The engine report's fifth field, beside the four above because out[4] is a
+ * fixed size callers allocate: how the scanner's streaming filter (K1)
+ * evaluates its window -- 1 as an OR of slot masks (TSG_K1_FORM=or, the
+ * default), 0 as the shift-or recurrence (TSG_K1_FORM=shiftor); read at scanner
+ * creation, the same for Run and Enqueue.  -1 for a scanner without a GPU engine. */
+int tsg_debug_scanner_k1_form(struct tsg_scanner* s);
+/* K1's OR-form table (trivy_amd/csrc/k1_orform.h) of compiled rules: out receives
+ * 256 rows of 4 u32, row b = (W_0, W_1, W_2, W_3)[b] with W_k = m_{2k+1} << 16 |
+ * m_{2k}, m_s the 16-bit not-allowed mask of window slot s over the 16 buckets
+ * (bit j = bit 4s + j%4 of reach word j/4), and W_3 = 1 for '\n' only.  It is
+ * the row every replica of the filter kernel's LDS image holds.  -1: no filter,
+ * or one that is not 16 buckets with a window of at most 6. */
+int tsg_debug_filter_orform(const tsg_compiled* c, uint32_t out[1024]);
 
 /* Where a scanner makes the findings of HBM-resident batches (tsg_batch.dev_arena):
  * mode 1 the GPU (trivy_amd/csrc/materialize.h), 0 the host, 2 (the default;
@@ -258,6 +271,14 @@ typedef struct tsg_debug_stage_dump {
 int tsg_debug_engine_stages(const tsg_compiled* c, int device, const uint8_t* arena, uint64_t n_bytes,
                             const uint64_t* offsets, uint32_t n_files, const uint8_t tail[64],
                             tsg_debug_stage_dump* out);
+/* The same scan with a skip list: skip holds one byte per file, non-zero for a file whose
+ * bytes the result does not need (NULL: no list, as above).  K1 then streams only the 4-KiB tiles that hold
+ * a byte of another file (filter_kernel<true>: runs of kept tiles), so recs holds the flagged blocks of the
+ * kept tiles only, and the nl entries of a dropped tile's four chunks are not written by this scan (their
+ * content is unspecified); the later stages see the kept tiles' records. */
+int tsg_debug_engine_stages_skip(const tsg_compiled* c, int device, const uint8_t* arena, uint64_t n_bytes,
+                                 const uint64_t* offsets, uint32_t n_files, const uint8_t tail[64],
+                                 const uint8_t* skip, tsg_debug_stage_dump* out);
 /* What the engine grows after a scan that overflowed a list (scan_layout.h
  * GrowOverflowed), without a GPU.  counters: the 16 scan counters above;
  * fs_counters: the 6 full-scan list counters {pairs, tasks per NFA width x 4,

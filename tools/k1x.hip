@@ -15,7 +15,16 @@
 //         round 6: before, a multiply per word inflated the VALU), 3 loads only, 4 full with a rolling ring of GRP table rows
 //         (row k + GRP read as row k is applied: GRP reads in flight at every
 //         step, no group-boundary drain), 5 = 4 with sched_group_barrier
-//         pinning the order (1 ds_read after every row's 4 v_lshl_or)
+//         pinning the order (1 ds_read after every row's 4 v_lshl_or),
+//         7 the OR-form loop (engine.hip filter_kernel<., true>: the table re-laid as slot
+//         pairs, k1_orform.h; per byte one v_perm address, one ds_read_b128, one v_or3, and
+//         per two bytes two v_perm + one v_bitop3 + one v_add3; GRP rows read ahead),
+//         8 bare conflict-free ds_read_b128s alone: 64 per lane and tile like the filter,
+//         one address per tile and immediate offsets, results unused.  UNRELIABLE as a
+//         rate: its launches showed 9.2e6 SQ_INSTS_LDS where 3.1e8 were expected (0.60 ms
+//         for 20 GB), which is not understood, and only three words of a tile are consumed,
+//         so the other tile loads are dead -- not the filter's loads at the same grid.  Use
+//         it for LDS cycles per conflict-free ds_read_b128 only (4.01 measured)
 //   STR   independent shift-or streams per lane (2: the lane's chunk halves,
 //         the second warmed up on the 5 bytes before it)
 //   MINW  workgroups of 1024 per CU (__launch_bounds__ min waves per SIMD / 4)
@@ -23,6 +32,8 @@
 
 #include <cstdint>
 #include <cstdio>
+
+#include "../trivy_amd/csrc/k1_orform.h"
 
 namespace {
 
@@ -88,7 +99,9 @@ __global__ __launch_bounds__(1024, 4 * MINW) void k1x(const uint8_t* __restrict_
   for (uint32_t i = threadIdx.x; i < 256 * REP; i += blockDim.x) {
     const uint32_t b = i / REP, r = i % REP;
     uint32_t* d = reinterpret_cast<uint32_t*>(s_tab + b * 256 + r * 4 * NREG);
-    if (NREG == 4) {
+    if (MODE == 7) {
+      tsg::OrFormRow(reach + b * 4, d);
+    } else if (NREG == 4) {
 #pragma unroll
       for (int w = 0; w < 4; w++) d[w] = reach[b * 4 + w];
     } else {
@@ -136,6 +149,56 @@ __global__ __launch_bounds__(1024, 4 * MINW) void k1x(const uint8_t* __restrict_
         }
       }
       sink ^= x ^ p0 ^ p1;
+      return;
+    }
+    if (MODE == 8) {
+      typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+      // rows r .. r + 63 (r < 128: inside the table), this lane's replica: conflict-free like the filter's reads
+      const uint32_t a = uint32_t(reinterpret_cast<uintptr_t>(s_tab)) + ((cur[0].x & 0x7Fu) << 8) + laneoff;
+#pragma unroll
+      for (int k = 0; k < LB; k++) {
+        u32x4 r;
+        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(a), "n"(k * 256));
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)");
+      sink ^= p0 ^ p1;
+      return;
+    }
+    if (MODE == 7) {  // the product's OR-form body (NREG 4, STR 1)
+      uint32_t xh[4], yh[2], hprev;
+      {
+        const Row<4> r5 = rd<4, 0>(s_tab, p0, 3, laneoff);
+        const Row<4> r4 = rd<4, 0>(s_tab, p1, 0, laneoff), r3 = rd<4, 0>(s_tab, p1, 1, laneoff);
+        const Row<4> r2 = rd<4, 0>(s_tab, p1, 2, laneoff), r1 = rd<4, 0>(s_tab, p1, 3, laneoff);
+        asm("v_or3_b32 %0, %1, %2, %3" : "=v"(hprev) : "v"(r5.w[0]), "v"(r3.w[1]), "v"(r1.w[2]));
+        xh[0] = r4.w[0], xh[1] = r3.w[0], xh[2] = r2.w[0], xh[3] = r1.w[0];
+        yh[0] = r2.w[1], yh[1] = r1.w[1];
+      }
+      uint32_t acc = ~0u;
+#pragma unroll
+      for (int g = 0; g < LB; g += GRP) {
+        Row<4> m[GRP];
+#pragma unroll
+        for (int q = 0; q < GRP; q++) m[q] = rd<4, 0>(s_tab, wsel(cur, (g + q) >> 2), (g + q) & 3, laneoff);
+#pragma unroll
+        for (int q = 0; q < GRP; q += 2) {
+          const int k = g + q;
+          uint32_t h0, h1;
+          asm("v_or3_b32 %0, %1, %2, %3" : "=v"(h0) : "v"(xh[k & 3]), "v"(yh[0]), "v"(m[q].w[2]));
+          asm("v_or3_b32 %0, %1, %2, %3" : "=v"(h1) : "v"(xh[(k + 1) & 3]), "v"(yh[1]), "v"(m[q + 1].w[2]));
+          xh[k & 3] = m[q].w[0], xh[(k + 1) & 3] = m[q + 1].w[0];
+          yh[0] = m[q].w[1], yh[1] = m[q + 1].w[1];
+          const uint32_t hi = __builtin_amdgcn_perm(h1, h0, 0x07060302u);
+          const uint32_t lo = __builtin_amdgcn_perm(h0, hprev, 0x05040100u);
+          asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xe0" : "=v"(acc) : "v"(acc), "v"(hi), "v"(lo));
+          nl += m[q].w[3] + m[q + 1].w[3];
+          hprev = h1;
+          if (k % 16 == 14) {
+            flagged += acc != ~0u;
+            acc = ~0u;
+          }
+        }
+      }
       return;
     }
     if (MODE == 4 || MODE == 5) {  // rolling ring (STR 1)
@@ -283,6 +346,11 @@ const Variant kVariants[] = {
     V("r4 lb64 ring12 sgb s1", 4, 64, 12, 5, 1, 1),
     V("r4 lb64 g8 lds-only 2wg", 4, 64, 8, 1, 1, 2),
     V("r4 lb64 g8 no-lds 2wg", 4, 64, 8, 2, 1, 2),
+    // the OR form of the window and what bounds it
+    V("r4 lb64 g4 or-form 2wg", 4, 64, 4, 7, 1, 2),
+    V("r4 lb64 g2 or-form 2wg", 4, 64, 2, 7, 1, 2),
+    V("r4 lb64 g8 or-form 2wg", 4, 64, 8, 7, 1, 2),
+    V("r4 lb64 bare ds_read_b128 2wg", 4, 64, 4, 8, 1, 2),
 };
 #undef V
 

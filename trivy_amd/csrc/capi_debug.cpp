@@ -15,6 +15,7 @@
 #include "fetch_windows.h"
 #include "filter.h"
 #include "goregex.h"
+#include "k1_orform.h"
 #include "parallel.h"
 #include "xform.h"
 
@@ -469,6 +470,12 @@ int tsg_debug_sparse_tail(const tsg_global* g, const tsg_batch* b, const void* c
 int tsg_debug_engine_stages(const tsg_compiled* c, int device, const uint8_t* arena, uint64_t n_bytes,
                             const uint64_t* offsets, uint32_t n_files, const uint8_t tail[64],
                             tsg_debug_stage_dump* out) {
+  return tsg_debug_engine_stages_skip(c, device, arena, n_bytes, offsets, n_files, tail, nullptr, out);
+}
+
+int tsg_debug_engine_stages_skip(const tsg_compiled* c, int device, const uint8_t* arena, uint64_t n_bytes,
+                                 const uint64_t* offsets, uint32_t n_files, const uint8_t tail[64],
+                                 const uint8_t* skip, tsg_debug_stage_dump* out) {
   if (!c || !offsets || !tail || !out || (n_bytes && !arena)) {
     tsg::SetError("tsg_debug_engine_stages: NULL argument");
     return -2;
@@ -482,7 +489,7 @@ int tsg_debug_engine_stages(const tsg_compiled* c, int device, const uint8_t* ar
     tsg::SetError("tsg_debug_engine_stages: offsets must end at n_bytes");
     return -2;
   }
-  void *d_arena = nullptr, *d_off = nullptr;
+  void *d_arena = nullptr, *d_off = nullptr, *d_skip = nullptr;
   hipError_t e = hipSetDevice(device);
   auto ok = [&](hipError_t r) {
     if (e == hipSuccess) e = r;
@@ -494,14 +501,20 @@ int tsg_debug_engine_stages(const tsg_compiled* c, int device, const uint8_t* ar
   if (ok(e) && ok(hipMalloc(&d_arena, n_bytes + 64)) && ok(hipMalloc(&d_off, (size_t(n_files) + 1) * 8)) &&
       ok(hipMemcpy(static_cast<uint8_t*>(d_arena) + n_bytes, tail, 64, hipMemcpyHostToDevice)) &&
       (n_bytes == 0 || ok(hipMemcpy(d_arena, arena, n_bytes, hipMemcpyHostToDevice))) &&
-      ok(hipMemcpy(d_off, offsets, (size_t(n_files) + 1) * 8, hipMemcpyHostToDevice))) {
+      ok(hipMemcpy(d_off, offsets, (size_t(n_files) + 1) * 8, hipMemcpyHostToDevice)) &&
+      (!skip || n_files == 0 ||
+       (ok(hipMalloc(&d_skip, n_files)) && ok(hipMemcpy(d_skip, skip, n_files, hipMemcpyHostToDevice))))) {
+    // a fresh engine per call: the TSG_* switches its constructor reads (TSG_K1_FORM among them) apply to
+    // this scan -- tests that compare variants rely on it
     std::unique_ptr<tsg::GpuEngine> eng(new tsg::GpuEngine(c->cr, device));
     std::vector<tsg::Candidate> cands;
+    tsg::SkipIn sk;
+    sk.d_skip = static_cast<const uint8_t*>(d_skip);
     if (!eng->ok() || !eng->Run(static_cast<const uint8_t*>(d_arena), n_bytes, static_cast<const uint64_t*>(d_off),
-                                n_files, &cands, nullptr, nullptr, nullptr, &d))
+                                n_files, &cands, nullptr, nullptr, d_skip ? &sk : nullptr, &d))
       run_err = eng->error().empty() ? "engine failed" : eng->error();
   }
-  for (void* p : {d_arena, d_off})
+  for (void* p : {d_arena, d_off, d_skip})
     if (p) (void)hipFree(p);
   if (e != hipSuccess || !run_err.empty()) {
     tsg::SetError(std::string("tsg_debug_engine_stages: ") + (e != hipSuccess ? hipGetErrorString(e) : run_err.c_str()));
@@ -562,6 +575,13 @@ int tsg_debug_filter_core(const tsg_compiled* c, uint32_t out[4]) {
   out[1] = uint32_t(cols.size());
   out[2] = most;
   out[3] = uint32_t(f->hash_keys.size());
+  return 0;
+}
+
+int tsg_debug_filter_orform(const tsg_compiled* c, uint32_t out[1024]) {
+  const auto* f = c->cr.filter.get();
+  if (!f || f->n_buckets != 16 || f->n_words != 4 || f->window > 6 || f->reach.size() != 256 * 4) return -1;
+  for (uint32_t b = 0; b < 256; b++) tsg::OrFormRow(&f->reach[size_t(b) * 4], out + size_t(b) * 4);
   return 0;
 }
 

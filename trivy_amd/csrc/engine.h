@@ -389,6 +389,9 @@ class GpuEngine {
     uint64_t retired_pending, retired_freed, cand_cap, slot_bytes;
   };
   HostMemInfo host_mem_info();
+  // K1's window evaluation in this engine's scans (TSG_K1_FORM at construction;
+  // DESIGN.md §4.1): true the OR of slot masks, false the shift-or recurrence.
+  bool k1_or_form() const { return k1_or_; }
 
  private:
   bool Transform(int b, uint32_t nf, const uint8_t** arena, const uint64_t** offsets, uint64_t* n_bytes,
@@ -405,6 +408,7 @@ class GpuEngine {
   PhaseEvents run_ev_;  // Run's (Slot::ev for Enqueue'd scans)
   // tables
   uint32_t diag_mode_ = 0, diag_confirm_ = 0;
+  bool k1_or_ = true;  // TSG_K1_FORM: or (default) | shiftor
   AnchorInfo* d_anchors_ = nullptr;
   RuleGpu* d_rules_ = nullptr;
   uint32_t* d_rule_kw_ = nullptr;

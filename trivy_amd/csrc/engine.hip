@@ -42,6 +42,7 @@
 #include "fetch_windows.h"
 #include "xform.h"
 #include "filter.h"
+#include "k1_orform.h"
 
 namespace tsg {
 
@@ -164,6 +165,13 @@ constexpr uint32_t kFGroup = 8;  // tiles per compaction: 4 flag bits each, 32 p
 #define TSG_K1_READAHEAD 4
 #endif
 constexpr uint32_t kFReadAhead = TSG_K1_READAHEAD;  // table rows read ahead of the shift-or chain
+#ifndef TSG_K1_OR_READAHEAD
+#define TSG_K1_OR_READAHEAD 4
+#endif
+#ifndef TSG_K1_OR_WHOLE_TAIL
+#define TSG_K1_OR_WHOLE_TAIL 0
+#endif
+constexpr uint32_t kFReadAheadOr = TSG_K1_OR_READAHEAD;  // ... ahead of the OR form's combine (8 measured slower on C2)
 constexpr int kFWindow = 6;          // filter window: a fire stays visible for 9 - 6 = 3 bytes
 constexpr int kFWords = 4;           // 16 buckets = 4 u32 registers of 8 slots x 4 buckets
 constexpr uint32_t kFireBits = 0xFFF00000u;  // slots 5..7 of a register
@@ -345,6 +353,15 @@ __device__ __forceinline__ uint4 reach_read(const uint8_t* sb, uint32_t w, uint3
   return *reinterpret_cast<const uint4*>(sb + __builtin_amdgcn_perm(w, laneoff, 0x0C0C0000u | ((4u + k) << 8)));
 }
 
+// The same read where only some of the row's words are used: an empty asm takes all four, so the
+// compiler cannot narrow the read to ds_read_b32 / b64 / b96 (those take more lanes per LDS cycle
+// than the 16 replicas keep apart: bank conflicts).
+__device__ __forceinline__ uint4 reach_read_whole(const uint8_t* sb, uint32_t w, uint32_t k, uint32_t laneoff) {
+  uint4 r = reach_read(sb, w, k, laneoff);
+  asm volatile("" : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w));
+  return r;
+}
+
 // R = R << 4 | m, per register: one v_lshl_or_b32 each.  Written as asm so the
 // compiler keeps the serial chain instead of re-associating it into shifted
 // copies of the table words (which costs ~1.6x the VALU instructions).
@@ -374,6 +391,33 @@ __device__ __forceinline__ void load_reach_lds(uint8_t* s_reach, const uint32_t*
   }
 }
 
+// The OR-form image (k1_orform.h): row b = 16 copies of (W_0, W_1, W_2, W_3)[b],
+// built from the same reach table.  A thread re-lays one row and writes 4 copies.
+__device__ __forceinline__ void load_orform_lds(uint8_t* s_reach, const uint32_t* reach, int tid, int nthreads) {
+  for (uint32_t i = tid; i < 256 * 4; i += nthreads) {
+    const uint32_t b = i >> 2;
+    const uint4 r = reinterpret_cast<const uint4*>(reach)[b];
+    const uint32_t in[4] = {r.x, r.y, r.z, r.w};
+    uint32_t w[4];
+    OrFormRow(in, w);
+#pragma unroll
+    for (uint32_t c = 0; c < 4; c++)
+      reinterpret_cast<uint4*>(s_reach)[b * 16 + (i & 3) * 4 + c] = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+}
+
+// H = a | b | c and acc &= a | b, one VALU each.  Written as asm (like
+// reach_apply) so the compiler keeps the three-input forms as written.
+__device__ __forceinline__ uint32_t or3_keep(uint32_t a, uint32_t b, uint32_t c) {
+  uint32_t h;
+  asm("v_or3_b32 %0, %1, %2, %3" : "=v"(h) : "v"(a), "v"(b), "v"(c));
+  return h;
+}
+__device__ __forceinline__ uint32_t and_or_keep(uint32_t acc, uint32_t a, uint32_t b) {
+  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xe0" : "=v"(acc) : "v"(acc), "v"(a), "v"(b));  // acc & (a | b)
+  return acc;
+}
+
 // K1.  A wave owns 4-KiB tiles (grid-strided); lane l streams its 64
 // contiguous bytes as 4 x 16-B loads with the next tile's loads in flight.
 // The 5 bytes before a lane's chunk come from lane l-1 (lane 0: an 8-B load).
@@ -385,22 +429,42 @@ __device__ __forceinline__ void load_reach_lds(uint8_t* s_reach, const uint32_t*
 // the confirm kernel (K2) checks them exactly.
 // (<= 64 VGPRs in both shapes: with one workgroup per CU the other half of the
 // VGPRs and LDS go to a concurrent scan's confirm kernel)
+// kOr (TSG_K1_FORM=or, the default): the window is evaluated as an OR of slot
+// masks from the re-laid table (k1_orform.h) instead of the recurrence.  With
+//   H_p = W_0[b_{p-4}] | W_1[b_{p-2}] | W_2[b_p]                 (one v_or3_b32)
+// position p's 16 fire bits are hi(H_p) | lo(H_{p-1}); two positions at once:
+// two v_perm gather {hi(H_p) : hi(H_{p+1})} and {lo(H_{p-1}) : lo(H_p)} and one
+// v_bitop3 ANDs their OR into the block's accumulator.  W_3 counts newlines.
+// No dependent chain, the same one ds_read_b128 per byte, the same flagged
+// blocks and newline counts (TSG_K1_FORM=shiftor keeps the recurrence).
 // kRuns: the scan has a skip list (P.runs).  Without one the kernel is the
 // instantiation with the plain loop over a contiguous tile range: the run walk's
 // scalar bookkeeping cost that loop 3 % (5.35 -> 5.5 ms on C2) when both shared one.
-template <bool kRuns>
+template <bool kRuns, bool kOr>
 __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P) {
   __shared__ __attribute__((aligned(16))) uint8_t s_reach[65536];
   __shared__ uint32_t s_queue[kScanWaves * kFQueue];
   __shared__ uint64_t s_nl[kScanWaves * kFNlTiles];  // per wave: the last tiles' 4 chunk counts
   const int tid = threadIdx.x;
-  load_reach_lds(s_reach, P.reach, 16, tid, blockDim.x);
+  if constexpr (kOr) load_orform_lds(s_reach, P.reach, tid, blockDim.x);
+  else load_reach_lds(s_reach, P.reach, 16, tid, blockDim.x);
   __syncthreads();
   const uint32_t lane = tid & 63;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(uint32_t(tid) >> 6);
   const uint32_t laneoff = (lane & 15) * 16;
   uint32_t* Q = s_queue + wave * kFQueue;
   uint64_t* NL = s_nl + wave * kFNlTiles;
+  // The OR form holds more table words live than the chain (6 history words
+  // and the rows in flight), so at 64 VGPRs nothing derived from the lane index
+  // may stay in a register across a tile: each use takes the index through an
+  // empty asm and recomputes its address (a few VALU per tile).  Left to the
+  // compiler these values are spilled and reloaded inside the tile loop, and a
+  // reload's s_waitcnt vmcnt(0) waits for the next tile's loads in flight.
+  auto ln = [&]() {
+    uint32_t l = lane;
+    if constexpr (kOr) asm volatile("" : "+v"(l));
+    return l;
+  };
   uint32_t nl_slots = 0;  // wave-uniform: tiles staged in NL
   uint32_t qn = 0;  // wave-uniform
   // Each wave streams one contiguous range of tiles, so lane 0's 8-byte
@@ -419,8 +483,15 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
   const uint64_t n_kept = RUNS ? uint64_t(uni(P.run_info[kSkKept])) : n_tiles;
   const bool tail_kept = RUNS ? uni(P.run_info[kSkTailKept]) != 0 : true;
   const uint64_t per = n_kept / n_waves, extra = n_kept % n_waves;
-  const uint64_t k_begin = wid * per + (wid < extra ? wid : extra);
-  const uint64_t k_end = k_begin + per + (wid < extra ? 1 : 0);
+  // (the 64-bit division is vector code, so the wave's range comes out in VGPRs though it is
+  // wave-uniform; the OR form moves it to scalar registers: the tile counter and its bounds
+  // otherwise hold 6 of the kernel's 64 VGPRs through the loop)
+  auto uni64 = [&](uint64_t v) {
+    if constexpr (kOr) return uint64_t(uni(uint32_t(v))) | uint64_t(uni(uint32_t(v >> 32))) << 32;
+    else return v;
+  };
+  const uint64_t k_begin = uni64(wid * per + (wid < extra ? wid : extra));
+  const uint64_t k_end = uni64(k_begin + per + (wid < extra ? 1 : 0));
   uint32_t run = 0;             // wave-uniform: the run of the tile in hand
   uint64_t run_k1 = n_kept;     // kept tiles before the next run
   uint64_t t_begin = k_begin;   // the tile of kept index k_begin
@@ -437,6 +508,11 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
     t_begin = uint64_t(uni(r0.x)) + (k_begin - uni(r0.y));
     run_k1 = uni(RUNS[lo + 1].y);
   }
+  // Shift-or form: two register buffers, the next tile loading into one while
+  // the other is worked on.  OR form: one buffer refilled in place -- a block's
+  // 4 registers take the next tile's same block as soon as the block is done
+  // (3/4 of a tile ahead of its use), which frees 16 VGPRs for the table words
+  // the OR form keeps live; bufB is then unused.
   uint4 bufA[kFBlocks], bufB[kFBlocks];
   uint32_t pre_x = 0, pre_y = 0;  // wave-uniform: the 8 bytes before the current tile
   auto load_pre = [&](uint64_t tt) {  // tt > 0
@@ -458,20 +534,24 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
     *nr = true;
     return uni(RUNS[run].x);
   };
+  // One clamp per lane, no branch (a wave-uniform full-tile branch around
+  // the loads cost 1.4 ms on C2): a lane chunk starting inside the arena is
+  // readable whole (64 readable bytes past n_bytes), one past it reloads 0.
+  auto lane_ptr = [&](uint64_t tt) -> const uint8_t* {
+    const uint64_t b0 = tt * kFTile + uint64_t(ln()) * kFLane;
+    return P.arena + (b0 < P.n_bytes ? b0 : 0);
+  };
   auto load_tile = [&](uint4* dst, uint64_t tt) {
-    // One clamp per lane, no branch (a wave-uniform full-tile branch around
-    // the loads cost 1.4 ms on C2): a lane chunk starting inside the arena is
-    // readable whole (64 readable bytes past n_bytes), one past it reloads 0.
-    const uint64_t b0 = tt * kFTile + uint64_t(lane) * kFLane;
-    const uint8_t* lp = P.arena + (b0 < P.n_bytes ? b0 : 0);
+    const uint8_t* lp = lane_ptr(tt);
 #pragma unroll
     for (int j = 0; j < kFBlocks; j++) dst[j] = load16(lp + 16 * j);
   };
   auto flush = [&]() {  // wave-uniform
     uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(&P.counters[kCtRecs], qn);
+    const uint32_t l = ln();
+    if (l == 0) base = atomicAdd(&P.counters[kCtRecs], qn);
     base = __builtin_amdgcn_readfirstlane(base);
-    for (uint32_t i = lane; i < qn; i += 64) {
+    for (uint32_t i = l; i < qn; i += 64) {
       if (base + i < P.rec_cap) P.recs[base + i] = Q[i];
       else P.counters[kCtRecOvf] = 1;
     }
@@ -505,7 +585,8 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
     const uint32_t total = __builtin_amdgcn_readlane(incl, 63);
     if (total) {
       if (qn + total > kFQueue) flush();
-      const uint32_t rec0 = __builtin_amdgcn_readfirstlane(uint32_t(grp_t0 * (kFTile / 16))) + lane * kFBlocks;
+      const uint32_t l = ln();
+      const uint32_t rec0 = __builtin_amdgcn_readfirstlane(uint32_t(grp_t0 * (kFTile / 16))) + l * kFBlocks;
       uint32_t m = fl_acc;
       if (total <= kFQueue) {  // into the queue
         uint32_t at = qn + incl - cnt;
@@ -517,7 +598,7 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
         qn += total;
       } else {  // a group denser than the queue: straight to the global list
         uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&P.counters[kCtRecs], total);
+        if (l == 0) base = atomicAdd(&P.counters[kCtRecs], total);
         uint32_t at = __builtin_amdgcn_readfirstlane(base) + incl - cnt;
         while (m) {
           const uint32_t b = uint32_t(__builtin_ctz(m));
@@ -551,8 +632,9 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
   // One tile: `cur` holds its 64 bytes per lane.  kTail: the arena's last,
   // partial tile (bytes past the end are zeroed); kept out of the main loop's
   // code so the full tiles carry no masking state.
-  auto tile = [&](uint4* cur, uint64_t tt, auto tail_tag) {
+  auto tile = [&](uint4* cur, uint64_t tt, auto tail_tag, const uint8_t* nxt = nullptr) {
     constexpr bool kTail = decltype(tail_tag)::value;
+    constexpr bool kRefill = kOr && !kTail;  // nxt: this lane's chunk of the next tile
     if (kTail) {
       const uint64_t b0 = tt * kFTile + uint64_t(lane) * kFLane;
 #pragma unroll
@@ -577,7 +659,57 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
     pre_x = __builtin_amdgcn_readlane(cur[kFBlocks - 1].z, 63);
     pre_y = __builtin_amdgcn_readlane(cur[kFBlocks - 1].w, 63);
     uint32_t flagged = 0, nl = 0;
-    if (P.diag_mode < 2) {
+    if (kOr && P.diag_mode < 2) {
+      const uint32_t laneoff = (ln() & 15) * 16;  // (shadows the kernel's: live inside the tile only)
+      constexpr uint32_t kRA = kFReadAheadOr;
+      static_assert(kRA % 2 == 0 && 16 % kRA == 0, "positions are combined in pairs");
+      // the 5 bytes before the chunk: their rows feed H_-1 .. H_3 (xh[p & 3] = W_0 of byte p - 4,
+      // yh[p & 1] = W_1 of byte p - 2 when position p is evaluated)
+      uint32_t xh[4], yh[2], hprev;
+      {
+        // Whole rows though only some words are used: left alone the compiler narrows these to
+        // ds_read_b32 / b64 / b96, which the replicas do not keep conflict-free (a b32 takes all
+        // 64 lanes at once: four rows per bank; measured 51 conflict cycles per wave and tile).
+        auto row = [&](uint32_t w, uint32_t k) { return reach_read_whole(s_reach, w, k, laneoff); };
+        const uint4 r5 = row(p0, 3), r4 = row(p1, 0), r3 = row(p1, 1), r2 = row(p1, 2), r1 = row(p1, 3);
+        hprev = or3_keep(r5.x, r3.y, r1.z);  // H_-1
+        xh[0] = r4.x, xh[1] = r3.x, xh[2] = r2.x, xh[3] = r1.x;
+        yh[0] = r2.y, yh[1] = r1.y;
+      }
+#pragma unroll
+      for (int j = 0; j < kFBlocks; j++) {
+        const uint32_t wd[4] = {cur[j].x, cur[j].y, cur[j].z, cur[j].w};
+        uint32_t acc = ~0u;  // two positions' fire words per step, AND-ed
+#pragma unroll
+        for (uint32_t g = 0; g < 16; g += kRA) {
+          uint4 m[kRA];
+#pragma unroll
+          for (uint32_t q = 0; q < kRA; q++) {
+            // the chunk's last four rows feed no later position (the next tile starts from its own
+            // prefix rows): their W_0 / W_1 are dead and the compiler narrows these reads (ds_read2_b32 +
+            // b32, b64), which conflict like the prefix rows' did.  TSG_K1_OR_WHOLE_TAIL=1 reads them
+            // whole; off: no conflicts then, but K1 measured 5.13 ms against 4.08
+            if (TSG_K1_OR_WHOLE_TAIL && j == kFBlocks - 1 && g + q >= 12) m[q] = reach_read_whole(s_reach, wd[(g + q) >> 2], (g + q) & 3, laneoff);
+            else m[q] = reach_read(s_reach, wd[(g + q) >> 2], (g + q) & 3, laneoff);
+          }
+#pragma unroll
+          for (uint32_t q = 0; q < kRA; q += 2) {
+            const uint32_t k = g + q;  // even: positions k, k + 1 of the block
+            const uint32_t h0 = or3_keep(xh[k & 3], yh[0], m[q].z);
+            const uint32_t h1 = or3_keep(xh[(k + 1) & 3], yh[1], m[q + 1].z);
+            xh[k & 3] = m[q].x, xh[(k + 1) & 3] = m[q + 1].x;
+            yh[0] = m[q].y, yh[1] = m[q + 1].y;
+            const uint32_t hi = __builtin_amdgcn_perm(h1, h0, 0x07060302u);     // hi(H_k) : hi(H_k+1)
+            const uint32_t lo = __builtin_amdgcn_perm(h0, hprev, 0x05040100u);  // lo(H_k-1) : lo(H_k)
+            acc = and_or_keep(acc, hi, lo);
+            nl += m[q].w + m[q + 1].w;
+            hprev = h1;
+          }
+        }
+        flagged |= uint32_t(acc != ~0u) << j;  // (the newline bucket's slots 4-5 allow nothing: its bit stays 1)
+        if constexpr (kRefill) cur[j] = load16(nxt + 16 * j);
+      }
+    } else if (P.diag_mode < 2) {
       uint32_t st[kFWords] = {~0u, ~0u, ~0u, ~0u};
       reach_apply(reach_read(s_reach, p0, 3, laneoff), st);
 #pragma unroll
@@ -606,8 +738,10 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
       }
     } else {
 #pragma unroll
-      for (int j = 0; j < kFBlocks; j++)
+      for (int j = 0; j < kFBlocks; j++) {
         nl += nl_count4(cur[j].x) + nl_count4(cur[j].y) + nl_count4(cur[j].z) + nl_count4(cur[j].w);
+        if constexpr (kRefill) cur[j] = load16(nxt + 16 * j);
+      }
     }
     {
     // newlines per 1-KiB chunk = per 16-lane DPP row: a row_shr 1/2/4/8 sum puts it in the row's last lane
@@ -617,7 +751,8 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
     nl += uint32_t(__builtin_amdgcn_update_dpp(0, int(nl), 0x118, 0xF, 0xF, true));
     static_assert(kChunk / kFLane == 16, "one newline chunk per DPP row");
     static_assert(kFTile / 16 == 256, "a tile's records: 256 blocks");
-    if ((lane & 15) == 15) reinterpret_cast<uint16_t*>(NL + nl_slots)[lane >> 4] = uint16_t(nl);
+    const uint32_t l = ln();
+    if ((l & 15) == 15) reinterpret_cast<uint16_t*>(NL + nl_slots)[l >> 4] = uint16_t(nl);
     if (++nl_slots == kFNlTiles) flush_nl(tt);
     }
 #if TSG_K1_GROUPQ
@@ -656,18 +791,26 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
     const uint64_t t_end = k_end;
     const uint64_t t_full = t_end < P.n_bytes / kFTile ? t_end : P.n_bytes / kFTile;
     uint64_t t = t_begin;
-    // two register buffers alternate roles (no copies): tile t in A while t + 1 loads into B
     if (t < t_full) load_tile(bufA, t);
-    while (t < t_full) {
-      flush_due();
-      load_tile(bufB, t + 1 < t_full ? t + 1 : t);  // past the range: a harmless reload
-      tile(bufA, t, Full());
-      t++;
-      if (t >= t_full) break;
-      flush_due();
-      load_tile(bufA, t + 1 < t_full ? t + 1 : t);
-      tile(bufB, t, Full());
-      t++;
+    if constexpr (kOr) {
+      while (t < t_full) {
+        flush_due();
+        tile(bufA, t, Full(), lane_ptr(t + 1 < t_full ? t + 1 : t));  // past the range: a harmless reload
+        t++;
+      }
+    } else {
+      // two register buffers alternate roles (no copies): tile t in A while t + 1 loads into B
+      while (t < t_full) {
+        flush_due();
+        load_tile(bufB, t + 1 < t_full ? t + 1 : t);  // past the range: a harmless reload
+        tile(bufA, t, Full());
+        t++;
+        if (t >= t_full) break;
+        flush_due();
+        load_tile(bufA, t + 1 < t_full ? t + 1 : t);
+        tile(bufB, t, Full());
+        t++;
+      }
     }
     if (t < t_end) {  // the partial last tile
       flush_due();
@@ -684,7 +827,7 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
   }
   // whole tiles; the arena's partial last tile (if any, and kept) is the last kept tile: the last of its wave's range
   const bool partial = (P.n_bytes % kFTile) != 0 && tail_kept;
-  const uint64_t k_full = (partial && k_end == n_kept && k_end > k_begin) ? k_end - 1 : k_end;
+  const uint64_t k_full = uni64((partial && k_end == n_kept && k_end > k_begin) ? k_end - 1 : k_end);
   uint64_t k = k_begin, t = t_begin, t_prev = t_begin;
   bool nr_cur = false;  // wave-uniform: tile t starts a run (the range's first tile loaded its prefix above)
   // A run ends before tile t: the staged newline counts and the flag group
@@ -709,8 +852,12 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
     // earlier, with this tile's own prefetch, the pair would stay live across
     // a whole tile body -- two more VGPRs spilled at the kernel's 64.
     if (nr_cur) load_pre(t);
-    load_tile(nxt, k + 1 < k_full ? tn : t);  // past the range: a harmless reload
-    tile(cur, t, Full());
+    if constexpr (kOr) {
+      tile(cur, t, Full(), lane_ptr(k + 1 < k_full ? tn : t));  // (nxt == cur: refilled in place)
+    } else {
+      load_tile(nxt, k + 1 < k_full ? tn : t);  // past the range: a harmless reload
+      tile(cur, t, Full());
+    }
     t_prev = t;
     t = tn;
     nr_cur = nr_n;
@@ -718,10 +865,14 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
   };
   // two register buffers alternate roles (no copies): tile t in A while the next loads into B
   if (k < k_full) load_tile(bufA, t);
-  while (k < k_full) {
-    step(bufA, bufB);
-    if (k >= k_full) break;
-    step(bufB, bufA);
+  if constexpr (kOr) {
+    while (k < k_full) step(bufA, bufA);
+  } else {
+    while (k < k_full) {
+      step(bufA, bufB);
+      if (k >= k_full) break;
+      step(bufB, bufA);
+    }
   }
   if (k < k_end) {  // the partial last tile
     if (nr_cur) run_boundary();
@@ -2581,6 +2732,14 @@ GpuEngine::GpuEngine(const CompiledRules& cr, int device) : device_(device) {
   {  // the K0 phase and the read-back of pipelined scans run beside the engine stream
     if (const char* e = std::getenv("TSG_OVERLAP_K0")) overlap_k0_ = std::atoi(e) != 0;
     if (const char* e = std::getenv("TSG_READBACK_STREAM")) readback_stream_ = std::atoi(e) != 0;
+    if (const char* e = std::getenv("TSG_K1_FORM")) {  // K1's window evaluation: or | shiftor
+      if (std::strcmp(e, "or") == 0) k1_or_ = true;
+      else if (std::strcmp(e, "shiftor") == 0) k1_or_ = false;
+      else {
+        err_ = std::string("TSG_K1_FORM=") + e + " (or, shiftor are the forms)";
+        return;
+      }
+    }
     int lo = 0, hi = 0;
     if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) lo = hi = 0;
     bool ok = hipStreamCreateWithPriority(&aux_stream_, hipStreamNonBlocking, hi) == hipSuccess &&
@@ -4187,8 +4346,13 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
       uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((f_tiles + kScanWaves - 1) / kScanWaves, 256 * kFWgPerCu)));
   if (k1_grid_cap_) f_grid = std::min(f_grid, k1_grid_cap_);
   HIP_OK(hipEventRecord(E.ev[kEvK1], stream_));
-  if (skip) filter_kernel<true><<<f_grid, kScanThreads, 0, stream_>>>(fp);
-  else filter_kernel<false><<<f_grid, kScanThreads, 0, stream_>>>(fp);
+  if (k1_or_) {
+    if (skip) filter_kernel<true, true><<<f_grid, kScanThreads, 0, stream_>>>(fp);
+    else filter_kernel<false, true><<<f_grid, kScanThreads, 0, stream_>>>(fp);
+  } else {
+    if (skip) filter_kernel<true, false><<<f_grid, kScanThreads, 0, stream_>>>(fp);
+    else filter_kernel<false, false><<<f_grid, kScanThreads, 0, stream_>>>(fp);
+  }
   HIP_OK(hipGetLastError());
   HIP_OK(hipEventRecord(E.ev[kEvK2], stream_));
   // K2: confirm + verify

@@ -125,12 +125,6 @@ int tsg_debug_pool_budget(void);
  * scanner without a GPU engine.  (Bookkeeping for tests; call it between scans.) */
 struct tsg_scanner;
 int tsg_debug_scanner_engine(struct tsg_scanner* s, uint64_t out[4]);
-/* The engine report's fifth field, beside the four above because out[4] is a
- * fixed size callers allocate: how the scanner's streaming filter (K1)
- * evaluates its window -- 1 as an OR of slot masks (TSG_K1_FORM=or, the
- * default), 0 as the shift-or recurrence (TSG_K1_FORM=shiftor); read at scanner
- * creation, the same for Run and Enqueue.  -1 for a scanner without a GPU engine. */
-int tsg_debug_scanner_k1_form(struct tsg_scanner* s);
 /* K1's OR-form table (trivy_amd/csrc/k1_orform.h) of compiled rules: out receives
  * 256 rows of 4 u32, row b = (W_0, W_1, W_2, W_3)[b] with W_k = m_{2k+1} << 16 |
  * m_{2k}, m_s the 16-bit not-allowed mask of window slot s over the 16 buckets

@@ -204,12 +204,10 @@ _VARIANT_CASE = {}
 
 
 @pytest.mark.parametrize("env", [
-    {},                                          # items + classes in LDS, 16-wave workgroups, first-byte test
-    {"TSG_FOLD_WAVES": "4"},                      # the same staging in 4-wave workgroups
+    {},                                          # items + classes in LDS, 16-wave workgroups
     {"TSG_FOLD_STAGE": "0"},                      # global tables, 4-wave workgroups
-    {"TSG_FOLD_STAGE": "0", "TSG_FOLD_FIRST": "0"},  # ... without the first-byte test
     {"TSG_CONFIRM_STAGE_CLASSES": "0"},            # confirm kernel with its classes in global memory
-], ids=["default", "waves4", "unstaged", "unstaged-nofirst", "confirm-global-classes"])
+], ids=["default", "unstaged", "confirm-global-classes"])
 def test_c3_global_table_kernel_variants_match_cpuref(tmp_path, monkeypatch, env):
     """The global-table (2,087-rule) fold and confirm kernels in each selectable shape (engine.hip
     fold_kernel / confirm_kernel): every file of a C3 corpus holding fold
@@ -217,7 +215,7 @@ def test_c3_global_table_kernel_variants_match_cpuref(tmp_path, monkeypatch, env
     from bench import full_diff
     from trivy_amd import corpus
     import trivy_amd.secret as secret
-    for k in ("TSG_FOLD_WAVES", "TSG_FOLD_STAGE", "TSG_FOLD_FIRST", "TSG_CONFIRM_STAGE_CLASSES"):
+    for k in ("TSG_FOLD_STAGE", "TSG_CONFIRM_STAGE_CLASSES"):
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)

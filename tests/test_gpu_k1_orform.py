@@ -1,23 +1,18 @@
-"""K1's two window evaluations, TSG_K1_FORM=or (default) and =shiftor, against the model and each other.
+"""K1's window evaluation (an OR of slot masks) against the model.
 
-Every case runs through tsg_debug_engine_stages (tests/stage_model.py run_engine) under both
-forms, with K1's grid uncapped and capped to one workgroup (TSG_DIAG_K1_GRID=1: a wave then
-streams several tiles, so the OR form's in-place refill of its tile buffer and the carried
-8-byte prefix are exercised), and asserts
-
-  * invariants 1-2 of check_all against the CPU model -- chunk map, per-KiB newline counts,
-    flagged blocks each once -- and the remaining invariants with them (check_all);
-  * the two forms' flagged-record sets are equal, and their per-KiB newline counts.
+Every case runs through tsg_debug_engine_stages (tests/stage_model.py run_engine) with K1's
+grid uncapped and capped to one workgroup (TSG_DIAG_K1_GRID=1: a wave then streams several
+tiles, so the in-place refill of its tile buffer and the carried 8-byte prefix are exercised),
+and asserts invariants 1-2 of check_all against the CPU model -- chunk map, per-KiB newline
+counts, flagged blocks each once -- and the remaining invariants with them (check_all).
 
 Cases: tests/stage_cases.py boundaries, arena edges 0..7, files, dense blocks; one seeded case
 of this file with a firing window end at every byte 59..69 of a lane's 64-B chunk and at every
-byte 4091..4101 of a 4-KiB tile (the OR form takes bytes p-5..p-1 from the lane before, or from
+byte 4091..4101 of a 4-KiB tile (the kernel takes bytes p-5..p-1 from the lane before, or from
 the tile before through scalar registers); arenas of 1, 63, 64, 4095, 4096 and 4097 bytes; and
 one batch with a skip list (filter_kernel<true>: run boundaries, a run's first tile, a kept
 partial last tile) through tsg_debug_engine_stages_skip: the sorted record set equals the model's
-blocks of the kept tiles, the kept tiles' per-KiB newline counts equal the model's, and both are
-equal under the two forms.  (Each tsg_debug_engine_stages call builds its own engine, so
-TSG_K1_FORM applies per call; test_scanner_reports_the_form checks the switch is read.)
+blocks of the kept tiles and the kept tiles' per-KiB newline counts equal the model's.
 """
 import ctypes as c
 import random
@@ -32,35 +27,28 @@ from trivy_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
-FORMS = ("or", "shiftor")
 GRIDS = {"uncapped": {}, "one-workgroup": {"TSG_DIAG_K1_GRID": "1"}}
 
 
-def _both_forms(name, prepared, monkeypatch, grid, full=True):
+def _run(name, prepared, monkeypatch, grid, full=True):
     case, model, e, matches = prepared
     b = case["batch"]
-    dumps = {}
-    for form in FORMS:
-        with monkeypatch.context() as m:
-            for k, v in {**(case.get("env") or {}), **GRIDS[grid], "TSG_K1_FORM": form}.items():
-                m.setenv(k, v)
-            d = sm.run_engine(model, b)
-        sm.check_overflow(d)
-        sm.check_chunks(d, e)   # invariant 1
-        sm.check_blocks(d, e)   # invariant 2
-        if full:
-            sm.check_all(d, e, model, b, matches)
-        dumps[form] = d
-    a, s = dumps["or"], dumps["shiftor"]
-    assert np.array_equal(np.sort(a.recs), np.sort(s.recs))
-    assert np.array_equal(a.nl, s.nl)
-    print("k1-form %s %s: bytes %d blocks %d newlines %d" % (name, grid, b.n_bytes, len(a.recs), int(a.nl.sum())))
-    return a
+    with monkeypatch.context() as m:
+        for k, v in {**(case.get("env") or {}), **GRIDS[grid]}.items():
+            m.setenv(k, v)
+        d = sm.run_engine(model, b)
+    sm.check_overflow(d)
+    sm.check_chunks(d, e)   # invariant 1
+    sm.check_blocks(d, e)   # invariant 2
+    if full:
+        sm.check_all(d, e, model, b, matches)
+    print("k1 %s %s: bytes %d blocks %d newlines %d" % (name, grid, b.n_bytes, len(d.recs), int(d.nl.sum())))
+    return d
 
 
 @pytest.mark.parametrize("grid", sorted(GRIDS))
 def test_boundaries(monkeypatch, grid):
-    d = _both_forms("boundaries", _prepared("boundaries", sc.case_boundaries, monkeypatch), monkeypatch, grid)
+    d = _run("boundaries", _prepared("boundaries", sc.case_boundaries, monkeypatch), monkeypatch, grid)
     assert len(d.recs) >= 100
 
 
@@ -68,19 +56,19 @@ def test_boundaries(monkeypatch, grid):
 def test_arena_edges(monkeypatch, grid):
     for k in range(8):
         p = _prepared("arena-edges-%d" % k, lambda: sc.case_arena_edges(k), monkeypatch)
-        assert len(_both_forms("arena-edges-%d" % k, p, monkeypatch, grid).recs) >= 4
+        assert len(_run("arena-edges-%d" % k, p, monkeypatch, grid).recs) >= 4
 
 
 @pytest.mark.parametrize("grid", sorted(GRIDS))
 def test_files(monkeypatch, grid):
-    _both_forms("files", _prepared("files", sc.case_files, monkeypatch), monkeypatch, grid)
+    _run("files", _prepared("files", sc.case_files, monkeypatch), monkeypatch, grid)
 
 
 @pytest.mark.parametrize("grid", sorted(GRIDS))
 def test_dense_blocks(monkeypatch, grid):
     p = _prepared("dense", sc.case_dense, monkeypatch)
     sc.check_case_shape("dense", p[0], p[2], p[1])
-    _both_forms("dense", p, monkeypatch, grid)
+    _run("dense", p, monkeypatch, grid)
 
 
 # ---- window ends around lane-chunk and tile boundaries ------------------------------------------------
@@ -124,7 +112,7 @@ def test_chunk_and_tile_edges(monkeypatch, grid):
     assert all(fr[e] for e in case["ends"])
     assert {e % 64 for e in case["ends"][:11]} == {x % 64 for x in CHUNK_ENDS}
     assert {e % 4096 for e in case["ends"][11:]} == {x % 4096 for x in TILE_ENDS}
-    d = _both_forms("chunk-edges", p, monkeypatch, grid)
+    d = _run("chunk-edges", p, monkeypatch, grid)
     assert set(np.array(case["ends"]) >> 4) <= set(d.recs.tolist())
 
 
@@ -141,7 +129,7 @@ def test_small_arenas(monkeypatch, grid):
     blocks = 0
     for n in (1, 63, 64, 4095, 4096, 4097):
         p = _prepared("k1-small-%d" % n, lambda: case_small(n), monkeypatch)
-        blocks += len(_both_forms("small-%d" % n, p, monkeypatch, grid).recs)
+        blocks += len(_run("small-%d" % n, p, monkeypatch, grid).recs)
     assert blocks >= 5
 
 
@@ -237,37 +225,19 @@ def skip_batch():
 @pytest.mark.parametrize("grid", sorted(GRIDS))
 def test_skip_list_runs(skip_batch, monkeypatch, grid):
     """filter_kernel<true>: the sorted record set equals the model's blocks of the kept tiles, each once;
-    the per-KiB newline counts of the kept tiles equal the model's; both are equal under the two forms.
+    the per-KiB newline counts of the kept tiles equal the model's.
     (The chunks of a dropped tile are not written by the scan and are not compared.)"""
     B = skip_batch
-    out = {}
-    for form in FORMS:
-        with monkeypatch.context() as m:
-            m.setenv("TSG_K1_FORM", form)
-            for k, v in GRIDS[grid].items():
-                m.setenv(k, v)
-            counters, recs, nl = run_engine_skip(B["model"], B["batch"], B["skip"])
-        assert not counters[sm.CT_REC_OVF] and counters[sm.CT_RECS] == len(recs)
-        got = np.sort(recs)
-        assert np.array_equal(got, B["blocks"]), (form, len(got), len(B["blocks"]),
-                                                  sorted(set(got.tolist()) ^ set(B["blocks"].tolist()))[:8])
-        assert len(nl) == len(B["nl"])
-        assert np.array_equal(nl[B["kept_chunks"]], B["nl"][B["kept_chunks"]]), form
-        out[form] = (got, nl[B["kept_chunks"]])
-    assert np.array_equal(out["or"][0], out["shiftor"][0]) and np.array_equal(out["or"][1], out["shiftor"][1])
+    with monkeypatch.context() as m:
+        for k, v in GRIDS[grid].items():
+            m.setenv(k, v)
+        counters, recs, nl = run_engine_skip(B["model"], B["batch"], B["skip"])
+    assert not counters[sm.CT_REC_OVF] and counters[sm.CT_RECS] == len(recs)
+    got = np.sort(recs)
+    assert np.array_equal(got, B["blocks"]), (len(got), len(B["blocks"]),
+                                              sorted(set(got.tolist()) ^ set(B["blocks"].tolist()))[:8])
+    assert len(nl) == len(B["nl"])
+    assert np.array_equal(nl[B["kept_chunks"]], B["nl"][B["kept_chunks"]])
     assert len(B["blocks"]) > 20 and int(B["nl"][B["kept_chunks"]].sum()) > 100
-    print("k1-form skip %s: tiles %d kept %d blocks %d" % (grid, len(B["kept"]), int(B["kept"].sum()), len(B["blocks"])))
+    print("k1 skip %s: tiles %d kept %d blocks %d" % (grid, len(B["kept"]), int(B["kept"].sum()), len(B["blocks"])))
 
-
-def test_scanner_reports_the_form(monkeypatch):
-    """tsg_debug_scanner_k1_form: TSG_K1_FORM is read at scanner creation; or is the default."""
-    import trivy_amd.secret as secret
-    for form, want in ((None, 1), ("or", 1), ("shiftor", 0)):
-        with monkeypatch.context() as m:
-            if form is None:
-                m.delenv("TSG_K1_FORM", raising=False)
-            else:
-                m.setenv("TSG_K1_FORM", form)
-            s = secret.NewScanner(None)
-        s._L.tsg_debug_scanner_k1_form.argtypes = [c.c_void_p]
-        assert s._L.tsg_debug_scanner_k1_form(s._h) == want, form

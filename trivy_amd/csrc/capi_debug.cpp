@@ -504,8 +504,8 @@ int tsg_debug_engine_stages_skip(const tsg_compiled* c, int device, const uint8_
       ok(hipMemcpy(d_off, offsets, (size_t(n_files) + 1) * 8, hipMemcpyHostToDevice)) &&
       (!skip || n_files == 0 ||
        (ok(hipMalloc(&d_skip, n_files)) && ok(hipMemcpy(d_skip, skip, n_files, hipMemcpyHostToDevice))))) {
-    // a fresh engine per call: the TSG_* switches its constructor reads (TSG_K1_FORM among them) apply to
-    // this scan -- tests that compare variants rely on it
+    // a fresh engine per call: the TSG_* switches its constructor reads apply to this scan -- tests
+    // that compare variants rely on it
     std::unique_ptr<tsg::GpuEngine> eng(new tsg::GpuEngine(c->cr, device));
     std::vector<tsg::Candidate> cands;
     tsg::SkipIn sk;

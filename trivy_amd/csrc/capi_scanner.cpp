@@ -723,11 +723,6 @@ int tsg_debug_scanner_engine(tsg_scanner* s, uint64_t out[4]) {
   return 0;
 }
 
-int tsg_debug_scanner_k1_form(tsg_scanner* s) {
-  if (!s || !s->s || s->s->n_engines() == 0) return -1;
-  return s->s->engine_at(0)->k1_or_form() ? 1 : 0;  // (every engine of a scanner reads the same TSG_K1_FORM)
-}
-
 int tsg_scanner_set_fetch_options(tsg_scanner* s, const tsg_fetch_options* opt) {
   if (!s || !s->s || !opt) {
     tsg::SetError("tsg_scanner_set_fetch_options: NULL argument");

@@ -271,7 +271,7 @@ class GpuEngine {
   // on aux_stream_ while scan i's kernels run, and scan i's candidates leave
   // on rb_stream_ while scan i + 1's kernels run.  Everything produced and
   // consumed between K1 and finalize (d_nl_, d_recs_, d_hits_, d_folds_,
-  // d_wins_, the full-scan lists) stays single: only stream_ touches it.
+  // the full-scan lists) stays single: only stream_ touches it.
   struct WorkSet {
     void* chunk_file = nullptr; size_t cap_chunk_file = 0;
     // scans with a skip list: the kept-tile bitmap, the runs of kept tiles (begin tile, kept tiles before),
@@ -389,9 +389,6 @@ class GpuEngine {
     uint64_t retired_pending, retired_freed, cand_cap, slot_bytes;
   };
   HostMemInfo host_mem_info();
-  // K1's window evaluation in this engine's scans (TSG_K1_FORM at construction;
-  // DESIGN.md §4.1): true the OR of slot masks, false the shift-or recurrence.
-  bool k1_or_form() const { return k1_or_; }
 
  private:
   bool Transform(int b, uint32_t nf, const uint8_t** arena, const uint64_t** offsets, uint64_t* n_bytes,
@@ -408,7 +405,6 @@ class GpuEngine {
   PhaseEvents run_ev_;  // Run's (Slot::ev for Enqueue'd scans)
   // tables
   uint32_t diag_mode_ = 0, diag_confirm_ = 0;
-  bool k1_or_ = true;  // TSG_K1_FORM: or (default) | shiftor
   AnchorInfo* d_anchors_ = nullptr;
   RuleGpu* d_rules_ = nullptr;
   uint32_t* d_rule_kw_ = nullptr;
@@ -428,7 +424,6 @@ class GpuEngine {
   void* d_fold_idx_off_ = nullptr;   // fold kernel: capable tasks by (rune kind, q, key byte)
   void* d_fold_idx_items_ = nullptr;
   uint32_t n_fold_cap_k_idx_ = 0, n_fold_cap_s_idx_ = 0;
-  bool fold_idx_ = true;
   void* d_kwfold_pairs_ = nullptr;  // kwfold kernel work list (keyword items through U+0130 / U+212A)
   uint32_t n_kwf_ri_ = 0, n_kwf_rk_ = 0, n_kwf_ci_ = 0, n_kwf_ck_ = 0;
   bool kw_fold_ = false;
@@ -440,10 +435,8 @@ class GpuEngine {
   uint32_t ft_hkeys_ = 0, ft_hitems_ = 0, hash_bits_ = 0, hash_buckets_ = 0;  // literal-window hash
   size_t c_lds_bytes_ = 0;
   bool lds_tabs_ = true;  // confirm/fold kernels stage the item tables in LDS
-  bool fold_stage_ = false;        // global-table fold kernel: items + classes staged in LDS
+  bool fold_stage_ = false;        // global-table fold kernel: items + classes staged in LDS, 16-wave workgroups
   uint32_t fold_grid_ = 2048;      // workgroups of the LDS-table fold kernel (TSG_FOLD_GRID)
-  bool fold_wide_ = false;         // staged global-table fold kernel: 16-wave workgroups (TSG_FOLD_WAVES=4: 4)
-  bool fold_check_first_ = true;   // global-table fold kernel: first-byte set test per start (TSG_FOLD_FIRST=0: off)
   bool c_stage_classes_ = false;   // global-table confirm kernel: classes staged in LDS
   size_t fold_stage_bytes_ = 0;
   uint32_t n_fclasses_ = 0;
@@ -456,7 +449,6 @@ class GpuEngine {
   void NoteSkip(const uint32_t* info, BatchStats* st) const;
   void* d_hits_ = nullptr; size_t cap_hits_ = 0;
   void* d_folds_ = nullptr; size_t cap_folds_ = 0;
-  void* d_wins_ = nullptr; size_t cap_wins_ = 0;  // TSG_K2_PACK experiment: packed confirm windows
   // host-batch streaming (RunHost): a ring of staging buffers, a copy stream
   hipStream_t copy_stream_ = nullptr;
   static constexpr int kNStage = 4;  // staging buffers: the copier runs up to three chunks ahead

@@ -5,8 +5,9 @@
 //                   4-KiB tiles that hold a byte of a file that is not skipped,
 //                   as runs of kept tiles; K1 then streams those alone.
 //  K1 filter      : streams every arena byte once (64 B per lane per tile);
-//                   bucketed shift-or over 15 item buckets + a newline bucket
-//                   (reach table replicated 16x in LDS); records the flagged
+//                   bucketed window filter over 15 item buckets + a newline
+//                   bucket, evaluated as an OR of slot masks (table rows
+//                   replicated 16x in LDS); records the flagged
 //                   16-B blocks and counts '\n' per chunk.
 //  K2 confirm     : three compacted wave phases over the flagged blocks:
 //                   fires -> core-table item candidates -> exact item check
@@ -138,7 +139,7 @@ __device__ __forceinline__ void wave_sync() {
 }
 
 // ---------------------------------------------------------------------------
-// K1: streaming bucketed shift-or filter
+// K1: streaming bucketed window filter
 // ---------------------------------------------------------------------------
 constexpr int kFLane = 64;           // bytes per lane per tile (4 blocks of 16 B)
 constexpr int kFBlocks = kFLane / 16;
@@ -157,25 +158,13 @@ constexpr int kFNlTiles = TSG_K1_NLTILES;           // tiles whose newline count
 #define TSG_K1_WGS 2
 #endif
 constexpr int kFWgPerCu = TSG_K1_WGS;  // 1: leaves ~80 KiB of LDS per CU to a concurrent scan's confirm kernel
-#ifndef TSG_K1_GROUPQ  // flagged blocks compacted once per kFGroup tiles (0: per tile and block column)
-#define TSG_K1_GROUPQ 1
-#endif
-constexpr uint32_t kFGroup = 8;  // tiles per compaction: 4 flag bits each, 32 per lane
-#ifndef TSG_K1_READAHEAD
-#define TSG_K1_READAHEAD 4
-#endif
-constexpr uint32_t kFReadAhead = TSG_K1_READAHEAD;  // table rows read ahead of the shift-or chain
+constexpr uint32_t kFGroup = 8;  // tiles per compaction of the flagged blocks: 4 flag bits each, 32 per lane
 #ifndef TSG_K1_OR_READAHEAD
 #define TSG_K1_OR_READAHEAD 4
 #endif
-#ifndef TSG_K1_OR_WHOLE_TAIL
-#define TSG_K1_OR_WHOLE_TAIL 0
-#endif
-constexpr uint32_t kFReadAheadOr = TSG_K1_OR_READAHEAD;  // ... ahead of the OR form's combine (8 measured slower on C2)
+constexpr uint32_t kFReadAheadOr = TSG_K1_OR_READAHEAD;  // table rows read ahead of the combine (8 measured slower on C2)
 constexpr int kFWindow = 6;          // filter window: a fire stays visible for 9 - 6 = 3 bytes
 constexpr int kFWords = 4;           // 16 buckets = 4 u32 registers of 8 slots x 4 buckets
-constexpr uint32_t kFireBits = 0xFFF00000u;  // slots 5..7 of a register
-constexpr uint32_t kNlBits = 0x8888u;        // newline bucket (15 = register 3, lane 3), slots 0..3
 static_assert(kChunk % kFLane == 0 && kChunk / kFLane <= 64, "a newline chunk must be whole lane chunks");
 static_assert(kFChunks * kChunk == kFTile && kFChunks == 4, "a tile's newline counts are one u64");
 
@@ -383,12 +372,9 @@ __device__ __forceinline__ uint32_t word_of(uint4 v, uint32_t i) {
   return i < 2 ? (i == 0 ? v.x : v.y) : (i == 2 ? v.z : v.w);
 }
 
-__device__ __forceinline__ void load_reach_lds(uint8_t* s_reach, const uint32_t* reach, uint32_t copies, int tid,
-                                               int nthreads) {
-  for (uint32_t i = tid; i < 256 * copies; i += nthreads) {
-    const uint32_t b = i / copies;
-    reinterpret_cast<uint4*>(s_reach)[i] = reinterpret_cast<const uint4*>(reach)[b];
-  }
+__device__ __forceinline__ void load_reach_lds(uint8_t* s_reach, const uint32_t* reach, int tid, int nthreads) {
+  for (uint32_t i = tid; i < 256; i += nthreads)
+    reinterpret_cast<uint4*>(s_reach)[i] = reinterpret_cast<const uint4*>(reach)[i];
 }
 
 // The OR-form image (k1_orform.h): row b = 16 copies of (W_0, W_1, W_2, W_3)[b],
@@ -421,48 +407,41 @@ __device__ __forceinline__ uint32_t and_or_keep(uint32_t acc, uint32_t a, uint32
 // K1.  A wave owns 4-KiB tiles (grid-strided); lane l streams its 64
 // contiguous bytes as 4 x 16-B loads with the next tile's loads in flight.
 // The 5 bytes before a lane's chunk come from lane l-1 (lane 0: an 8-B load).
-// Per byte: table address by v_perm, one conflict-free ds_read_b128 (issued a
-// block ahead of the chain), four v_lshl_or_b32.  Every 3 bytes the top slots
-// are AND-ed into the block's accumulator; every 4 bytes the newline bucket's
-// 4 slots are popcounted.  Flagged blocks go through a ballot/mbcnt-compacted
-// per-wave LDS queue to the global record list (one atomic per 64 records);
-// the confirm kernel (K2) checks them exactly.
-// (<= 64 VGPRs in both shapes: with one workgroup per CU the other half of the
-// VGPRs and LDS go to a concurrent scan's confirm kernel)
-// kOr (TSG_K1_FORM=or, the default): the window is evaluated as an OR of slot
-// masks from the re-laid table (k1_orform.h) instead of the recurrence.  With
+// Per byte: table address by v_perm and one conflict-free ds_read_b128 of the
+// re-laid table (k1_orform.h), issued kFReadAheadOr rows ahead.  The window is
+// an OR of slot masks: with
 //   H_p = W_0[b_{p-4}] | W_1[b_{p-2}] | W_2[b_p]                 (one v_or3_b32)
 // position p's 16 fire bits are hi(H_p) | lo(H_{p-1}); two positions at once:
 // two v_perm gather {hi(H_p) : hi(H_{p+1})} and {lo(H_{p-1}) : lo(H_p)} and one
 // v_bitop3 ANDs their OR into the block's accumulator.  W_3 counts newlines.
-// No dependent chain, the same one ds_read_b128 per byte, the same flagged
-// blocks and newline counts (TSG_K1_FORM=shiftor keeps the recurrence).
+// No dependent chain.  Flagged blocks go through a per-wave LDS queue to the
+// global record list; the confirm kernel (K2) checks them exactly.
+// (<= 64 VGPRs: with one workgroup per CU the other half of the VGPRs and LDS
+// go to a concurrent scan's confirm kernel)
 // kRuns: the scan has a skip list (P.runs).  Without one the kernel is the
 // instantiation with the plain loop over a contiguous tile range: the run walk's
 // scalar bookkeeping cost that loop 3 % (5.35 -> 5.5 ms on C2) when both shared one.
-template <bool kRuns, bool kOr>
+template <bool kRuns>
 __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P) {
   __shared__ __attribute__((aligned(16))) uint8_t s_reach[65536];
   __shared__ uint32_t s_queue[kScanWaves * kFQueue];
   __shared__ uint64_t s_nl[kScanWaves * kFNlTiles];  // per wave: the last tiles' 4 chunk counts
   const int tid = threadIdx.x;
-  if constexpr (kOr) load_orform_lds(s_reach, P.reach, tid, blockDim.x);
-  else load_reach_lds(s_reach, P.reach, 16, tid, blockDim.x);
+  load_orform_lds(s_reach, P.reach, tid, blockDim.x);
   __syncthreads();
   const uint32_t lane = tid & 63;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(uint32_t(tid) >> 6);
-  const uint32_t laneoff = (lane & 15) * 16;
   uint32_t* Q = s_queue + wave * kFQueue;
   uint64_t* NL = s_nl + wave * kFNlTiles;
-  // The OR form holds more table words live than the chain (6 history words
-  // and the rows in flight), so at 64 VGPRs nothing derived from the lane index
-  // may stay in a register across a tile: each use takes the index through an
-  // empty asm and recomputes its address (a few VALU per tile).  Left to the
-  // compiler these values are spilled and reloaded inside the tile loop, and a
-  // reload's s_waitcnt vmcnt(0) waits for the next tile's loads in flight.
+  // The tile body holds 6 history words and the table rows in flight live, so
+  // at 64 VGPRs nothing derived from the lane index may stay in a register
+  // across a tile: each use takes the index through an empty asm and
+  // recomputes its address (a few VALU per tile).  Left to the compiler these
+  // values are spilled and reloaded inside the tile loop, and a reload's
+  // s_waitcnt vmcnt(0) waits for the next tile's loads in flight.
   auto ln = [&]() {
     uint32_t l = lane;
-    if constexpr (kOr) asm volatile("" : "+v"(l));
+    asm volatile("" : "+v"(l));
     return l;
   };
   uint32_t nl_slots = 0;  // wave-uniform: tiles staged in NL
@@ -484,12 +463,9 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
   const bool tail_kept = RUNS ? uni(P.run_info[kSkTailKept]) != 0 : true;
   const uint64_t per = n_kept / n_waves, extra = n_kept % n_waves;
   // (the 64-bit division is vector code, so the wave's range comes out in VGPRs though it is
-  // wave-uniform; the OR form moves it to scalar registers: the tile counter and its bounds
-  // otherwise hold 6 of the kernel's 64 VGPRs through the loop)
-  auto uni64 = [&](uint64_t v) {
-    if constexpr (kOr) return uint64_t(uni(uint32_t(v))) | uint64_t(uni(uint32_t(v >> 32))) << 32;
-    else return v;
-  };
+  // wave-uniform; moved to scalar registers: the tile counter and its bounds otherwise hold 6
+  // of the kernel's 64 VGPRs through the loop)
+  auto uni64 = [&](uint64_t v) { return uint64_t(uni(uint32_t(v))) | uint64_t(uni(uint32_t(v >> 32))) << 32; };
   const uint64_t k_begin = uni64(wid * per + (wid < extra ? wid : extra));
   const uint64_t k_end = uni64(k_begin + per + (wid < extra ? 1 : 0));
   uint32_t run = 0;             // wave-uniform: the run of the tile in hand
@@ -508,12 +484,10 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
     t_begin = uint64_t(uni(r0.x)) + (k_begin - uni(r0.y));
     run_k1 = uni(RUNS[lo + 1].y);
   }
-  // Shift-or form: two register buffers, the next tile loading into one while
-  // the other is worked on.  OR form: one buffer refilled in place -- a block's
-  // 4 registers take the next tile's same block as soon as the block is done
-  // (3/4 of a tile ahead of its use), which frees 16 VGPRs for the table words
-  // the OR form keeps live; bufB is then unused.
-  uint4 bufA[kFBlocks], bufB[kFBlocks];
+  // One register buffer refilled in place: a block's 4 registers take the next
+  // tile's same block as soon as the block is done (3/4 of a tile ahead of its
+  // use), which leaves 16 VGPRs to the table words the tile body keeps live.
+  uint4 buf[kFBlocks];
   uint32_t pre_x = 0, pre_y = 0;  // wave-uniform: the 8 bytes before the current tile
   auto load_pre = [&](uint64_t tt) {  // tt > 0
     const uint2 pv = *reinterpret_cast<const uint2*>(P.arena + tt * kFTile - 8);
@@ -557,17 +531,15 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
     }
     qn = 0;
   };
-#if TSG_K1_GROUPQ
   // Flagged blocks: each lane keeps 4 bits per tile for kFGroup consecutive
   // tiles of its range; one compaction per group appends the group's records
   // to the wave's LDS queue (a DPP wave prefix sum of the lanes' counts, each
   // lane writing its own), and the queue goes to the global list in flushes of
-  // >= kFFlushAt records (one atomic each).  Against the per-tile, per-column
-  // ballot appends (TSG_K1_GROUPQ=0) it measured equal to 0.2 ms faster on C2;
-  // an atomic per group straight to the global list instead of the queue
-  // serialised on the one counter (K1 5.5 -> 7.5 ms).  (Diagnostic builds that
-  // dropped the queue let the compiler delete the filter itself -- only the
-  // newline bucket's word stayed live -- so they measured nothing: DESIGN §4.1.)
+  // >= kFFlushAt records (one atomic each).  An atomic per group straight to
+  // the global list instead of the queue serialised on the one counter
+  // (K1 5.5 -> 7.5 ms).  (Diagnostic builds that dropped the queue let the
+  // compiler delete the filter itself -- only the newline bucket's word stayed
+  // live -- so they measured nothing: DESIGN §4.1.)
   uint32_t fl_acc = 0;  // per lane: bit 4 * (tile - grp_t0) + block column
   uint32_t grp_n = 0;   // wave-uniform: tiles in the group so far
   uint64_t grp_t0 = 0;  // wave-uniform: the group's first tile
@@ -612,7 +584,6 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
     fl_acc = 0;
     grp_n = 0;
   };
-#endif
   // Global stores are rare on purpose: on gfx9 a store counts in vmcnt like
   // the loads, so a store per tile would make the next tile's wait for its
   // prefetched data also wait for the store's completion.
@@ -629,12 +600,13 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
     }
     nl_slots = 0;
   };
-  // One tile: `cur` holds its 64 bytes per lane.  kTail: the arena's last,
-  // partial tile (bytes past the end are zeroed); kept out of the main loop's
-  // code so the full tiles carry no masking state.
+  // One tile: `cur` holds its 64 bytes per lane and is refilled from nxt, this
+  // lane's chunk of the next tile.  kTail: the arena's last, partial tile (bytes
+  // past the end are zeroed, no refill); kept out of the main loop's code so the
+  // full tiles carry no masking state.
   auto tile = [&](uint4* cur, uint64_t tt, auto tail_tag, const uint8_t* nxt = nullptr) {
     constexpr bool kTail = decltype(tail_tag)::value;
-    constexpr bool kRefill = kOr && !kTail;  // nxt: this lane's chunk of the next tile
+    constexpr bool kRefill = !kTail;
     if (kTail) {
       const uint64_t b0 = tt * kFTile + uint64_t(lane) * kFLane;
 #pragma unroll
@@ -659,8 +631,8 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
     pre_x = __builtin_amdgcn_readlane(cur[kFBlocks - 1].z, 63);
     pre_y = __builtin_amdgcn_readlane(cur[kFBlocks - 1].w, 63);
     uint32_t flagged = 0, nl = 0;
-    if (kOr && P.diag_mode < 2) {
-      const uint32_t laneoff = (ln() & 15) * 16;  // (shadows the kernel's: live inside the tile only)
+    if (P.diag_mode < 2) {
+      const uint32_t laneoff = (ln() & 15) * 16;  // (live inside the tile only)
       constexpr uint32_t kRA = kFReadAheadOr;
       static_assert(kRA % 2 == 0 && 16 % kRA == 0, "positions are combined in pairs");
       // the 5 bytes before the chunk: their rows feed H_-1 .. H_3 (xh[p & 3] = W_0 of byte p - 4,
@@ -683,15 +655,12 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
 #pragma unroll
         for (uint32_t g = 0; g < 16; g += kRA) {
           uint4 m[kRA];
+          // the chunk's last four rows feed no later position (the next tile starts from its own
+          // prefix rows): their W_0 / W_1 are dead and the compiler narrows these reads (ds_read2_b32 +
+          // b32, b64), which conflict like the prefix rows' did.  Read whole they do not conflict,
+          // but K1 measured 5.13 ms against 4.08
 #pragma unroll
-          for (uint32_t q = 0; q < kRA; q++) {
-            // the chunk's last four rows feed no later position (the next tile starts from its own
-            // prefix rows): their W_0 / W_1 are dead and the compiler narrows these reads (ds_read2_b32 +
-            // b32, b64), which conflict like the prefix rows' did.  TSG_K1_OR_WHOLE_TAIL=1 reads them
-            // whole; off: no conflicts then, but K1 measured 5.13 ms against 4.08
-            if (TSG_K1_OR_WHOLE_TAIL && j == kFBlocks - 1 && g + q >= 12) m[q] = reach_read_whole(s_reach, wd[(g + q) >> 2], (g + q) & 3, laneoff);
-            else m[q] = reach_read(s_reach, wd[(g + q) >> 2], (g + q) & 3, laneoff);
-          }
+          for (uint32_t q = 0; q < kRA; q++) m[q] = reach_read(s_reach, wd[(g + q) >> 2], (g + q) & 3, laneoff);
 #pragma unroll
           for (uint32_t q = 0; q < kRA; q += 2) {
             const uint32_t k = g + q;  // even: positions k, k + 1 of the block
@@ -708,33 +677,6 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
         }
         flagged |= uint32_t(acc != ~0u) << j;  // (the newline bucket's slots 4-5 allow nothing: its bit stays 1)
         if constexpr (kRefill) cur[j] = load16(nxt + 16 * j);
-      }
-    } else if (P.diag_mode < 2) {
-      uint32_t st[kFWords] = {~0u, ~0u, ~0u, ~0u};
-      reach_apply(reach_read(s_reach, p0, 3, laneoff), st);
-#pragma unroll
-      for (uint32_t k = 0; k < 4; k++) reach_apply(reach_read(s_reach, p1, k, laneoff), st);
-#pragma unroll
-      for (int j = 0; j < kFBlocks; j++) {
-        const uint32_t wd[4] = {cur[j].x, cur[j].y, cur[j].z, cur[j].w};
-        uint32_t acc = ~0u;
-        // table reads in groups of kFReadAhead ahead of the chain (independent of
-        // the state): fewer live VGPRs than a whole block's 16 rows
-#pragma unroll
-        for (uint32_t g = 0; g < 16; g += kFReadAhead) {
-          uint4 m[kFReadAhead];
-#pragma unroll
-          for (uint32_t q = 0; q < kFReadAhead; q++)
-            m[q] = reach_read(s_reach, wd[(g + q) >> 2], (g + q) & 3, laneoff);
-#pragma unroll
-          for (uint32_t q = 0; q < kFReadAhead; q++) {
-            const uint32_t k = g + q;
-            reach_apply(m[q], st);
-            if (k % 3 == 2 || k == 15) acc &= st[0] & st[1] & st[2] & st[3];
-            if (k % 4 == 3) nl += __popc(~st[3] & kNlBits);
-          }
-        }
-        flagged |= uint32_t((acc | ~kFireBits) != ~0u) << j;
       }
     } else {
 #pragma unroll
@@ -755,34 +697,15 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
     if ((l & 15) == 15) reinterpret_cast<uint16_t*>(NL + nl_slots)[l >> 4] = uint16_t(nl);
     if (++nl_slots == kFNlTiles) flush_nl(tt);
     }
-#if TSG_K1_GROUPQ
     if (grp_n == 0) grp_t0 = tt;
     fl_acc |= flagged << (4 * grp_n);
     grp_n++;
-#else
-    // the flagged block columns, compacted (record = arena byte / 16)
-    const uint32_t rec0 = uint32_t(tt * (kFTile / 16)) + lane * kFBlocks;
-#pragma unroll
-    for (int j = 0; j < kFBlocks; j++) {
-      const bool fj = (flagged >> j) & 1u;
-      const uint64_t m = __ballot(fj);
-      if (m) {
-        if (qn + 64 > kFQueue) flush();  // wave-uniform; rare (> 128 records since the last flush)
-        const uint32_t below =
-            __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
-        if (fj) Q[qn + below] = rec0 + uint32_t(j);
-        qn += uint32_t(__popcll(m));
-      }
-    }
-#endif
   };
   // A flush's atomicAdd returns the records' base: waiting for it waits for every
   // older vector-memory op too, so it goes before the next tile's loads are issued
   // (then it only waits for the loads the coming tile needs at once anyway).
   auto flush_due = [&]() {
-#if TSG_K1_GROUPQ
     if (grp_n == kFGroup) compact();
-#endif
     if (qn >= kFFlushAt) flush();
   };
   using Full = std::false_type;
@@ -791,36 +714,19 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
     const uint64_t t_end = k_end;
     const uint64_t t_full = t_end < P.n_bytes / kFTile ? t_end : P.n_bytes / kFTile;
     uint64_t t = t_begin;
-    if (t < t_full) load_tile(bufA, t);
-    if constexpr (kOr) {
-      while (t < t_full) {
-        flush_due();
-        tile(bufA, t, Full(), lane_ptr(t + 1 < t_full ? t + 1 : t));  // past the range: a harmless reload
-        t++;
-      }
-    } else {
-      // two register buffers alternate roles (no copies): tile t in A while t + 1 loads into B
-      while (t < t_full) {
-        flush_due();
-        load_tile(bufB, t + 1 < t_full ? t + 1 : t);  // past the range: a harmless reload
-        tile(bufA, t, Full());
-        t++;
-        if (t >= t_full) break;
-        flush_due();
-        load_tile(bufA, t + 1 < t_full ? t + 1 : t);
-        tile(bufB, t, Full());
-        t++;
-      }
+    if (t < t_full) load_tile(buf, t);
+    while (t < t_full) {
+      flush_due();
+      tile(buf, t, Full(), lane_ptr(t + 1 < t_full ? t + 1 : t));  // past the range: a harmless reload
+      t++;
     }
     if (t < t_end) {  // the partial last tile
       flush_due();
-      load_tile(bufA, t);
-      tile(bufA, t, std::true_type());
+      load_tile(buf, t);
+      tile(buf, t, std::true_type());
       t++;
     }
-#if TSG_K1_GROUPQ
     if (grp_n) compact();
-#endif
     if (qn) flush();
     if (nl_slots) flush_nl(t - 1);
     return;
@@ -834,13 +740,11 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
   // assume consecutive tiles, so they go out first (a store and maybe a
   // flush's wait per run boundary, none inside a run).
   auto run_boundary = [&]() {
-#if TSG_K1_GROUPQ
     if (grp_n) compact();
-#endif
     if (nl_slots) flush_nl(t_prev);
   };
-  // tile t from `cur` while the next kept tile loads into `nxt`
-  auto step = [&](uint4* cur, uint4* nxt) {
+  // tile t from `cur`, refilled in place with the next kept tile
+  auto step = [&](uint4* cur) {
     if (nr_cur) run_boundary();
     flush_due();
     uint64_t tn = t;
@@ -852,40 +756,24 @@ __global__ __launch_bounds__(kScanThreads, 8) void filter_kernel(FilterParams P)
     // earlier, with this tile's own prefetch, the pair would stay live across
     // a whole tile body -- two more VGPRs spilled at the kernel's 64.
     if (nr_cur) load_pre(t);
-    if constexpr (kOr) {
-      tile(cur, t, Full(), lane_ptr(k + 1 < k_full ? tn : t));  // (nxt == cur: refilled in place)
-    } else {
-      load_tile(nxt, k + 1 < k_full ? tn : t);  // past the range: a harmless reload
-      tile(cur, t, Full());
-    }
+    tile(cur, t, Full(), lane_ptr(k + 1 < k_full ? tn : t));  // past the range: a harmless reload
     t_prev = t;
     t = tn;
     nr_cur = nr_n;
     k++;
   };
-  // two register buffers alternate roles (no copies): tile t in A while the next loads into B
-  if (k < k_full) load_tile(bufA, t);
-  if constexpr (kOr) {
-    while (k < k_full) step(bufA, bufA);
-  } else {
-    while (k < k_full) {
-      step(bufA, bufB);
-      if (k >= k_full) break;
-      step(bufB, bufA);
-    }
-  }
+  if (k < k_full) load_tile(buf, t);
+  while (k < k_full) step(buf);
   if (k < k_end) {  // the partial last tile
     if (nr_cur) run_boundary();
     flush_due();
     if (nr_cur) load_pre(t);
-    load_tile(bufA, t);
-    tile(bufA, t, std::true_type());
+    load_tile(buf, t);
+    tile(buf, t, std::true_type());
     t_prev = t;
     k++;
   }
-#if TSG_K1_GROUPQ
   if (grp_n) compact();
-#endif
   if (qn) flush();
   if (nl_slots) flush_nl(t_prev);
   if (RUNS && lane == 0 && k_begin < k_end) atomicMax(&P.run_info[kSkWaveRuns], runs_walked);
@@ -1158,9 +1046,6 @@ struct ConfirmParams {
   uint32_t t_hkeys, t_hitems, hash_bits, hash_buckets;
   // global-table variant: the n_classes byte classes (8 u32 each) staged in LDS (0: read from tabs)
   uint32_t n_classes_lds;
-  // TSG_K2_PACK experiment: each record's 48-B window packed sequentially (64-B
-  // stride) by pack_kernel, read linearly instead of gathered from the arena
-  const uint8_t* wins;
 };
 
 // Shift-and NFA over arena bytes [fs + start, fs + len), read 16 B at a time
@@ -1302,26 +1187,13 @@ __device__ int64_t count_nl_abs(const uint8_t* arena, const uint16_t* nl, uint64
 #ifndef TSG_C_Q2
 #define TSG_C_Q2 96
 #endif
-#ifndef TSG_C_FSE
-#define TSG_C_FSE 0
-#endif
-#ifndef TSG_C_PREFETCH
-#define TSG_C_PREFETCH 1
-#endif
-#ifndef TSG_C_REACH_COPIES
-#define TSG_C_REACH_COPIES 1
-#endif
-constexpr bool kCFse = TSG_C_FSE;     // cache each block's file in LDS in phase A (-0.2 ms at equal occupancy; costs 20 B/lane)
-// Copies of the 4-KiB reach table in the confirm kernel's LDS, the copy chosen
-// by lane & (copies - 1).  Phase A's row reads conflict (SQ_LDS_BANK_CONFLICT is
-// 29 % of K2's LDS cycles, profiles/r04f), but four copies (+12 KiB per
-// workgroup) measured K2 2.42 -> 3.42 ms (profiles/r04y): one copy stays.
-constexpr uint32_t kCReachCopies = TSG_C_REACH_COPIES;
-static_assert((kCReachCopies & (kCReachCopies - 1)) == 0, "a power of two");
+// One copy of the 4-KiB reach table in the confirm kernel's LDS.  Phase A's row
+// reads conflict (SQ_LDS_BANK_CONFLICT is 29 % of K2's LDS cycles, profiles/r04f),
+// but four copies (+12 KiB per workgroup) measured K2 2.42 -> 3.42 ms (profiles/r04y).
 constexpr uint32_t kCQ1 = TSG_C_Q1;  // fires (overflow: handled in place)
 constexpr uint32_t kCQ2 = TSG_C_Q2;  // candidate items (overflow: checked in place)
 constexpr size_t ConfirmFixedLds(int t) {  // LDS of a t-thread workgroup besides the staged tables
-  return 4096 * kCReachCopies + size_t(t) * (kCWin + 8 + (kCFse ? 20 : 0)) + size_t(t / 64) * (kCQ1 + kCQ2) * 4 +
+  return 4096 + size_t(t) * (kCWin + 8) + size_t(t / 64) * (kCQ1 + kCQ2) * 4 +
          size_t(t / 64) * kCWaveHits * 12 + size_t(t / 64) * 16;
 }
 
@@ -1336,18 +1208,16 @@ __global__ __launch_bounds__(ConfirmThreads<kLdsTabs>(), TSG_C_MINW) void confir
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   constexpr int kCThreads = ConfirmThreads<kLdsTabs>();  // shadows the file-scope constant
   constexpr uint32_t kWaves = kCThreads / 64;
-  uint8_t* s_reach = smem;                                        // 4 KiB x kCReachCopies (row b: copies x 16 B)
-  uint8_t* s_win = smem + 4096 * kCReachCopies;                   // kCThreads x 64 B
+  uint8_t* s_reach = smem;                                        // 4 KiB (row b: 16 B)
+  uint8_t* s_win = smem + 4096;                                   // kCThreads x kCWin B
   uint64_t* s_base = reinterpret_cast<uint64_t*>(s_win + kCThreads * kCWin);    // kCThreads
-  uint64_t* s_fse = s_base + kCThreads;                                         // kCThreads x 2: block's file [fs, fe)
-  uint32_t* s_file = reinterpret_cast<uint32_t*>(s_fse + (kCFse ? 2 * kCThreads : 0));  // kCThreads: block's file
-  uint32_t* s_q1 = s_file + (kCFse ? kCThreads : 0);                            // kWaves x kCQ1
+  uint32_t* s_q1 = reinterpret_cast<uint32_t*>(s_base + kCThreads);             // kWaves x kCQ1
   uint32_t* s_q2 = s_q1 + kWaves * kCQ1;                                        // kWaves x kCQ2
   uint32_t* s_hbuf = s_q2 + kWaves * kCQ2;                                      // kWaves x kCWaveHits x 3
   uint32_t* s_cnt = s_hbuf + kWaves * kCWaveHits * 3;                           // kWaves x 4
   uint8_t* s_tabs = reinterpret_cast<uint8_t*>(s_cnt + kWaves * 4);
   const int tid = threadIdx.x;
-  load_reach_lds(s_reach, P.reach, kCReachCopies, tid, blockDim.x);
+  load_reach_lds(s_reach, P.reach, tid, blockDim.x);
   if (kLdsTabs) {
     const uint4* t = reinterpret_cast<const uint4*>(P.tabs);
     uint4* d = reinterpret_cast<uint4*>(s_tabs);
@@ -1370,8 +1240,6 @@ __global__ __launch_bounds__(ConfirmThreads<kLdsTabs>(), TSG_C_MINW) void confir
   }
   uint8_t* wwin = s_win + wave * 64 * kCWin;  // the wave's 64 windows
   uint64_t* wbase = s_base + wave * 64;      // block base per lane
-  uint64_t* wfse = s_fse + wave * 128;       // the file holding the block's first byte, per lane
-  uint32_t* wfile = s_file + wave * 64;
   uint32_t* q1 = s_q1 + wave * kCQ1;
   uint32_t* q2 = s_q2 + wave * kCQ2;
   uint32_t* hbuf = s_hbuf + wave * kCWaveHits * 3;
@@ -1392,25 +1260,12 @@ __global__ __launch_bounds__(ConfirmThreads<kLdsTabs>(), TSG_C_MINW) void confir
     // 0.35 ms more -- the sets reject half the literal hits at a lower cost).
     const uint64_t cw0 = base >= 16 ? base - 16 : 0;  // the lane window [cw0, cw0 + kCWin)
     const uint8_t* cwin = wwin + l * kCWin;
-#ifndef TSG_C_PRE
-#define TSG_C_PRE 0
-#endif
-    // global tables: the first positions' class ids loaded up front (independent
-    // loads instead of one dependent round trip per position)
-    constexpr uint32_t kPre = kLdsTabs ? 0 : TSG_C_PRE;
-    uint32_t pre[kPre > 0 ? kPre : 1];
-#pragma unroll
-    for (uint32_t q = 0; q < kPre; q++) pre[q] = q < it.n ? item_cls[it.cls_off + q] : 0u;
     auto sets_ok = [&](uint32_t q0, uint32_t q1) {
       for (uint32_t q = q0; q < q1; q++) {
         if (q >= core_lo && q < it.back) continue;
         const uint64_t pos = uint64_t(start) + q;
         const uint32_t bt = pos - cw0 < uint64_t(kCWin) ? uint32_t(cwin[pos - cw0]) : uint32_t(P.arena[pos]);
-        uint32_t c = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < kPre; k++)
-          if (q == k) c = pre[k];
-        if (q >= kPre) c = item_cls[it.cls_off + q];
+        const uint32_t c = item_cls[it.cls_off + q];
         if (!((classes[c * 8 + (bt >> 5)] >> (bt & 31)) & 1u)) return false;
       }
       return true;
@@ -1419,22 +1274,12 @@ __global__ __launch_bounds__(ConfirmThreads<kLdsTabs>(), TSG_C_MINW) void confir
     if (!sets_ok(0, check_to)) return;
     if (P.diag & 16) return;
     const uint64_t s0 = uint64_t(start);
-    uint32_t f = 0;
-    uint64_t fs = 1, fe = 0;
-    if (kCFse) {  // phase A's attribution of the block start, when the item lies in that file
-      f = wfile[l];
-      fs = wfse[2 * l];
-      fe = wfse[2 * l + 1];
-    }
-    if (s0 < fs || s0 >= fe) {
-      f = P.chunk_file[s0 / kChunk];
-      fs = P.off[f];
+    uint32_t f = P.chunk_file[s0 / kChunk];
+    uint64_t fs = P.off[f], fe = P.off[f + 1];
+    while (s0 >= fe) {  // s0 < n_bytes = off[n_files]
+      f++;
+      fs = fe;
       fe = P.off[f + 1];
-      while (s0 >= fe) {  // s0 < n_bytes = off[n_files]
-        f++;
-        fs = fe;
-        fe = P.off[f + 1];
-      }
     }
     if (s0 < fs || s0 + it.n > fe) return;  // crosses a file boundary
     if (P.diag & 8) return;
@@ -1559,16 +1404,10 @@ __global__ __launch_bounds__(ConfirmThreads<kLdsTabs>(), TSG_C_MINW) void confir
   };
   const uint32_t stride = gridDim.x * blockDim.x;
   // The records are loaded two batches ahead and their window bytes one batch
-  // ahead (TSG_C_PREFETCH): the gather of the next blocks' bytes is in flight
-  // while this batch's phases run, instead of one dependent global round trip
-  // (record -> window bytes) at the top of every batch.
-  auto load_win = [&](uint32_t r, uint32_t rec, bool valid, uint4* dst) {
-    if (P.wins) {  // TSG_K2_PACK: the window packed at record r
-#pragma unroll
-      for (int q = 0; q < kCWin / 16; q++)
-        dst[q] = valid ? load16(P.wins + uint64_t(r) * 64 + 16 * q) : make_uint4(0, 0, 0, 0);
-      return;
-    }
+  // ahead: the gather of the next blocks' bytes is in flight while this batch's
+  // phases run, instead of one dependent global round trip (record -> window
+  // bytes) at the top of every batch.
+  auto load_win = [&](uint32_t rec, bool valid, uint4* dst) {
     const uint64_t base = uint64_t(rec) * 16;
     const uint64_t w0 = base >= 16 ? base - 16 : 0;
 #pragma unroll
@@ -1577,26 +1416,19 @@ __global__ __launch_bounds__(ConfirmThreads<kLdsTabs>(), TSG_C_MINW) void confir
   };
   const uint32_t r_first = blockIdx.x * blockDim.x + wave * 64 + lane;
   uint32_t rec_next = r_first < n_recs ? P.recs[r_first] : 0u;
-#if TSG_C_PREFETCH
   uint4 dwn[kCWin / 16];
-  load_win(r_first, rec_next, r_first < n_recs, dwn);
+  load_win(rec_next, r_first < n_recs, dwn);
   uint32_t rec_nn = r_first + stride < n_recs ? P.recs[r_first + stride] : 0u;
-#endif
   for (uint32_t r0 = blockIdx.x * blockDim.x + wave * 64; r0 < n_recs; r0 += stride) {
     // ---- A: one block per lane
     const uint32_t r = r0 + lane;
     const uint32_t rec = rec_next;
     uint4 dw[kCWin / 16];
-#if TSG_C_PREFETCH
 #pragma unroll
     for (int q = 0; q < kCWin / 16; q++) dw[q] = dwn[q];
     rec_next = rec_nn;
-    load_win(r + stride, rec_next, r + stride < n_recs, dwn);
+    load_win(rec_next, r + stride < n_recs, dwn);
     rec_nn = r + 2 * stride < n_recs ? P.recs[r + 2 * stride] : 0u;
-#else
-    rec_next = r + stride < n_recs ? P.recs[r + stride] : 0u;
-    load_win(r, rec, r < n_recs, dw);
-#endif
     uint32_t fire_e[4], n_fire = 0;
     if (r < n_recs) {
       const uint64_t base = uint64_t(rec) * 16;
@@ -1605,24 +1437,11 @@ __global__ __launch_bounds__(ConfirmThreads<kLdsTabs>(), TSG_C_MINW) void confir
 #pragma unroll
       for (int q = 0; q < kCWin / 16; q++) wl[q] = dw[q];
       wbase[lane] = base;
-      if (kCFse) {  // the file holding the block's first byte (check_item's attribution, usually)
-        uint32_t f = P.chunk_file[base / kChunk];
-        uint64_t fs = P.off[f], fe = P.off[f + 1];
-        while (base >= fe) {
-          f++;
-          fs = fe;
-          fe = P.off[f + 1];
-        }
-        wfile[lane] = f;
-        wfse[2 * lane] = fs;
-        wfse[2 * lane + 1] = fe;
-      }
       const uint4 pv = base >= 16 ? d0 : make_uint4(0, 0, 0, 0);
       const uint4 v = base >= 16 ? d1 : d0;
       uint32_t st[kFWords] = {~0u, ~0u, ~0u, ~0u};
-      const uint32_t rcopy = lane & (kCReachCopies - 1);
-      auto rd1 = [&](uint32_t w, uint32_t k) {  // entry b, copy c at 16 * (b * copies + c)
-        return *reinterpret_cast<const uint4*>(s_reach + ((((w >> (8 * k)) & 0xFFu) * kCReachCopies + rcopy) << 4));
+      auto rd1 = [&](uint32_t w, uint32_t k) {  // entry b at 16 * b
+        return *reinterpret_cast<const uint4*>(s_reach + (((w >> (8 * k)) & 0xFFu) << 4));
       };
 #pragma unroll
       for (uint32_t k = 11; k < 16; k++) reach_apply(rd1(word_of(pv, k >> 2), k & 3), st);
@@ -1682,26 +1501,6 @@ __global__ __launch_bounds__(ConfirmThreads<kLdsTabs>(), TSG_C_MINW) void confir
   if (lane == 0 && n_anchor) atomicAdd(&P.counters[kCtAnchorHits], n_anchor);  // anchor-item matches (stats)
 }
 
-// TSG_K2_PACK experiment: the 48-B window of every flagged
-// block record written to a sequential buffer (64-B stride), so the confirm
-// kernel's phase A reads records linearly instead of gathering 128-B lines
-// the filter kernel streamed long before.  Measures what the confirm kernel
-// would gain if K1 streamed the windows itself.
-__global__ __launch_bounds__(256) void pack_windows_kernel(const uint8_t* __restrict__ arena, uint64_t n_bytes,
-                                                           const uint32_t* __restrict__ recs, uint32_t rec_cap,
-                                                           const uint32_t* __restrict__ counters,
-                                                           uint8_t* __restrict__ wins) {
-  const uint32_t n_recs = counters[kCtRecs] < rec_cap ? counters[kCtRecs] : rec_cap;
-  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n_recs; r += gridDim.x * blockDim.x) {
-    const uint64_t base = uint64_t(recs[r]) * 16;
-    const uint64_t w0 = base >= 16 ? base - 16 : 0;
-    uint4* d = reinterpret_cast<uint4*>(wins + uint64_t(r) * 64);
-#pragma unroll
-    for (int q = 0; q < kCWin / 16; q++)
-      d[q] = w0 + 16 * q + 16 <= n_bytes + 64 ? load16(arena + w0 + 16 * q) : make_uint4(0, 0, 0, 0);
-  }
-}
-
 // Fold kernel.  Items whose bytes hold a fold rune are invisible to the byte-
 // exact filter; for each fold site and each item, every item start that puts
 // the rune inside the item is tried with a fold-tolerant match: a position
@@ -1738,7 +1537,6 @@ struct FoldParams {
   // tasks with q >= kFoldIdxQ or a single position stay in the pair lists.
   const uint32_t* idx_off;
   const uint32_t* idx_items;
-  uint32_t use_idx;
   uint32_t n_cap_k_idx, n_cap_s_idx;  // leading capable pairs covered by the index
   const FoldSite* folds;
   uint32_t fold_cap;
@@ -1748,9 +1546,6 @@ struct FoldParams {
   // global-table variant (large rule sets): the item records and the byte
   // classes staged in LDS when they fit (n_classes classes of 8 u32)
   uint32_t stage_items, n_classes;
-  // global tables: test position 0 against the item's first-byte set (one more
-  // dependent global load per start; without it the position loop rejects)
-  uint32_t check_first;
   uint32_t diag;  // TSG_DIAG_FOLD (timing only, findings wrong): 1 skips sites with another rune before, 2 the others
 };
 
@@ -1821,7 +1616,7 @@ void fold_kernel(FoldParams P) {
     const uint32_t* first = firsts + 8ull * ix;
     const uint64_t st = S.x - back;
     const uint32_t b0 = S.wb[st - S.w0];
-    if ((kLdsTabs || P.check_first) && !((first[b0 >> 5] >> (b0 & 31)) & 1u)) return;  // position 0 fails (superset test)
+    if (!((first[b0 >> 5] >> (b0 & 31)) & 1u)) return;  // position 0 fails (superset test)
     uint64_t p = st, lit_bytes_end = 0;
     bool ok = true, covered = false;
     // the first positions' class ids up front: independent loads instead of
@@ -1909,37 +1704,34 @@ void fold_kernel(FoldParams P) {
         } else if (!skip) {
           const FoldPair* pairs = P.pairs + P.n_pairs_k + P.n_pairs_s + (kay ? 0 : P.n_cap_k);
           const uint32_t n_pairs = kay ? P.n_cap_k : P.n_cap_s;
-          uint32_t total = 0;  // indexed capable tasks
           uint32_t* ex = s_idx[wave][0];
           uint32_t* lw = s_idx[wave][1];
-          if (P.use_idx) {
-            // indexed capable tasks: lane q looks up its list by the key byte, a
-            // wave prefix sum spreads the lists' tasks over the lanes
-            const uint32_t q = lane;
-            const uint32_t rl = kay ? 3u : 2u;
-            uint32_t key = 256;
-            if (q == 0) key = S.x + rl < S.w1 ? wb[S.x + rl - S.w0] : 256u;
-            else if (S.x >= S.w0 + q) key = wb[S.x - q - S.w0];
-            uint32_t lo = 0, cnt = 0;
-            if (key < 256) {
-              const uint32_t* o = P.idx_off + (size_t(kay ? 0 : 1) * kFoldIdxQ + q) * 257 + key;
-              lo = o[0];
-              cnt = o[1] - lo;
-            }
-            uint32_t incl = cnt;  // inclusive prefix over the lanes
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-              const uint32_t v = __shfl_up(incl, d);
-              if (lane >= uint32_t(d)) incl += v;
-            }
-            total = __shfl(incl, 63);
-            wave_sync();
-            ex[lane] = incl - cnt;
-            lw[lane] = lo;
-            wave_sync();
+          // indexed capable tasks: lane q looks up its list by the key byte, a
+          // wave prefix sum spreads the lists' tasks over the lanes
+          const uint32_t q = lane;
+          const uint32_t rl = kay ? 3u : 2u;
+          uint32_t key = 256;
+          if (q == 0) key = S.x + rl < S.w1 ? wb[S.x + rl - S.w0] : 256u;
+          else if (S.x >= S.w0 + q) key = wb[S.x - q - S.w0];
+          uint32_t lo = 0, cnt = 0;
+          if (key < 256) {
+            const uint32_t* o = P.idx_off + (size_t(kay ? 0 : 1) * kFoldIdxQ + q) * 257 + key;
+            lo = o[0];
+            cnt = o[1] - lo;
           }
+          uint32_t incl = cnt;  // inclusive prefix over the lanes
+#pragma unroll
+          for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t v = __shfl_up(incl, d);
+            if (lane >= uint32_t(d)) incl += v;
+          }
+          const uint32_t total = __builtin_amdgcn_readlane(incl, 63);  // (the wave is whole here)
+          wave_sync();
+          ex[lane] = incl - cnt;
+          lw[lane] = lo;
+          wave_sync();
           // tasks outside the index (q >= kFoldIdxQ or single-position items) follow in the pair list
-          const uint32_t t0 = P.use_idx ? (kay ? P.n_cap_k_idx : P.n_cap_s_idx) : 0u;
+          const uint32_t t0 = kay ? P.n_cap_k_idx : P.n_cap_s_idx;
           if (total + (n_pairs > t0 ? n_pairs - t0 : 0u) > uint32_t(TSG_FOLD_COOP_TASKS)) {
             // a heavy site (many items take the rune's byte context): the workgroup's too
             coop = 1u | (kay ? 2u : 0u) | 4u;
@@ -1998,7 +1790,7 @@ void fold_kernel(FoldParams P) {
         }
         const FoldPair* pairs = P.pairs + P.n_pairs_k + P.n_pairs_s + (kay ? 0 : P.n_cap_k);
         const uint32_t n_pairs = kay ? P.n_cap_k : P.n_cap_s;
-        const uint32_t t0 = P.use_idx ? (kay ? P.n_cap_k_idx : P.n_cap_s_idx) : 0u;
+        const uint32_t t0 = kay ? P.n_cap_k_idx : P.n_cap_s_idx;
         for (uint32_t t = t0 + threadIdx.x; t < n_pairs; t += blockDim.x) {
           const FoldPair fp = pairs[t];
           for (uint32_t back = fp.lo; back <= fp.hi; back++) try_start(S, fp.item, back);
@@ -2732,14 +2524,6 @@ GpuEngine::GpuEngine(const CompiledRules& cr, int device) : device_(device) {
   {  // the K0 phase and the read-back of pipelined scans run beside the engine stream
     if (const char* e = std::getenv("TSG_OVERLAP_K0")) overlap_k0_ = std::atoi(e) != 0;
     if (const char* e = std::getenv("TSG_READBACK_STREAM")) readback_stream_ = std::atoi(e) != 0;
-    if (const char* e = std::getenv("TSG_K1_FORM")) {  // K1's window evaluation: or | shiftor
-      if (std::strcmp(e, "or") == 0) k1_or_ = true;
-      else if (std::strcmp(e, "shiftor") == 0) k1_or_ = false;
-      else {
-        err_ = std::string("TSG_K1_FORM=") + e + " (or, shiftor are the forms)";
-        return;
-      }
-    }
     int lo = 0, hi = 0;
     if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) lo = hi = 0;
     bool ok = hipStreamCreateWithPriority(&aux_stream_, hipStreamNonBlocking, hi) == hipSuccess &&
@@ -2961,8 +2745,6 @@ GpuEngine::GpuEngine(const CompiledRules& cr, int device) : device_(device) {
           return;
         d_fold_idx_off_ = d_off;
         d_fold_idx_items_ = d_items;
-        const char* fi = std::getenv("TSG_FOLD_INDEX");  // 0: pair lists only (A/B)
-        fold_idx_ = !fi || std::atoi(fi) != 0;
       }
       n_fold_pairs_k_ = uint32_t(pk.size());
       n_fold_pairs_s_ = uint32_t(ps.size());
@@ -3052,7 +2834,6 @@ GpuEngine::GpuEngine(const CompiledRules& cr, int device) : device_(device) {
       c_stage_classes_ = !lds_tabs_ && c_lds_bytes_ + 32 * size_t(n_fclasses_) <= 40 * 1024 && (!sc || std::atoi(sc) != 0);
       if (c_stage_classes_) c_lds_bytes_ += 32 * size_t(n_fclasses_);
     }
-    if (const char* e = std::getenv("TSG_CONFIRM_LDS_PAD")) c_lds_bytes_ += size_t(std::strtoull(e, nullptr, 10));  // occupancy experiments
     if (std::getenv("TSG_ENGINE_DEBUG"))
       std::fprintf(stderr, "confirm LDS: fixed %zu + tables %u (fold prefix %u) = %zu B, limit %zu, %s tables, %d threads; "
                    "fold kernel static LDS %zu B\n",
@@ -3067,20 +2848,15 @@ GpuEngine::GpuEngine(const CompiledRules& cr, int device) : device_(device) {
     fold_stage_bytes_ = 16 * size_t(n_fitems_) + 32 * size_t(n_fclasses_);
     const char* fse = std::getenv("TSG_FOLD_STAGE");
     fold_stage_ = !lds_tabs_ && fold_stage_bytes_ <= 48 * 1024 && (!fse || std::atoi(fse) != 0);
-    const char* ffe = std::getenv("TSG_FOLD_FIRST");
-    fold_check_first_ = !ffe || std::atoi(ffe) != 0;  // r05g: without it 3.0-3.7 ms instead of 1.6-2.1
     // LDS-table fold kernel's grid: every workgroup stages the tables first (TSG_FOLD_GRID)
     if (const char* fg = std::getenv("TSG_FOLD_GRID")) fold_grid_ = uint32_t(std::max(1, std::atoi(fg)));
-    const char* fwe = std::getenv("TSG_FOLD_WAVES");
-    fold_wide_ = fold_stage_ && (!fwe || std::atoi(fwe) == 16);
     if (std::getenv("TSG_ENGINE_DEBUG"))
-      std::fprintf(stderr, "fold: %u items, %u classes, staged %s (%zu B), first-byte test %s, %d waves per workgroup\n",
+      std::fprintf(stderr, "fold: %u items, %u classes, staged %s (%zu B), %d waves per workgroup\n",
                    n_fitems_, n_fclasses_,
                    lds_tabs_ ? "(LDS tables)" : fold_stage_ ? "yes" : "no", fold_stage_bytes_,
-                   lds_tabs_ || fold_check_first_ ? "on" : "off", fold_wide_ ? 16 : kFoldWaves);
+                   fold_stage_ ? 16 : kFoldWaves);
     if (fold_stage_)
-      hipFuncSetAttribute(fold_wide_ ? reinterpret_cast<const void*>(&fold_kernel<false, 16>)
-                                     : reinterpret_cast<const void*>(&fold_kernel<false>),
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&fold_kernel<false, 16>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, int(fold_stage_bytes_));
   }
 }
@@ -3102,7 +2878,7 @@ GpuEngine::~GpuEngine() {
   void* ps[] = {d_item_diag_, d_fold_pairs_, d_kwfold_pairs_, d_fold_idx_off_, d_fold_idx_items_, d_fold_first_, d_reach_, d_core_, d_group_items_, d_bucket_groups_, d_ftabs_, d_folds_, d_recs_, d_anchors_,
                 d_rules_, d_rule_kw_, d_nfa_, d_fullscan_rules_, d_nl_,
                 d_hits_, d_fs_pairs_, d_fs_tasks_, d_fs_wave_, d_xlen_, d_xoff_, d_xscan_,
-                d_xf_, d_gfiles_, d_gdst_, d_gbuf_, d_wins_};
+                d_xf_, d_gfiles_, d_gdst_, d_gbuf_};
   for (void* p : ps)
     if (p) hipFree(p);
   for (WorkSet& W : sets_) {
@@ -4144,7 +3920,6 @@ struct GpuEngine::KernelArgs {
     cp.hash_bits = e.hash_bits_;
     cp.hash_buckets = e.hash_buckets_;
     cp.n_classes_lds = e.c_stage_classes_ ? e.n_fclasses_ : 0u;
-    cp.wins = nullptr;
     return cp;
   }
   static FoldParams Fold(const GpuEngine& e, const WorkSet& W, const uint8_t* d_arena, const uint64_t* d_offsets) {
@@ -4160,7 +3935,6 @@ struct GpuEngine::KernelArgs {
     fo.n_items = e.n_fitems_;
     fo.stage_items = e.fold_stage_ ? 1u : 0u;
     fo.n_classes = e.n_fclasses_;
-    fo.check_first = e.fold_check_first_ ? 1u : 0u;
     static const uint32_t fold_diag =
         std::getenv("TSG_DIAG_FOLD") ? uint32_t(std::atoi(std::getenv("TSG_DIAG_FOLD"))) : 0u;
     fo.diag = fold_diag;
@@ -4174,7 +3948,6 @@ struct GpuEngine::KernelArgs {
     fo.fold_cap = e.caps_.fold;
     fo.idx_off = static_cast<const uint32_t*>(e.d_fold_idx_off_);
     fo.idx_items = static_cast<const uint32_t*>(e.d_fold_idx_items_);
-    fo.use_idx = e.fold_idx_ ? 1u : 0u;
     fo.n_cap_k_idx = e.n_fold_cap_k_idx_;
     fo.n_cap_s_idx = e.n_fold_cap_s_idx_;
     fo.hits = static_cast<uint32_t*>(e.d_hits_);
@@ -4272,7 +4045,7 @@ struct GpuEngine::KernelArgs {
 //     drained (and hipFree waits for the device); both sets are sized together
 //     (EnsureSets), under the lock the caller of Enqueue / Run holds.
 //  5. Off-stream readers.  The buffers that stay single (d_nl_, d_recs_,
-//     d_hits_, d_folds_, d_wins_, the full-scan lists) are touched by kernels on
+//     d_hits_, d_folds_, the full-scan lists) are touched by kernels on
 //     stream_ only: fetch.hip and fetch_windows.hip run on stream_ and read the
 //     set's candidates and counter besides the arena; materialize.hip and
 //     classify.hip read the arena and the offsets alone.
@@ -4346,27 +4119,12 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
       uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((f_tiles + kScanWaves - 1) / kScanWaves, 256 * kFWgPerCu)));
   if (k1_grid_cap_) f_grid = std::min(f_grid, k1_grid_cap_);
   HIP_OK(hipEventRecord(E.ev[kEvK1], stream_));
-  if (k1_or_) {
-    if (skip) filter_kernel<true, true><<<f_grid, kScanThreads, 0, stream_>>>(fp);
-    else filter_kernel<false, true><<<f_grid, kScanThreads, 0, stream_>>>(fp);
-  } else {
-    if (skip) filter_kernel<true, false><<<f_grid, kScanThreads, 0, stream_>>>(fp);
-    else filter_kernel<false, false><<<f_grid, kScanThreads, 0, stream_>>>(fp);
-  }
+  if (skip) filter_kernel<true><<<f_grid, kScanThreads, 0, stream_>>>(fp);
+  else filter_kernel<false><<<f_grid, kScanThreads, 0, stream_>>>(fp);
   HIP_OK(hipGetLastError());
   HIP_OK(hipEventRecord(E.ev[kEvK2], stream_));
   // K2: confirm + verify
-  ConfirmParams cp = KernelArgs::Confirm(*this, W, d_arena, n_bytes, d_offsets);
-  static const bool k2_pack = std::getenv("TSG_K2_PACK") && std::atoi(std::getenv("TSG_K2_PACK")) != 0;
-  if (k2_pack && diag_mode_ == 0) {  // (experiment) the windows packed between K1 and K2, outside K2's events
-    if (!Ensure(&d_wins_, &cap_wins_, size_t(caps_.rec) * 64)) return false;
-    pack_windows_kernel<<<8192, 256, 0, stream_>>>(d_arena, n_bytes, static_cast<const uint32_t*>(d_recs_), caps_.rec,
-                                                   W.counters, static_cast<uint8_t*>(d_wins_));
-    HIP_OK(hipGetLastError());
-    // re-recorded: K1 + pack count as the scan phase, K2 alone as confirm
-    HIP_OK(hipEventRecord(E.ev[kEvK2], stream_));
-    cp.wins = static_cast<const uint8_t*>(d_wins_);
-  }
+  const ConfirmParams cp = KernelArgs::Confirm(*this, W, d_arena, n_bytes, d_offsets);
   if (diag_mode_ == 0) {
     if (lds_tabs_)
       confirm_kernel<true><<<2048 * 256 / kCThreads, kCThreads, c_lds_bytes_, stream_>>>(cp);
@@ -4382,10 +4140,10 @@ bool GpuEngine::EnqueuePhase(const uint8_t* d_arena, uint64_t n_bytes, const uin
   if (diag_mode_ == 0) {
     if (lds_tabs_)
       fold_kernel<true><<<fold_grid_, 64 * kFoldWaves, ftabs_fold_bytes_ + 32 * n_fitems_, stream_>>>(fo);
-    else if (fold_wide_)
+    else if (fold_stage_)
       fold_kernel<false, 16><<<2048, 64 * 16, fold_stage_bytes_, stream_>>>(fo);
     else
-      fold_kernel<false><<<2048, 64 * kFoldWaves, fold_stage_ ? fold_stage_bytes_ : 0, stream_>>>(fo);
+      fold_kernel<false><<<2048, 64 * kFoldWaves, 0, stream_>>>(fo);
   }
   HIP_OK(hipGetLastError());
   if (diag_mode_ == 0 && kw_fold_ && n_kwf_ci_ + n_kwf_ck_ > 0) {

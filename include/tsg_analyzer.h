@@ -353,6 +353,63 @@ int tsg_tar_index_walk_stats(const tsg_tar_index* ix, tsg_tar_walk_stats* out);
  * options).  -1: NULL argument or an unknown struct_size. */
 int tsg_tar_index_skip_stats(const tsg_tar_index* ix, tsg_tar_skip_stats* out);
 
+/* All layers of an image resident in HBM, indexed by one call.  The
+ * layers may be separate allocations or 512-B-aligned ranges of one buffer (as inside
+ * a `docker save` archive); each obeys tsg_device_tar's contract on its own: only the
+ * complete blocks below its n_bytes are read by the index, and the 64 readable bytes
+ * past a range's end are whatever follows it in the buffer.  Versioned like
+ * tsg_device_files. */
+typedef struct tsg_device_tars {
+  uint32_t struct_size, n_layers;
+  const tsg_device_tar* layers; /* n_layers of them, each v1 */
+} tsg_device_tars;
+#define TSG_DEVICE_TARS_SIZE_V1 ((uint32_t)(offsetof(tsg_device_tars, layers) + sizeof(const tsg_device_tar*)))
+#define TSG_DEVICE_TARS_MAX_LAYERS 65536u
+
+/* layers: of the call; batched: layers whose index came from a forest pass; fallbacks:
+ * layers a pass left INCOMPLETE (or too large for one) and mode 0 indexed again;
+ * passes: forest passes run (more than one when the layers' virtual block space --
+ * each layer's blocks rounded up to whole segments -- exceeds 2^31 blocks);
+ * virtual_blocks, segments: summed over the passes; device_bytes: the most HBM the
+ * call held at one time.  ms_candidates .. ms_compact: the kernels by stage and ms_copy
+ * the records and names to the host (HIP events); ms_host: clean, classify, Required
+ * and the indexes of all layers (wall); ms_total: the whole call.  All zero but layers
+ * and ms_total in walk mode 0. */
+typedef struct tsg_tar_forest_stats {
+  uint32_t struct_size, reserved;
+  uint64_t layers, batched, fallbacks, passes, virtual_blocks, segments, device_bytes;
+  double ms_candidates, ms_entries, ms_mark, ms_compact, ms_copy, ms_host, ms_total;
+} tsg_tar_forest_stats;
+#define TSG_TAR_FOREST_STATS_SIZE_V1 ((uint32_t)(offsetof(tsg_tar_forest_stats, ms_total) + sizeof(double)))
+
+/* out[k] (n_layers pointers) becomes what tsg_analyzer_index_device_tar gives for
+ * layer k alone in the analyzer's walk mode and with its tar-skip options: the files,
+ * the spans, st[k].tar and the skip stats; each index is independent, is freed with
+ * tsg_tar_index_free and is submitted with tsg_analyzer_submit_device_tar.  st
+ * (optional): n_layers stats, each with its struct_size set; for a layer indexed by a
+ * forest pass kernel_runs is 1, ms_kernel 0 (the kernels are shared: fs) and ms_total
+ * that layer's host half.  fs, bad_layer: optional.
+ * Walk mode 1: the header chains of all layers are walked by one GPU pass
+ * (trivy_amd/csrc/tarforest.hip) on one stream with one work buffer, one copy of the
+ * heads, one of all records and one of all names; the host half then runs per layer,
+ * the layers in parallel.  A layer the pass does not complete is indexed again by mode
+ * 0, alone (its tsg_tar_walk_stats.fallback says why); the others keep their batched
+ * result.  For a batched index tsg_tar_index_walk_stats carries walk, fallback,
+ * chain_entries, name_bytes and segments of that layer; the stage times are shared and
+ * live in fs.  Walk mode 0: the layers are indexed one after another by the
+ * single-layer path.
+ * Argument errors return -1 before any GPU work, a layer's with "layer k: " before the
+ * single-layer call's text: a NULL argument, an unknown struct_size (of t, of a layer,
+ * of a st[k], of fs), n_layers 0 or above TSG_DEVICE_TARS_MAX_LAYERS, a NULL or
+ * misaligned dev_tar, a layer of 2^32 or more blocks.  -3: a malformed layer -- the
+ * first one, lowest index -- with the host walk's message after "layer k: ", *bad_layer
+ * set; -2: no GPU engine, or a HIP error (one met in a layer's own single-layer pass has
+ * "layer k: " before its text; *bad_layer is written for -3 alone).  On any error every index made is freed and
+ * out[] is all NULL.  Work buffers above 16 MiB are freed before the call returns:
+ * once per image. */
+int tsg_analyzer_index_device_tars(tsg_analyzer* a, const tsg_device_tars* t, tsg_tar_index** out,
+                                   tsg_device_tar_stats* st, tsg_tar_forest_stats* fs, uint32_t* bad_layer);
+
 #ifdef __cplusplus
 }
 #endif

@@ -323,6 +323,27 @@ int tsg_debug_index_tar_records(struct tsg_analyzer* a, const uint8_t* host_tar,
 int tsg_debug_tar_chain(int device, const void* dev_tar, uint64_t n_bytes, uint32_t segment_blocks, uint32_t grid_cap,
                         void* records_out, uint64_t rec_cap, uint64_t* n_records, uint8_t* names_out,
                         uint64_t name_cap, uint64_t* name_bytes, uint64_t* stop_out, uint64_t* candidates_out);
+/* The virtual block space of a forest pass without a GPU (trivy_amd/csrc/tarforest.h:
+ * TarForestSpan, TarForestCut): v0_out[k], layer k's first virtual block with segments
+ * of segment_blocks (0 = the default), as if all layers shared one pass; *v_blocks_out,
+ * their total; *first_pass_out, how many layers from layer 0 on fit the first pass (0:
+ * layer 0 alone is too large).  -1: an argument error. */
+int tsg_debug_tar_forest_layout(const uint64_t* n_bytes, uint32_t n_layers, uint32_t segment_blocks, uint64_t* v0_out,
+                                uint64_t* v_blocks_out, uint32_t* first_pass_out);
+/* The GPU half of tsg_analyzer_index_device_tars alone (trivy_amd/csrc/tarforest.h):
+ * one forest pass over n_layers layers on HIP device `device`.  dev_tars: n_layers
+ * DEVICE pointers, each 16-B aligned; n_bytes: their sizes; segment_blocks and
+ * grid_cap as above.  The outputs are HOST buffers: heads_out, 8 words per layer --
+ * the 64 bytes of the layer's head: kind and reason (u32 each), offset, extension
+ * headers hopped, stitch steps, entries, name bytes, candidates, 0; rec_base_out and
+ * name_base_out, n_layers words each: where the layer's records (in records) and
+ * names (in bytes) begin; the records and names of all layers (-3 when either
+ * buffer is too small; *n_records and *name_bytes are the totals in any case).
+ * Nothing is written past the outputs.  -2: an argument or HIP error. */
+int tsg_debug_tar_forest(int device, const void* const* dev_tars, const uint64_t* n_bytes, uint32_t n_layers,
+                         uint32_t segment_blocks, uint32_t grid_cap, uint64_t* heads_out, uint64_t* rec_base_out,
+                         uint64_t* name_base_out, void* records_out, uint64_t rec_cap, uint64_t* n_records,
+                         uint8_t* names_out, uint64_t name_cap, uint64_t* name_bytes);
 /* The fallback reason (tsg_tar_walk_stats.fallback) of the analyzer's last index
  * call in mode 1, also of one that failed and so left no index to ask; -1: NULL. */
 int tsg_debug_tar_walk_last_fallback(const struct tsg_analyzer* a);

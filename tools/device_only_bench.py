@@ -41,8 +41,18 @@ host layer path), in one process on one scanner, with --fetch / --resident in fo
 JSON line per mode: ms per step with every block's figure, the index's ms_kernel / ms_total and
 counters, the bytes fetched per step and the host CPUs busy (process CPU time / wall time).
 
+--layers N [--layer-mb M | --layer-gb G]: an image of N layers resident in HBM as slices of one buffer
+(N = 5: bench.py's five-layer C4 image of G GB; otherwise N layers of M MB).  Blocks of
+AnalyzeLayersDevice -- one index call per group of layers, one window for all batches -- alternate
+with blocks of the loop of AnalyzeLayerDevice it replaces and of AnalyzeLayers(gather=True) on the
+host copies, all in tar-walk mode "gpu"; with --index-only, one tsg_analyzer_index_device_tars call
+against the loop of single-layer index calls.  One JSON line per mode: ms per step (median, min,
+max of the blocks), the host CPUs, the findings (equal in every mode), the forest stats and the
+share of the index time that ran beside scans.
+
 Usage: python tools/device_only_bench.py [--gb 4] [--steps 20] [--warmup 5] [--depth 3]
                                          [--analyze [--resident split]] [--layer [--layer-gb 4]]
+                                         [--layers N [--layer-mb 2] [--group-mb 1024] [--index-only]]
                                          [--fetch windows [--fwd N] [--fwd-cap N] [--back N]] [--out FILE]
 """
 import argparse
@@ -72,6 +82,15 @@ def main():
                     help="with --analyze; split: chunked and split blocks of AnalyzeDevice interleaved")
     ap.add_argument("--layer", action="store_true", help="the resident tar layer leg")
     ap.add_argument("--layer-gb", type=float, default=4.0)
+    ap.add_argument("--layers", type=int, default=0,
+                    help="the resident image leg: an image of this many layers, all in HBM as slices of one buffer; 5: "
+                         "bench.py's five-layer C4 image of --layer-gb in all (34/26/20/12/8 %%); otherwise equal layers "
+                         "of --layer-mb each.  AnalyzeLayersDevice (one index call per group, one window for all batches) "
+                         "against the loop of AnalyzeLayerDevice in gpu walk mode and against AnalyzeLayers(gather=True); "
+                         "with --index-only one tsg_analyzer_index_device_tars call against the loop of single-layer "
+                         "index calls")
+    ap.add_argument("--layer-mb", type=float, default=2.0, help="--layers: the size of each of the equal layers")
+    ap.add_argument("--group-mb", type=int, default=1024, help="--layers: AnalyzeLayersDevice's group_bytes")
     ap.add_argument("--arena-mb", type=int, default=256, help="--layer: batch size of both modes")
     ap.add_argument("--collectors", type=int, default=6, help="--layer: the host mode's collectors")
     ap.add_argument("--walk", choices=("host", "gpu", "both"), default="host",
@@ -87,6 +106,8 @@ def main():
     ap.add_argument("--fwd-cap", type=int, default=None)
     ap.add_argument("--back", type=int, default=None)
     args = ap.parse_args()
+    if args.layers:
+        return layers_leg(args)
     if args.layer:
         return layer_leg(args)
     if args.analyze and args.resident == "split":
@@ -578,6 +599,131 @@ def layer_leg(args):
             out["wait_s"] = med([r["wait_s"] for r in res[m]])
             out["added"] = int(last["added"])
         out["scan"] = {k[5:]: med([r[k] for r in res[m]]) for k in last if k.startswith("scan_")}
+        line = json.dumps(out)
+        print(line)
+        if args.out:
+            Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+
+
+def layers_leg(args):
+    """--layers: interleaved blocks of the batched calls and the loops they replace, on one image in one process."""
+    import torch
+    import trivy_amd.secret as secret
+    from trivy_amd import corpus
+    from trivy_amd.analyzer import AnalyzerOptions, SecretAnalyzer
+
+    if args.layers == 5:
+        w = [0.34, 0.26, 0.20, 0.12, 0.08]
+        layers = [corpus.generate_layer(int(args.layer_gb * 1e9 * x), seed=corpus.SEED + 1000 * k) for k, x in enumerate(w)]
+    else:
+        layers = [corpus.generate_layer(int(args.layer_mb * 1e6), seed=corpus.SEED + 1000 * k) for k in range(args.layers)]
+    sizes = [int(ly.nbytes) for ly in layers]
+    assert all(n % 512 == 0 for n in sizes)
+    total = sum(sizes)
+    dev = torch.device("cuda", 0)
+    d_image = torch.empty(total + 64, dtype=torch.uint8, device=dev)  # the layers back to back, as in a saved image
+    at, slices = 0, []
+    for ly, n in zip(layers, sizes):
+        d_image[at:at + n].copy_(torch.from_numpy(ly))
+        slices.append((d_image[at:at + n + 64], n))
+        at += n
+    d_image[total:].zero_()
+    torch.cuda.synchronize()
+    an = SecretAnalyzer(device=0)
+    an.Init(AnalyzerOptions())
+    sc = an.scanner
+    sc.set_resident_transform(args.resident)
+    if args.fetch == "windows":
+        sc.set_fetch_mode("windows", back=args.back, fwd=args.fwd, fwd_cap=args.fwd_cap)
+    an.set_tar_walk("gpu")
+    modes = ("batched", "loop") if args.index_only else ("batched", "loop", "host")
+    unregister = []
+    workers = None
+    if "host" in modes:
+        unregister = [secret.HostRegister(ly, mapped=True) for ly in layers]  # once, outside the timed region
+        workers = an.LayerWorkers(3, args.arena_mb << 20, args.collectors, gather=True)
+    arena = args.arena_mb << 20
+
+    def step(mode):
+        st = {"findings": 0}
+        if mode == "batched" and args.index_only:
+            stats = []
+            an.IndexLayersDevice(slices, stats=stats)
+            st["forest"] = stats[-1]
+        elif mode == "loop" and args.index_only:
+            per = []
+            for t, n in slices:
+                ix = an.IndexDevice(t, n)
+                per.append(ix.walk_stats)
+            st["stages"] = {k: sum(w[k] for w in per) for k in per[0] if k.startswith("ms_")}
+            st["device_bytes"] = sum(w["device_bytes"] for w in per)  # allocated and freed over the image
+        elif mode == "batched":
+            stats = []
+            an.AnalyzeLayersDevice(slices, arena_bytes=arena, depth=args.depth, group_bytes=args.group_mb << 20,
+                                   materialize=False, stats=stats)
+            st["forest"] = stats[-1]
+            st["findings"] = sum(d.get("scan_findings", 0) for d in stats[:-1])
+        elif mode == "loop":
+            for t, n in slices:
+                d = {}
+                an.AnalyzeLayerDevice(t, n, arena_bytes=arena, depth=args.depth, stats=d, materialize=False)
+                st["findings"] += d.get("scan_findings", 0)
+        else:
+            stats = []
+            an.AnalyzeLayers(layers, materialize=False, stats=stats, workers=workers, registered=True)
+            st["findings"] = sum(d.get("scan_findings", 0) for d in stats)
+        return st
+
+    def block(mode, n):
+        torch.cuda.synchronize()
+        t0, c0 = time.perf_counter(), time.process_time()
+        sts = [step(mode) for _ in range(n)]
+        wall = time.perf_counter() - t0
+        return wall, (time.process_time() - c0) / wall, sts
+
+    try:
+        for mode in modes:
+            block(mode, args.warmup)
+        per = {m: [] for m in modes}
+        cpus = {m: [] for m in modes}
+        res = {m: [] for m in modes}
+        done = 0
+        while done < args.steps:
+            n = min(args.block, args.steps - done)
+            for mode in modes:
+                s, cpu, sts = block(mode, n)
+                per[mode].append(1e3 * s / n)
+                cpus[mode].append(cpu)
+                res[mode] += sts
+            done += n
+    finally:
+        for u in unregister:
+            u()
+
+    def med(xs):
+        return float(statistics.median(xs))
+    findings = {m: int(res[m][-1]["findings"]) for m in modes}
+    if not args.index_only:
+        assert len(set(findings.values())) == 1, findings
+    for m in modes:
+        out = {"tool": "device_only_bench --layers", "mode": m, "index_only": args.index_only, "layers": len(layers),
+               "gb": total / 1e9, "layer_bytes": sizes if len(sizes) <= 8 else [sizes[0], "...", sizes[-1]],
+               "steps": args.steps, "block": args.block, "depth": args.depth, "arena_mb": args.arena_mb,
+               "group_mb": args.group_mb, "fetch": args.fetch, "resident": args.resident,
+               "ms_per_step": med(per[m]), "blocks_ms": per[m], "min_ms": min(per[m]), "max_ms": max(per[m]),
+               "gbps": total / 1e6 / med(per[m]), "host_cpus": med(cpus[m]), "findings": findings[m]}
+        if m == "batched":
+            out["batched_slowest_below_loop_fastest"] = max(per["batched"]) < min(per["loop"])
+            out["forest"] = {k: med([r["forest"][k] for r in res[m]]) for k in res[m][-1]["forest"]}
+            if not args.index_only:  # the share of the index time that ran beside scans
+                f = out["forest"]
+                hidden = f["index_s"] + f["scan_s"] - f["wall_s"]
+                out["index_hidden_share"] = max(0.0, min(1.0, hidden / f["index_s"])) if f["index_s"] > 0 else 0.0
+        if m == "loop" and args.index_only:
+            out["stages"] = {k: med([r["stages"][k] for r in res[m]]) for k in res[m][-1]["stages"]}
+            out["device_bytes_allocated"] = med([r["device_bytes"] for r in res[m]])
         line = json.dumps(out)
         print(line)
         if args.out:

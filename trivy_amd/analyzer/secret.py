@@ -104,6 +104,46 @@ TAR_WALK_FALLBACKS = ("", "size field", "PAX record", "PAX size form", "cap", "n
                       "too many blocks")
 
 
+class _CDeviceTars(c.Structure):  # tsg_device_tars (versioned)
+    _fields_ = [("struct_size", c.c_uint32), ("n_layers", c.c_uint32), ("layers", c.POINTER(_CDeviceTar))]
+
+
+DEVICE_TARS_SIZE_V1 = _CDeviceTars.layers.offset + c.sizeof(c.c_void_p)
+DEVICE_TARS_MAX_LAYERS = 65536
+
+
+class _CTarForestStats(c.Structure):  # tsg_tar_forest_stats (versioned)
+    _fields_ = [("struct_size", c.c_uint32), ("reserved", c.c_uint32)] + \
+               [(n, c.c_uint64) for n in ("layers", "batched", "fallbacks", "passes", "virtual_blocks", "segments",
+                                          "device_bytes")] + \
+               [(n, c.c_double) for n in ("ms_candidates", "ms_entries", "ms_mark", "ms_compact", "ms_copy", "ms_host",
+                                          "ms_total")]
+
+    def to_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n not in ("struct_size", "reserved")}
+
+
+TAR_FOREST_STATS_SIZE_V1 = _CTarForestStats.ms_total.offset + c.sizeof(c.c_double)
+
+
+def layer_groups(nbytes: Sequence[int], base: Optional[Sequence[bool]] = None, group_bytes: int = 1 << 30):
+    """How AnalyzeLayersDevice groups the layers of an image for its index calls: the layers that are no
+    base layer, in order, in runs of at most group_bytes of layer bytes; a larger layer goes alone.
+    Returns lists of layer numbers."""
+    out, cur, tot = [], [], 0
+    for k, n in enumerate(nbytes):
+        if base is not None and base[k]:
+            continue
+        if cur and tot + int(n) > group_bytes:
+            out.append(cur)
+            cur, tot = [], 0
+        cur.append(k)
+        tot += int(n)
+    if cur:
+        out.append(cur)
+    return out
+
+
 class _CTarSkipStats(c.Structure):  # tsg_tar_skip_stats (versioned)
     _fields_ = [("struct_size", c.c_uint32), ("reserved", c.c_uint32)] + \
                [(n, c.c_uint64) for n in ("skipped_dirs", "skipped_files", "under_skipped_dir")]
@@ -130,6 +170,10 @@ def _declare(L):
         L.tsg_analyzer_get_tar_walk.argtypes = [c.c_void_p, c.POINTER(c.c_int)]
         L.tsg_tar_index_walk_stats.argtypes = [c.c_void_p, c.POINTER(_CTarWalkStats)]
         L.tsg_debug_tar_walk_last_fallback.argtypes = [c.c_void_p]
+    if hasattr(L, "tsg_analyzer_index_device_tars"):  # (absent from an older build of the library: TSG_LIB)
+        L.tsg_analyzer_index_device_tars.argtypes = [c.c_void_p, c.POINTER(_CDeviceTars), c.POINTER(c.c_void_p),
+                                                     c.POINTER(_CDeviceTarStats), c.POINTER(_CTarForestStats),
+                                                     c.POINTER(c.c_uint32)]
     L.tsg_analyzer_classify_device.argtypes = [c.c_void_p, c.POINTER(_CDeviceFiles), c.c_void_p, c.c_void_p,
                                                c.POINTER(_CDeviceClassifyStats)]
     L.tsg_analyzer_submit_device.argtypes = [c.c_void_p, c.POINTER(_CDeviceFiles), c.POINTER(c.c_void_p)]
@@ -854,6 +898,166 @@ class SecretAnalyzer:
             stats.update({"scan_" + k2: v for k2, v in scan_tot.items()})
             stats.update({"files": ix.n, "scan_s": time.perf_counter() - t0})
         return result
+
+    # --- all layers of an image resident in HBM --------------------------------
+    def _device_layers(self, layers):
+        """[(ptr, nbytes, keep)] of the layers of an image: each a torch.uint8 tensor (nbytes = numel - 64), a
+        (tensor, nbytes) pair or a (ptr, nbytes) pair, checked as _device_layer checks one.  Slices of one
+        resident buffer are layers like any other."""
+        out = []
+        for k, ly in enumerate(layers):
+            try:
+                r = self._device_layer(*ly) if isinstance(ly, (tuple, list)) else self._device_layer(ly, None)
+                if r[0] % 16 != 0:
+                    raise ValueError("AnalyzeLayerDevice: the layer must be 16-B aligned")
+            except ValueError as e:
+                raise ValueError("layer %d: %s" % (k, e)) from None
+            out.append(r)
+        return out
+
+    def _index_device_layers(self, resolved, which):
+        """One tsg_analyzer_index_device_tars call over the layers `which` of `resolved`:
+        ([DeviceTarIndex], the forest stats dict)."""
+        if not hasattr(self._L, "tsg_analyzer_index_device_tars"):
+            raise RuntimeError("this build of the library has no tsg_analyzer_index_device_tars")
+        n = len(which)
+        arr = (_CDeviceTar * n)(*[_CDeviceTar(DEVICE_TAR_SIZE_V1, 0, resolved[k][0], resolved[k][1]) for k in which])
+        t = _CDeviceTars(DEVICE_TARS_SIZE_V1, n, arr)
+        st = (_CDeviceTarStats * n)()
+        for x in st:
+            x.struct_size = DEVICE_TAR_STATS_SIZE_V1
+        fs = _CTarForestStats()
+        fs.struct_size = TAR_FOREST_STATS_SIZE_V1
+        hs = (c.c_void_p * n)()
+        bad = c.c_uint32(0)
+        rc = self._L.tsg_analyzer_index_device_tars(self._h, c.byref(t), hs, st, c.byref(fs), c.byref(bad))
+        if rc == -3:  # a malformed archive: "layer j: " + the host walk's message, j counted in this call
+            msg = _lib.last_error(self._L)
+            pre = "layer %d: " % bad.value
+            raise ValueError("tar layer %d: %s" % (which[bad.value], msg[len(pre):] if msg.startswith(pre) else msg))
+        if rc != 0:
+            raise RuntimeError("tsg_analyzer_index_device_tars failed: %s" % _lib.last_error(self._L))
+        out = []
+        for j, k in enumerate(which):
+            d = st[j].to_dict()
+            ix = DeviceTarIndex(self, c.c_void_p(hs[j]), resolved[k][2], d)
+            d.update(ix.skip_stats)
+            out.append(ix)
+        return out, fs.to_dict()
+
+    def IndexLayersDevice(self, layers, stats: Optional[list] = None) -> List[DeviceTarIndex]:
+        """The DeviceTarIndex of every layer of an image resident in HBM, made by one call
+        (tsg_analyzer_index_device_tars): in tar-walk mode "gpu" one GPU pass walks the header chains of all
+        layers.  Each layer is a torch.uint8 tensor (nbytes = numel - 64), a (tensor, nbytes) pair or a
+        (ptr, nbytes) pair; slices of one resident buffer are allowed (a slice's 64 readable bytes past its
+        end are whatever follows it in the buffer).  Each index is what IndexDevice gives for that layer alone
+        and keeps its tensor alive.  stats (a list): the per-layer stats dicts, then the forest stats."""
+        resolved = self._device_layers(layers)
+        ixs, fs = self._index_device_layers(resolved, list(range(len(resolved))))
+        if stats is not None:
+            stats[:] = [ix.stats for ix in ixs] + [fs]
+        return ixs
+
+    def AnalyzeLayersDevice(self, layers, base: Optional[Sequence[bool]] = None, arena_bytes: int = 1 << 30,
+                            depth: int = 2, group_bytes: int = 1 << 30, materialize: bool = True,
+                            stats: Optional[list] = None) -> List[AnalysisResult]:
+        """AnalyzeLayers for an image whose layers exist only in HBM (layers as IndexLayersDevice takes them):
+        per layer exactly what AnalyzeLayerDevice returns, sorted as AnalyzeLayers sorts.  A base layer is
+        neither indexed nor scanned and yields an empty result.  The other layers are taken in order in groups
+        of at most group_bytes of layer bytes (layer_groups); a background thread indexes group g + 1 with one
+        tsg_analyzer_index_device_tars call while this thread submits and collects the batches of group g.  All
+        batches of all layers share one window of `depth` in flight, which is not drained at a layer or group
+        boundary.  stats (a list): per layer the dict AnalyzeLayerDevice fills (None for base layers), then one
+        dict of the forest stats summed over the groups with index_s, scan_s and wall_s.  An error stops the
+        pipeline, joins every batch in flight and the index thread, and is raised: ValueError("tar layer k:
+        ...") for a malformed layer, RuntimeError otherwise."""
+        import queue
+        import threading
+        t_wall = time.perf_counter()
+        resolved = self._device_layers(layers)
+        n = len(resolved)
+        base = list(base) if base is not None else [False] * n
+        if len(base) != n:
+            raise ValueError("AnalyzeLayersDevice: base flags must match the layers")
+        groups = layer_groups([r[1] for r in resolved], base, group_bytes)
+        results = [AnalysisResult() for _ in range(n)]
+        per: List[Optional[dict]] = [None] * n
+        scan_tot: List[dict] = [{} for _ in range(n)]
+        span = [[None, None] for _ in range(n)]  # first submit, last collect
+        forest: dict = {}
+        index_s = [0.0]
+        q: "queue.Queue" = queue.Queue()
+        go = threading.Semaphore(0)  # one release per group the indexer may start on
+        stop = threading.Event()
+
+        def indexer():
+            for gi, g in enumerate(groups):
+                go.acquire()
+                if stop.is_set():
+                    return
+                t0 = time.perf_counter()
+                try:
+                    item = self._index_device_layers(resolved, g)
+                except BaseException as e:
+                    q.put(e)
+                    return
+                index_s[0] += time.perf_counter() - t0
+                q.put(item)
+
+        inflight = collections.deque()
+
+        def take():
+            k, p = inflight.popleft()
+            out = p.wait(materialize)
+            span[k][1] = time.perf_counter()
+            if materialize:
+                results[k].Secrets.extend(sec for sec in out if sec is not None)
+            else:
+                for k2, v in out.items():
+                    scan_tot[k][k2] = scan_tot[k].get(k2, 0) + v
+        th = threading.Thread(target=indexer, name="tsg-layers-index")
+        th.start()
+        scan_s = 0.0
+        try:
+            go.release()  # group 0
+            for g in groups:
+                item = q.get()
+                if isinstance(item, BaseException):
+                    raise item
+                go.release()  # the next group is indexed while this one's batches are submitted and collected
+                ixs, fs = item
+                for k2, v in fs.items():
+                    forest[k2] = max(forest.get(k2, 0), v) if k2 == "device_bytes" else forest.get(k2, 0) + v
+                t0 = time.perf_counter()
+                for k, ix in zip(g, ixs):
+                    per[k] = dict(ix.stats)
+                    per[k]["walk"] = ix.walk_stats
+                    per[k]["files"] = ix.n
+                    span[k][0] = time.perf_counter()
+                    for first, count in ix.batches(arena_bytes):
+                        while len(inflight) >= max(1, depth):
+                            take()
+                        inflight.append((k, ix.submit(first, count)))
+                scan_s += time.perf_counter() - t0
+            t0 = time.perf_counter()
+            while inflight:
+                take()
+            scan_s += time.perf_counter() - t0
+        finally:
+            while inflight:  # an error left batches in flight: join them before the indexes go
+                inflight.popleft()[1].__del__()
+            stop.set()
+            go.release()
+            th.join()
+        for k in range(n):
+            results[k].Sort()
+            if per[k] is not None:
+                per[k].update({"scan_" + k2: v for k2, v in scan_tot[k].items()})
+                per[k]["scan_s"] = (span[k][1] - span[k][0]) if span[k][1] is not None else 0.0
+        if stats is not None:
+            forest.update({"index_s": index_s[0], "scan_s": scan_s, "wall_s": time.perf_counter() - t_wall})
+            stats[:] = per + [forest]
+        return results
 
     def AnalyzeFS(self, root: str, opt=None, arena_bytes: int = 256 << 20, stats: Optional[dict] = None,
                   materialize: bool = True, colls: Optional[List["Collector"]] = None,

@@ -8,6 +8,10 @@
 // mode 1 (tsg_analyzer_set_tar_walk) the GPU walks the chain as well
 // (tarchain.hip) and the host half starts from its entry records
 // (IndexTarEntries); a layer that walk does not complete takes the path above.
+// tsg_analyzer_index_device_tars takes all layers of an image: in walk mode 1
+// one forest pass (tarforest.hip) walks the chains of all of them, the host half
+// runs per layer, and a layer the pass does not complete takes the single-layer
+// path alone.
 #include <hip/hip_runtime_api.h>
 #include <pthread.h>
 
@@ -50,13 +54,19 @@ struct TarIndexCtx {
   uint64_t cap_rec = 0, cap_h = 0;  // records
   // the GPU walk (tsg_analyzer_set_tar_walk mode 1): its stage events, its work buffer, the entry
   // records and names on the device and page-locked on the host, the head the host reads
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // ([5], [6]: the forest pass)
   uint8_t* d_work = nullptr;
   uint8_t* d_out = nullptr;
   uint8_t* h_out = nullptr;        // pinned
   TarChainHead* h_head = nullptr;  // pinned
   uint64_t cap_work = 0, cap_out = 0, cap_hout = 0;  // bytes
+  // the forest pass (tsg_analyzer_index_device_tars): the head array and the uploaded tables, pinned
+  uint8_t* h_heads = nullptr;
+  uint8_t* h_tables = nullptr;
+  uint64_t cap_heads = 0, cap_tables = 0;  // bytes
   ~TarIndexCtx() {
+    if (h_heads) (void)hipHostFree(h_heads);
+    if (h_tables) (void)hipHostFree(h_tables);
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
     if (d_work) (void)hipFree(d_work);
@@ -136,6 +146,16 @@ void GiveCtx(tsg_analyzer* a, std::unique_ptr<TarIndexCtx> c) {
     (void)hipHostFree(c->h_out);
     c->h_out = nullptr;
     c->cap_hout = 0;
+  }
+  if (c->cap_heads > kKeepBytes) {
+    (void)hipHostFree(c->h_heads);
+    c->h_heads = nullptr;
+    c->cap_heads = 0;
+  }
+  if (c->cap_tables > kKeepBytes) {
+    (void)hipHostFree(c->h_tables);
+    c->h_tables = nullptr;
+    c->cap_tables = 0;
   }
   std::lock_guard<std::mutex> g(a->tar_index->mu);
   if (a->tar_index->free.size() < 2) a->tar_index->free.push_back(std::move(c));  // (else freed here)
@@ -301,46 +321,125 @@ int ChainOnGpu(TarIndexCtx* c, const uint8_t* dev_tar, uint64_t n_bytes, uint32_
   return 0;
 }
 
+// One forest pass (tarforest.h) over n layers on the context's stream: 0 with the heads (in c->h_heads),
+// every layer's record and name base, and *recs / *names (in c->h_out) for all of them; -2 a HIP error or
+// a segment size that is none, its text set.  The layers fit one pass (TarForestCut).  Two
+// synchronisations: after the head copy, and after the compaction and the two copies.
+struct ForestPass {
+  TarForestLayout L;
+  const TarChainHead* heads = nullptr;
+  std::vector<uint64_t> rec_base, name_base;  // n + 1 each
+  const tsg_tar_entry_rec* recs = nullptr;
+  const uint8_t* names = nullptr;
+};
+int ForestOnGpu(TarIndexCtx* c, const void* const* ptrs, const uint64_t* n_bytes, uint32_t n, uint32_t segment_blocks,
+                uint32_t grid_cap, const std::string& who, ForestPass* P, tsg_tar_forest_stats* fs) {
+  TarForestLayout& L = P->L;
+  if (!TarForestPlan(n_bytes, n, segment_blocks, &L)) {
+    SetError(who + ": segment_blocks must be a power of two from 8 to 8192, and the layers must fit one pass");
+    return -2;
+  }
+  hipError_t e = hipSuccess;
+  auto ok = [&](hipError_t r) {
+    if (e == hipSuccess) e = r;
+    return e == hipSuccess;
+  };
+  for (hipEvent_t& v : c->ev)
+    if (!v) ok(hipEventCreate(&v));
+  const uint64_t head_bytes = uint64_t(n) * sizeof(TarChainHead);
+  if (ok(e)) Grow(&c->h_heads, &c->cap_heads, head_bytes, true, &e);
+  if (ok(e)) Grow(&c->h_tables, &c->cap_tables, L.tables_bytes, true, &e);
+  if (ok(e)) Grow(&c->d_work, &c->cap_work, L.bytes, false, &e);
+  uint64_t rec_bytes = 0, out_bytes = 0, entries = 0, name_bytes = 0;
+  if (ok(e)) {
+    TarForestTables(L, ptrs, n_bytes, c->h_tables);
+    if (ok(TarForestWalk(L, c->h_tables, c->d_work, grid_cap, c->s, c->ev)) &&
+        ok(hipMemcpyAsync(c->h_heads, c->d_work + L.heads, head_bytes, hipMemcpyDeviceToHost, c->s)))
+      ok(hipStreamSynchronize(c->s));
+  }
+  if (ok(e)) {
+    P->heads = reinterpret_cast<const TarChainHead*>(c->h_heads);
+    constexpr size_t kHeadWords = sizeof(TarChainHead) / 8;
+    TarForestBases(&P->heads[0].entries, kHeadWords, n, &P->rec_base);
+    TarForestBases(&P->heads[0].name_bytes, kHeadWords, n, &P->name_base);
+    entries = P->rec_base[n];
+    name_bytes = P->name_base[n];
+    rec_bytes = (entries * sizeof(tsg_tar_entry_rec) + 255) & ~uint64_t(255);
+    out_bytes = rec_bytes + name_bytes + 256;
+    // one compaction, one copy of all records, one of all names, one synchronisation
+    if (Grow(&c->d_out, &c->cap_out, out_bytes, false, &e) && Grow(&c->h_out, &c->cap_hout, out_bytes, true, &e) &&
+        ok(hipEventRecord(c->ev[5], c->s)) &&
+        ok(TarForestCompact(L, c->d_work, entries, name_bytes, c->d_out, c->d_out + rec_bytes, grid_cap, c->s)) &&
+        ok(hipEventRecord(c->ev[4], c->s)) &&
+        (entries == 0 || ok(hipMemcpyAsync(c->h_out, c->d_out, entries * sizeof(tsg_tar_entry_rec),
+                                           hipMemcpyDeviceToHost, c->s))) &&
+        (name_bytes == 0 || ok(hipMemcpyAsync(c->h_out + rec_bytes, c->d_out + rec_bytes, name_bytes,
+                                              hipMemcpyDeviceToHost, c->s))) &&
+        ok(hipEventRecord(c->ev[6], c->s)))
+      ok(hipStreamSynchronize(c->s));
+  }
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(c->s);  // nothing of a failed pass is left queued on a pooled stream
+    SetError(who + ": " + hipGetErrorString(e));
+    return -2;
+  }
+  P->recs = reinterpret_cast<const tsg_tar_entry_rec*>(c->h_out);
+  P->names = c->h_out + rec_bytes;
+  if (fs) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) fs->ms_candidates += ms;
+    if (hipEventElapsedTime(&ms, c->ev[1], c->ev[2]) == hipSuccess) fs->ms_entries += ms;
+    if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) fs->ms_mark += ms;
+    if (hipEventElapsedTime(&ms, c->ev[5], c->ev[4]) == hipSuccess) fs->ms_compact += ms;
+    if (hipEventElapsedTime(&ms, c->ev[4], c->ev[6]) == hipSuccess) fs->ms_copy += ms;
+    fs->passes++;
+    fs->virtual_blocks += L.v_blocks;
+    fs->segments += L.n_segments;
+    fs->device_bytes = std::max<uint64_t>(fs->device_bytes, L.bytes + out_bytes);
+  }
+  return 0;
+}
+
 }  // namespace
 }  // namespace tsg
 
 extern "C" {
 
-int tsg_analyzer_index_device_tar(tsg_analyzer* a, const tsg_device_tar* t, tsg_tar_index** out,
-                                  tsg_device_tar_stats* st) {
+// The checks of one tsg_device_tar; `who` names the call (and the layer, where there are several).
+static bool DeviceTarOk(const std::string& who, const tsg_device_tar* t) {
   using namespace tsg;
-  const std::string who = "tsg_analyzer_index_device_tar";
-  if (out) *out = nullptr;
-  if (!a || !t || !out) {
-    SetError(who + ": NULL analyzer, tar or out");
-    return -1;
-  }
   if (t->struct_size != TSG_DEVICE_TAR_SIZE_V1) {
     SetError(who + ": tsg_device_tar.struct_size " + std::to_string(t->struct_size) +
              " is not a size this library knows (v1 = " + std::to_string(TSG_DEVICE_TAR_SIZE_V1) + ")");
-    return -1;
+    return false;
   }
-  if (!StatsSizeOk(st, who.c_str())) return -1;
   if (!t->dev_tar) {
     SetError(who + ": dev_tar is NULL (the layer's bytes, resident in HBM)");
-    return -1;
+    return false;
   }
   if (reinterpret_cast<uintptr_t>(t->dev_tar) % 16 != 0) {
     SetError(who + ": dev_tar must be 16-B aligned");
-    return -1;
+    return false;
   }
   if ((t->n_bytes / 512) >> 32) {
     SetError(who + ": a layer of " + std::to_string(t->n_bytes) + " bytes has 2^32 or more 512-B blocks");
-    return -1;
+    return false;
   }
+  return true;
+}
+
+// One layer by the single-layer path, its arguments checked: tsg_analyzer_index_device_tar's work.
+// forced_fallback != NULL: the layer is one a forest pass (tsg_analyzer_index_device_tars) did not
+// complete for that reason -- mode 0 indexes it, and the index says walk 1 with that fallback.
+static int IndexOneLayer(tsg_analyzer* a, const std::string& who, const uint8_t* dev_tar, uint64_t n_bytes,
+                         const uint32_t* forced_fallback, tsg_tar_index** out, tsg_device_tar_stats* st) {
+  using namespace tsg;
   const int device = a->s->s->device();
   if (device < 0) {
     SetError(who + ": no GPU engine bound to this analyzer's scanner");
     return -2;
   }
   const double t0 = NowMs();
-  const uint8_t* dev_tar = static_cast<const uint8_t*>(t->dev_tar);
-  const uint64_t n_bytes = t->n_bytes;
   hipError_t e = hipSetDevice(device);
   std::unique_ptr<TarIndexCtx> c = e == hipSuccess ? TakeCtx(a) : nullptr;
   if (!c) {
@@ -352,8 +451,9 @@ int tsg_analyzer_index_device_tar(tsg_analyzer* a, const tsg_device_tar* t, tsg_
     return e == hipSuccess;
   };
   tsg_tar_walk_stats ws{};
-  ws.walk = uint32_t(a->tar_walk.load());
-  if (ws.walk == 1) {
+  ws.walk = forced_fallback ? 1u : uint32_t(a->tar_walk.load());
+  if (forced_fallback) ws.fallback = *forced_fallback;
+  if (ws.walk == 1 && !forced_fallback) {
     // The chain walk on the GPU.  A layer it does not complete falls through to the host walk below,
     // from scratch: that path alone words what is wrong with a malformed archive.
     std::unique_ptr<tsg_tar_index> ix(new tsg_tar_index());
@@ -463,6 +563,215 @@ int tsg_analyzer_index_device_tar(tsg_analyzer* a, const tsg_device_tar* t, tsg_
   FillStats(st, ix->d, src, n_bytes, count, runs, ms_kernel, NowMs() - t0);
   ix->ws = ws;
   *out = ix.release();
+  return 0;
+}
+
+int tsg_analyzer_index_device_tar(tsg_analyzer* a, const tsg_device_tar* t, tsg_tar_index** out,
+                                  tsg_device_tar_stats* st) {
+  using namespace tsg;
+  const std::string who = "tsg_analyzer_index_device_tar";
+  if (out) *out = nullptr;
+  if (!a || !t || !out) {
+    SetError(who + ": NULL analyzer, tar or out");
+    return -1;
+  }
+  if (t->struct_size == TSG_DEVICE_TAR_SIZE_V1 && !StatsSizeOk(st, who.c_str())) return -1;
+  if (!DeviceTarOk(who, t)) return -1;
+  return IndexOneLayer(a, who, static_cast<const uint8_t*>(t->dev_tar), t->n_bytes, nullptr, out, st);
+}
+
+int tsg_analyzer_index_device_tars(tsg_analyzer* a, const tsg_device_tars* t, tsg_tar_index** out,
+                                   tsg_device_tar_stats* st, tsg_tar_forest_stats* fs, uint32_t* bad_layer) {
+  using namespace tsg;
+  const std::string who = "tsg_analyzer_index_device_tars";
+  if (!a || !t || !out) {
+    SetError(who + ": NULL analyzer, tars or out");
+    return -1;
+  }
+  if (t->struct_size != TSG_DEVICE_TARS_SIZE_V1) {
+    SetError(who + ": tsg_device_tars.struct_size " + std::to_string(t->struct_size) +
+             " is not a size this library knows (v1 = " + std::to_string(TSG_DEVICE_TARS_SIZE_V1) + ")");
+    return -1;
+  }
+  if (t->n_layers == 0 || t->n_layers > TSG_DEVICE_TARS_MAX_LAYERS) {
+    SetError(who + ": n_layers " + std::to_string(t->n_layers) + " is not from 1 to " +
+             std::to_string(TSG_DEVICE_TARS_MAX_LAYERS));
+    return -1;
+  }
+  const uint32_t n = t->n_layers;
+  for (uint32_t k = 0; k < n; k++) out[k] = nullptr;
+  if (!t->layers) {
+    SetError(who + ": layers is NULL");
+    return -1;
+  }
+  if (fs && fs->struct_size != TSG_TAR_FOREST_STATS_SIZE_V1) {
+    SetError(who + ": tsg_tar_forest_stats.struct_size " + std::to_string(fs->struct_size) +
+             " is not a size this library knows (v1 = " + std::to_string(TSG_TAR_FOREST_STATS_SIZE_V1) + ")");
+    return -1;
+  }
+  for (uint32_t k = 0; k < n; k++) {
+    const std::string lw = who + ": layer " + std::to_string(k);
+    if (t->layers[k].struct_size == TSG_DEVICE_TAR_SIZE_V1 && st && !StatsSizeOk(&st[k], lw.c_str())) return -1;
+    if (!DeviceTarOk(lw, &t->layers[k])) return -1;
+  }
+  const double t0 = NowMs();
+  tsg_tar_forest_stats F{};
+  F.struct_size = TSG_TAR_FOREST_STATS_SIZE_V1;
+  F.layers = n;
+  std::vector<std::unique_ptr<tsg_tar_index>> ixs(n);  // (an error return frees what was made)
+  std::vector<const void*> ptrs(n);
+  std::vector<uint64_t> nb(n);
+  for (uint32_t k = 0; k < n; k++) {
+    ptrs[k] = t->layers[k].dev_tar;
+    nb[k] = t->layers[k].n_bytes;
+  }
+  const int mode = a->tar_walk.load();
+  std::vector<uint8_t> single(n, mode == 1 ? 0 : 1);  // layers the single-layer path indexes
+  std::vector<uint32_t> fallback(n, 0);
+  if (mode == 1) {
+    const int device = a->s->s->device();
+    if (device < 0) {
+      SetError(who + ": no GPU engine bound to this analyzer's scanner");
+      return -2;
+    }
+    std::unique_ptr<TarIndexCtx> c = hipSetDevice(device) == hipSuccess ? TakeCtx(a) : nullptr;
+    if (!c) {
+      SetError(who + ": stream / events");
+      return -2;
+    }
+    for (uint32_t first = 0; first < n;) {
+      const uint32_t cnt = TarForestCut(nb.data(), n, first, kTarDefaultSegment);
+      if (cnt == 0) {  // too large for a pass of its own
+        single[first] = 1;
+        fallback[first++] = kTarTooLarge;
+        continue;
+      }
+      ForestPass P;
+      if (ForestOnGpu(c.get(), ptrs.data() + first, nb.data() + first, cnt, 0, 0, who, &P, &F) < 0) {
+        GiveCtx(a, std::move(c));
+        return -2;
+      }
+      // the host half per layer, the layers side by side on the host pool
+      std::vector<int> rcs(cnt, 0);
+      const double th = NowMs();
+      ParallelFor(cnt, 16, [&](size_t j) {
+        const uint32_t k = first + uint32_t(j);
+        const TarChainHead& head = P.heads[j];
+        if (head.stop.kind != kTarStopEnd) {
+          single[k] = 1;
+          fallback[k] = head.stop.reason ? head.stop.reason : uint32_t(kTarNotCandidate);
+          return;
+        }
+        const double tl = NowMs();
+        std::unique_ptr<tsg_tar_index> ix(new tsg_tar_index());
+        ix->dev_tar = static_cast<const uint8_t*>(ptrs[k]);
+        ix->n_bytes = nb[k];
+        tsg_device_tar_stats tmp{};
+        tsg_device_tar_stats* sk = st ? &st[k] : &tmp;
+        rcs[j] = EntriesToIndex(a, P.recs + P.rec_base[j], head.entries, P.names + P.name_base[j], head.name_bytes,
+                                head.stop, nb[k], head.candidates, &ix->d, sk);
+        if (rcs[j] < 0) return;
+        ix->ws.walk = 1;
+        ix->ws.chain_entries = head.entries;
+        ix->ws.name_bytes = head.name_bytes;
+        ix->ws.segments = (nb[k] / 512 + P.L.segment - 1) / P.L.segment;
+        ix->ws.ms_host = NowMs() - tl;
+        sk->kernel_runs = 1;
+        sk->ms_kernel = 0;  // (the kernels are shared by the layers: tsg_tar_forest_stats)
+        sk->ms_total = ix->ws.ms_host;
+        ixs[k] = std::move(ix);
+      });
+      F.ms_host += NowMs() - th;
+      for (uint32_t j = 0; j < cnt; j++) {
+        if (rcs[j] < 0) {  // (records that contradict the name blob: the layer changed under the pass)
+          GiveCtx(a, std::move(c));
+          SetError(who + ": layer " + std::to_string(first + j) + ": the entry records contradict the name blob");
+          return -2;
+        }
+        if (ixs[first + j]) F.batched++;
+      }
+      first += cnt;
+    }
+    GiveCtx(a, std::move(c));  // (buffers above 16 MiB are freed here: once per image)
+    uint32_t last = 0;
+    for (uint32_t k = 0; k < n && !last; k++) last = fallback[k];
+    a->tar_fallback_last.store(last);
+  }
+  // The layers left to the single-layer path, in order: the first malformed one ends the call.
+  for (uint32_t k = 0; k < n; k++) {
+    if (!single[k]) continue;
+    tsg_tar_index* ix = nullptr;
+    const int rc = IndexOneLayer(a, who, static_cast<const uint8_t*>(ptrs[k]), nb[k], mode == 1 ? &fallback[k] : nullptr,
+                                 &ix, st ? &st[k] : nullptr);
+    if (rc != 0) {
+      const std::string msg = tsg_last_error();
+      SetError("layer " + std::to_string(k) + ": " + msg);
+      if (rc == -3 && bad_layer) *bad_layer = k;  // (a -2 names its layer in the text only)
+      return rc;
+    }
+    ixs[k].reset(ix);
+    if (mode == 1) F.fallbacks++;
+  }
+  for (uint32_t k = 0; k < n; k++) out[k] = ixs[k].release();
+  F.ms_total = NowMs() - t0;
+  if (fs) *fs = F;
+  return 0;
+}
+
+int tsg_debug_tar_forest_layout(const uint64_t* n_bytes, uint32_t n_layers, uint32_t segment_blocks, uint64_t* v0_out,
+                                uint64_t* v_blocks_out, uint32_t* first_pass_out) {
+  using namespace tsg;
+  const uint32_t seg = segment_blocks ? segment_blocks : kTarDefaultSegment;
+  if (!n_bytes || !v0_out || !v_blocks_out || !first_pass_out || n_layers == 0 || n_layers > kTarForestMaxLayers ||
+      seg < kTarMinSegment || (seg & (seg - 1))) {
+    SetError("tsg_debug_tar_forest_layout: NULL argument, a layer count out of range, or no segment size");
+    return -1;
+  }
+  uint64_t v = 0;
+  for (uint32_t k = 0; k < n_layers; k++) {
+    v0_out[k] = v;
+    v += TarForestSpan(n_bytes[k], seg);
+  }
+  *v_blocks_out = v;
+  *first_pass_out = TarForestCut(n_bytes, n_layers, 0, seg);
+  return 0;
+}
+
+int tsg_debug_tar_forest(int device, const void* const* dev_tars, const uint64_t* n_bytes, uint32_t n_layers,
+                         uint32_t segment_blocks, uint32_t grid_cap, uint64_t* heads_out, uint64_t* rec_base_out,
+                         uint64_t* name_base_out, void* records_out, uint64_t rec_cap, uint64_t* n_records,
+                         uint8_t* names_out, uint64_t name_cap, uint64_t* name_bytes) {
+  using namespace tsg;
+  const std::string who = "tsg_debug_tar_forest";
+  bool bad = !dev_tars || !n_bytes || !heads_out || !rec_base_out || !name_base_out || !n_records || !name_bytes ||
+             n_layers == 0 || n_layers > kTarForestMaxLayers || (rec_cap && !records_out) || (name_cap && !names_out);
+  for (uint32_t k = 0; !bad && k < n_layers; k++)
+    bad = (n_bytes[k] >= 512 && !dev_tars[k]) || reinterpret_cast<uintptr_t>(dev_tars[k]) % 16 != 0;
+  if (bad) {
+    SetError(who + ": NULL or misaligned pointer, or a layer count out of range");
+    return -2;
+  }
+  *n_records = *name_bytes = 0;
+  TarIndexCtx c;
+  hipError_t e = hipSetDevice(device);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&c.s, hipStreamNonBlocking);
+  if (e != hipSuccess) {
+    SetError(who + ": " + hipGetErrorString(e));
+    return -2;
+  }
+  ForestPass P;
+  if (ForestOnGpu(&c, dev_tars, n_bytes, n_layers, segment_blocks, grid_cap, who, &P, nullptr) < 0) return -2;
+  std::memcpy(heads_out, P.heads, size_t(n_layers) * sizeof(TarChainHead));
+  std::memcpy(rec_base_out, P.rec_base.data(), size_t(n_layers) * 8);
+  std::memcpy(name_base_out, P.name_base.data(), size_t(n_layers) * 8);
+  *n_records = P.rec_base[n_layers];
+  *name_bytes = P.name_base[n_layers];
+  if (*n_records > rec_cap || *name_bytes > name_cap) {
+    SetError(who + ": the output buffers are too small");
+    return -3;
+  }
+  if (*n_records) std::memcpy(records_out, P.recs, size_t(*n_records) * sizeof(tsg_tar_entry_rec));
+  if (*name_bytes) std::memcpy(names_out, P.names, size_t(*name_bytes));
   return 0;
 }
 

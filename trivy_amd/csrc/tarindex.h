@@ -11,6 +11,7 @@
 #include <cstdint>
 
 #include "tarchain.h"
+#include "tarforest.h"
 
 namespace tsg {
 
@@ -65,5 +66,32 @@ hipError_t TarChainWalk(const uint8_t* dev_tar, uint64_t n_bytes, const TarChain
 hipError_t TarChainCompact(const uint8_t* dev_tar, uint64_t n_bytes, const TarChainLayout& L, const uint8_t* d_work,
                            uint64_t n_entries, uint64_t name_bytes, uint8_t* d_records, uint8_t* d_names,
                            uint32_t grid_cap, hipStream_t s);
+
+// ---- all layers of an image in one pass (tarforest.hip; the contract: tarforest.h) ----
+// The one device buffer of a pass over n_layers layers whose virtual space has
+// v_blocks blocks: byte offsets of its parts (256-B aligned) and its size.  The
+// head array (a TarChainHead per layer) comes first; the layer table and the
+// u32 per segment that names its layer follow it as one range of tables_bytes,
+// which the host fills (TarForestTables) and the pass uploads.
+struct TarForestLayout {
+  uint32_t n_layers = 0, segment = 0;
+  uint64_t v_blocks = 0, n_segments = 0;
+  uint64_t heads = 0, layers = 0, seg_layer = 0, cand = 0, chain = 0, seg_entry = 0, succ = 0, nlen = 0, rank = 0,
+           noff = 0, temp = 0;
+  uint64_t tables_bytes = 0, temp_bytes = 0, bytes = 0;
+};
+// segment_blocks as for TarChainPlan.  false: it is no segment size, n_layers is 0 or above
+// kTarForestMaxLayers, or the layers do not fit one pass (TarForestCut says how many do).
+bool TarForestPlan(const uint64_t* n_bytes, uint32_t n_layers, uint32_t segment_blocks, TarForestLayout* L);
+// The tables of a planned pass into h_tables (L.tables_bytes bytes, host memory): ptrs[k] is 16-B aligned.
+void TarForestTables(const TarForestLayout& L, const void* const* ptrs, const uint64_t* n_bytes, uint8_t* h_tables);
+// Events as for TarChainWalk, ev[0] recorded after the upload of the tables.  After it the head array (d_work + L.heads) is complete.  h_tables stays
+// valid until the stream has passed the upload.
+hipError_t TarForestWalk(const TarForestLayout& L, const uint8_t* h_tables, uint8_t* d_work, uint32_t grid_cap,
+                         hipStream_t s, hipEvent_t* ev);
+// The records (64 B each; n_entries: the sum of the heads' entries) and the names (name_bytes: the sum
+// of the heads' name_bytes) of all layers, layer after layer; nothing is written past either.
+hipError_t TarForestCompact(const TarForestLayout& L, const uint8_t* d_work, uint64_t n_entries, uint64_t name_bytes,
+                            uint8_t* d_records, uint8_t* d_names, uint32_t grid_cap, hipStream_t s);
 
 }  // namespace tsg

@@ -353,6 +353,44 @@ int tsg_tar_index_walk_stats(const tsg_tar_index* ix, tsg_tar_walk_stats* out);
  * options).  -1: NULL argument or an unknown struct_size. */
 int tsg_tar_index_skip_stats(const tsg_tar_index* ix, tsg_tar_skip_stats* out);
 
+/* Where the path work and Required of a resident layer's index run.
+ * Mode 0, host (the default): as described above.  Mode 1, gpu (opt-in): behind the
+ * GPU walk's compaction a device stage (trivy_amd/csrc/tarrequired.hip) decides per
+ * entry what the host's clean-and-classify followed by Required decide, and hands
+ * over only the files Required keeps -- 48-B records and their cleaned paths, laid
+ * out as the index stores them -- plus the entries it leaves to the host: files
+ * whose path holds a literal of an allow-path rule (the exact rules run on those),
+ * and names that need more of path.Clean than a "./" or "/" prefix and trailing
+ * slashes.  The index, the stats and the results are those of mode 0 for any bytes.
+ * Applies to tsg_analyzer_index_device_tar and tsg_analyzer_index_device_tars, and is
+ * in force only when the walk mode is 1, no tsg_analyzer_set_tar_skip options are set
+ * and the GPU walk completed the layer; otherwise the host half of the walk mode in
+ * force runs, and tsg_tar_required_stats.reason says why -- that is no error.
+ * Takes effect with the next index call.  TSG_TAR_REQUIRED=gpu (or host) in the
+ * environment sets the initial mode of analyzers made afterwards.  -1: NULL analyzer
+ * or another mode (the text names it). */
+int tsg_analyzer_set_tar_required(tsg_analyzer* a, int mode);
+int tsg_analyzer_get_tar_required(const tsg_analyzer* a, int* mode);
+
+/* How an index's Required ran (versioned, struct_size first).  mode: the one in force
+ * for this index (1: the device stage ran); reason, when it is 0: 1 the setter is off,
+ * 2 walk mode 0, 3 skip options are set, 4 the GPU walk did not complete the layer
+ * (reason 0: the stage ran).  Of the layer's `entries` the device kept `kept` files,
+ * dropped `dropped` by Required, and asked the host about `ask_allow` (the exact allow
+ * rules) and `ask_name` (clean, classify, Required); ask_dropped: asked entries the
+ * host then dropped; path_bytes: the path blob handed over.  ms_kernel: the stage (HIP
+ * events; shared by the layers of one tsg_analyzer_index_device_tars pass, as ms_copy
+ * is); ms_copy: the file records and paths to the host; ms_host: the host half. */
+typedef struct tsg_tar_required_stats {
+  uint32_t struct_size, reserved;
+  uint32_t mode, reason;
+  uint64_t entries, kept, dropped, ask_allow, ask_name, ask_dropped, path_bytes;
+  double ms_kernel, ms_copy, ms_host;
+} tsg_tar_required_stats;
+#define TSG_TAR_REQUIRED_STATS_SIZE_V1 ((uint32_t)(offsetof(tsg_tar_required_stats, ms_host) + sizeof(double)))
+/* -1: NULL argument or an unknown struct_size. */
+int tsg_tar_index_required_stats(const tsg_tar_index* ix, tsg_tar_required_stats* out);
+
 /* All layers of an image resident in HBM, indexed by one call.  The
  * layers may be separate allocations or 512-B-aligned ranges of one buffer (as inside
  * a `docker save` archive); each obeys tsg_device_tar's contract on its own: only the

@@ -357,6 +357,34 @@ int tsg_debug_index_tar_entries(struct tsg_analyzer* a, const void* records, uin
                                 struct tsg_device_tar_stats* st);
 int tsg_debug_tar_batch_plan(const struct tsg_tar_index* ix, uint32_t first, uint32_t count, const uint8_t* flags,
                              uint64_t* base, uint64_t* offs, uint8_t* kinds, uint8_t* binary);
+/* The allow-path tables the Required stage of a resident layer reads (tsg_analyzer_set_tar_required
+ * mode 1; trivy_amd/csrc/pathfilter.h), as the scanner keeps them on the host: the raw PathTable
+ * into path_table_out and the raw SureTable into sure_table_out.  *have_out: bit 0 a path table,
+ * bit 1 a sure table.  -1: an argument error or a buffer too small. */
+int tsg_debug_tar_required_tables(const struct tsg_analyzer* a, void* path_table_out, uint64_t path_cap,
+                                  void* sure_table_out, uint64_t sure_cap, uint32_t* have_out);
+/* The device stage alone (trivy_amd/csrc/tarrequired.h) on the analyzer's GPU, over HOST buffers:
+ * n_records 64-B entry records in walk order, the name blob, and the layer table as n_layers + 1
+ * record bases and name bases (from 0 to n_records / name_bytes).  grid_cap != 0 caps every grid.
+ * Back come: a verdict byte per entry (0 other, 1 whiteout, 2 opaque dir, 3 dropped, 4 kept,
+ * 5 ask-allow, 6 ask-name, 7 a name outside its layer's blob), up to rec_cap 48-B file records, up to
+ * blob_cap bytes of paths (-3 when either is too small; the two totals are set in any case), and 16
+ * words of counts per layer.  -4: a record has its name outside its layer's blob -- it was not read,
+ * its verdict is 7, and the other outputs are those of the remaining entries.  -2: an argument or
+ * HIP error. */
+int tsg_debug_tar_required(struct tsg_analyzer* a, const void* records, uint64_t n_records, const uint8_t* names,
+                           uint64_t name_bytes, const uint64_t* rec_base, const uint64_t* name_base, uint32_t n_layers,
+                           uint32_t grid_cap, uint8_t* verdicts_out, void* file_recs_out, uint64_t rec_cap,
+                           uint64_t* n_file_recs, uint8_t* blob_out, uint64_t blob_cap, uint64_t* blob_bytes,
+                           uint64_t* counts_out);
+/* The host half behind that stage without a GPU: one layer's file records, its path blob and its 16
+ * words of counts are given instead of computed, with the stop (it must be END) as for
+ * tsg_debug_index_tar_entries.  The index (not submittable) and the stats come back as from the
+ * real call; kernel_runs is 0.  -1: an argument error, or records that contradict the blob or the
+ * counts. */
+int tsg_debug_index_tar_files(struct tsg_analyzer* a, const void* file_recs, uint64_t n_recs, const uint8_t* blob,
+                              uint64_t blob_bytes, const uint64_t* counts, const uint64_t* stop, uint64_t n_bytes,
+                              uint64_t candidates_given, struct tsg_tar_index** out, struct tsg_device_tar_stats* st);
 
 /* Thread-local text of the last error. */
 const char* tsg_last_error(void);

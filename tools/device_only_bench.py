@@ -50,6 +50,11 @@ against the loop of single-layer index calls.  One JSON line per mode: ms per st
 max of the blocks), the host CPUs, the findings (equal in every mode), the forest stats and the
 share of the index time that ran beside scans.
 
+--required host|gpu|both (with --layer --walk gpu|both, and with --layers): where the path work and
+Required of a GPU-walked layer run (SecretAnalyzer.set_tar_required).  gpu and both add the modes
+ending in "-req", in the same interleaved blocks; with --index-only their lines carry the stage's
+counts and times ("required").
+
 Usage: python tools/device_only_bench.py [--gb 4] [--steps 20] [--warmup 5] [--depth 3]
                                          [--analyze [--resident split]] [--layer [--layer-gb 4]]
                                          [--layers N [--layer-mb 2] [--group-mb 1024] [--index-only]]
@@ -98,6 +103,10 @@ def main():
                          "both: a block of each per round, interleaved")
     ap.add_argument("--layer-format", choices=("ustar", "pax"), default="ustar",
                     help="--layer: pax rewrites the generated layer with a PAX x header (path, mtime) before every entry")
+    ap.add_argument("--required", choices=("host", "gpu", "both"), default="host",
+                    help="--layer / --layers: where a GPU-walked layer's path work and Required run "
+                         "(SecretAnalyzer.set_tar_required); gpu and both need the GPU walk (--layer: --walk gpu or both) "
+                         "and add the modes ending in -req, interleaved with the others")
     ap.add_argument("--index-only", action="store_true", help="--layer: time IndexDevice alone, no scans, no host leg")
     ap.add_argument("--skip-dirs", default="", help="--layer: LayerTar skipDirs patterns, comma-separated; every mode "
                     "then also runs with the options set (mode name + \"+skip\"), in the same interleaved blocks")
@@ -514,7 +523,11 @@ def layer_leg(args):
     colls = [Collector(an, args.arena_mb << 20, True, gather=True) for _ in range(args.collectors)]
     unregister = secret.HostRegister(layer, mapped=True)  # registered once, outside the timed region
     walks = ("host", "gpu") if args.walk == "both" else (args.walk,)
-    dev_modes = tuple("device" if w == "host" else "device-gpu-walk" for w in walks)
+    reqs = ("host", "gpu") if args.required == "both" else (args.required,)
+    dev_modes = tuple(("device" if w == "host" else "device-gpu-walk") + ("-req" if r == "gpu" else "")
+                      for w in walks for r in reqs if r == "host" or w == "gpu")
+    if not dev_modes:
+        raise SystemExit("--required gpu needs --walk gpu or both")
     modes = dev_modes if args.index_only else dev_modes + ("host",)
     walker = None
     if args.skip_dirs or args.skip_files:
@@ -528,11 +541,16 @@ def layer_leg(args):
             an.set_layer_walker(walker if mode.endswith("+skip") else None)
             mode = mode.split("+")[0]
         st = {}
+        req = mode.endswith("-req")
+        mode = mode[:-4] if req else mode
+        if req or hasattr(an._L, "tsg_analyzer_set_tar_required"):
+            an.set_tar_required("gpu" if req else "host")
         if mode != "host" and (mode == "device-gpu-walk" or hasattr(an._L, "tsg_analyzer_set_tar_walk")):
             an.set_tar_walk("gpu" if mode == "device-gpu-walk" else "host")
         if mode != "host" and args.index_only:
             ix = an.IndexDevice(d_layer, n_bytes, stats=st)
             st["walk"] = ix.walk_stats
+            st["required_stats"] = ix.required_stats
             st["files"] = ix.n
         elif mode != "host":
             an.AnalyzeLayerDevice(d_layer, n_bytes, arena_bytes=args.arena_mb << 20, depth=args.depth, stats=st,
@@ -594,6 +612,10 @@ def layer_leg(args):
             out["index"] = {k: med([r[k] for r in res[m]]) for k in keys}
             out["index_kernel_gbps"] = n_bytes / 1e6 / out["index"]["ms_kernel"]
             out["walk"] = {k: med([r["walk"][k] for r in res[m]]) for k in last["walk"] if k != "walk"}
+            if "required_stats" in last:
+                out["required"] = {k: med([r["required_stats"][k] for r in res[m]]) for k in last["required_stats"]
+                                   if k != "mode"}
+                out["required"]["mode"] = last["required_stats"]["mode"]
         else:
             out["walk_s"] = med([r["walk_s"] for r in res[m]])
             out["wait_s"] = med([r["wait_s"] for r in res[m]])
@@ -638,7 +660,8 @@ def layers_leg(args):
     if args.fetch == "windows":
         sc.set_fetch_mode("windows", back=args.back, fwd=args.fwd, fwd_cap=args.fwd_cap)
     an.set_tar_walk("gpu")
-    modes = ("batched", "loop") if args.index_only else ("batched", "loop", "host")
+    reqs = ("", "-req") if args.required == "both" else ("-req",) if args.required == "gpu" else ("",)
+    modes = tuple(m + r for m in ("batched", "loop") for r in reqs) + (() if args.index_only else ("host",))
     unregister = []
     workers = None
     if "host" in modes:
@@ -648,15 +671,32 @@ def layers_leg(args):
 
     def step(mode):
         st = {"findings": 0}
+        req = mode.endswith("-req")
+        mode = mode[:-4] if req else mode
+        if req or hasattr(an._L, "tsg_analyzer_set_tar_required"):
+            an.set_tar_required("gpu" if req else "host")
+
+        def required_of(ixs):  # the layers' counts summed; the stage and its copies are one per pass
+            rs = [ix.required_stats for ix in ixs]
+            out = {k: sum(r[k] for r in rs) for k in ("entries", "kept", "dropped", "ask_allow", "ask_name",
+                                                      "ask_dropped", "path_bytes")}
+            shared = mode == "batched"
+            for k in ("ms_kernel", "ms_copy"):
+                out[k] = max(r[k] for r in rs) if shared else sum(r[k] for r in rs)
+            out["ms_host_sum"] = sum(r["ms_host"] for r in rs)
+            out["on_gpu_layers"] = sum(r["mode"] == "gpu" for r in rs)
+            return out
         if mode == "batched" and args.index_only:
             stats = []
-            an.IndexLayersDevice(slices, stats=stats)
+            st["required"] = required_of(an.IndexLayersDevice(slices, stats=stats))
             st["forest"] = stats[-1]
         elif mode == "loop" and args.index_only:
-            per = []
+            per, ixs = [], []
             for t, n in slices:
                 ix = an.IndexDevice(t, n)
                 per.append(ix.walk_stats)
+                ixs.append(ix)
+            st["required"] = required_of(ixs)
             st["stages"] = {k: sum(w[k] for w in per) for k in per[0] if k.startswith("ms_")}
             st["device_bytes"] = sum(w["device_bytes"] for w in per)  # allocated and freed over the image
         elif mode == "batched":
@@ -714,14 +754,17 @@ def layers_leg(args):
                "group_mb": args.group_mb, "fetch": args.fetch, "resident": args.resident,
                "ms_per_step": med(per[m]), "blocks_ms": per[m], "min_ms": min(per[m]), "max_ms": max(per[m]),
                "gbps": total / 1e6 / med(per[m]), "host_cpus": med(cpus[m]), "findings": findings[m]}
-        if m == "batched":
-            out["batched_slowest_below_loop_fastest"] = max(per["batched"]) < min(per["loop"])
+        if "required" in res[m][-1]:
+            out["required"] = {k: med([r["required"][k] for r in res[m]]) for k in res[m][-1]["required"]}
+        if m.startswith("batched"):
+            loop = "loop" + m[len("batched"):]
+            out["batched_slowest_below_loop_fastest"] = max(per[m]) < min(per[loop])
             out["forest"] = {k: med([r["forest"][k] for r in res[m]]) for k in res[m][-1]["forest"]}
             if not args.index_only:  # the share of the index time that ran beside scans
                 f = out["forest"]
                 hidden = f["index_s"] + f["scan_s"] - f["wall_s"]
                 out["index_hidden_share"] = max(0.0, min(1.0, hidden / f["index_s"])) if f["index_s"] > 0 else 0.0
-        if m == "loop" and args.index_only:
+        if m.startswith("loop") and args.index_only:
             out["stages"] = {k: med([r["stages"][k] for r in res[m]]) for k in res[m][-1]["stages"]}
             out["device_bytes_allocated"] = med([r["device_bytes"] for r in res[m]])
         line = json.dumps(out)

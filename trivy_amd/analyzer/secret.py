@@ -104,6 +104,24 @@ TAR_WALK_FALLBACKS = ("", "size field", "PAX record", "PAX size form", "cap", "n
                       "too many blocks")
 
 
+class _CTarRequiredStats(c.Structure):  # tsg_tar_required_stats (versioned)
+    _fields_ = [("struct_size", c.c_uint32), ("reserved", c.c_uint32), ("mode", c.c_uint32), ("reason", c.c_uint32)] + \
+               [(n, c.c_uint64) for n in ("entries", "kept", "dropped", "ask_allow", "ask_name", "ask_dropped",
+                                          "path_bytes")] + \
+               [(n, c.c_double) for n in ("ms_kernel", "ms_copy", "ms_host")]
+
+    def to_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n not in ("struct_size", "reserved", "mode")}
+        d["mode"] = TAR_REQUIRED_MODES[self.mode] if self.mode < len(TAR_REQUIRED_MODES) else self.mode
+        return d
+
+
+TAR_REQUIRED_STATS_SIZE_V1 = _CTarRequiredStats.ms_host.offset + c.sizeof(c.c_double)
+TAR_REQUIRED_MODES = ("host", "gpu")  # tsg_analyzer_set_tar_required
+# tsg_tar_required_stats.reason: why Required ran on the host
+TAR_REQUIRED_REASONS = ("", "setter off", "walk mode host", "skip options", "layer fell back to the host walk")
+
+
 class _CDeviceTars(c.Structure):  # tsg_device_tars (versioned)
     _fields_ = [("struct_size", c.c_uint32), ("n_layers", c.c_uint32), ("layers", c.POINTER(_CDeviceTar))]
 
@@ -170,6 +188,10 @@ def _declare(L):
         L.tsg_analyzer_get_tar_walk.argtypes = [c.c_void_p, c.POINTER(c.c_int)]
         L.tsg_tar_index_walk_stats.argtypes = [c.c_void_p, c.POINTER(_CTarWalkStats)]
         L.tsg_debug_tar_walk_last_fallback.argtypes = [c.c_void_p]
+    if hasattr(L, "tsg_analyzer_set_tar_required"):  # (absent from an older build of the library: TSG_LIB)
+        L.tsg_analyzer_set_tar_required.argtypes = [c.c_void_p, c.c_int]
+        L.tsg_analyzer_get_tar_required.argtypes = [c.c_void_p, c.POINTER(c.c_int)]
+        L.tsg_tar_index_required_stats.argtypes = [c.c_void_p, c.POINTER(_CTarRequiredStats)]
     if hasattr(L, "tsg_analyzer_index_device_tars"):  # (absent from an older build of the library: TSG_LIB)
         L.tsg_analyzer_index_device_tars.argtypes = [c.c_void_p, c.POINTER(_CDeviceTars), c.POINTER(c.c_void_p),
                                                      c.POINTER(_CDeviceTarStats), c.POINTER(_CTarForestStats),
@@ -483,6 +505,19 @@ class DeviceTarIndex:
         if self._an._L.tsg_tar_index_walk_stats(self._h, c.byref(ws)) != 0:
             raise RuntimeError("tsg_tar_index_walk_stats failed: %s" % _lib.last_error(self._an._L))
         return ws.to_dict()
+
+    @property
+    def required_stats(self) -> dict:
+        """Where this index's Required ran (tsg_tar_index_required_stats): the mode in force, the reason
+        when it was the host (TAR_REQUIRED_REASONS), what the device decided and asked, the stage's times."""
+        rs = _CTarRequiredStats()
+        rs.struct_size = TAR_REQUIRED_STATS_SIZE_V1
+        if not hasattr(self._an._L, "tsg_tar_index_required_stats"):  # an older build: the host, setter absent
+            rs.reason = 1
+            return rs.to_dict()
+        if self._an._L.tsg_tar_index_required_stats(self._h, c.byref(rs)) != 0:
+            raise RuntimeError("tsg_tar_index_required_stats failed: %s" % _lib.last_error(self._an._L))
+        return rs.to_dict()
 
     @property
     def skip_stats(self) -> dict:
@@ -829,6 +864,22 @@ class SecretAnalyzer:
         if self._L.tsg_analyzer_get_tar_walk(self._h, c.byref(m)) != 0:
             raise RuntimeError("tsg_analyzer_get_tar_walk failed: %s" % _lib.last_error(self._L))
         return TAR_WALK_MODES[m.value]
+
+    def set_tar_required(self, mode):
+        """Where the path work and Required of a resident layer's index run (tsg_analyzer_set_tar_required):
+        "host" (the default) or "gpu" (a device stage behind the GPU walk hands over only the files Required
+        keeps and what it leaves to the host; the same index).  In force only with set_tar_walk("gpu"), without
+        skip options, on a layer the GPU walk completes: DeviceTarIndex.required_stats says which ran and why."""
+        if mode not in TAR_REQUIRED_MODES:
+            raise ValueError("set_tar_required: mode must be one of %s" % (TAR_REQUIRED_MODES,))
+        if self._L.tsg_analyzer_set_tar_required(self._h, TAR_REQUIRED_MODES.index(mode)) != 0:
+            raise ValueError("tsg_analyzer_set_tar_required failed: %s" % _lib.last_error(self._L))
+
+    def tar_required(self) -> str:
+        m = c.c_int(0)
+        if self._L.tsg_analyzer_get_tar_required(self._h, c.byref(m)) != 0:
+            raise RuntimeError("tsg_analyzer_get_tar_required failed: %s" % _lib.last_error(self._L))
+        return TAR_REQUIRED_MODES[m.value]
 
     def last_tar_fallback(self) -> int:
         """tsg_tar_walk_stats.fallback of the last "gpu"-mode index call, also of one that raised."""

@@ -249,6 +249,7 @@ int tsg_analyzer_new(const tsg_scanner* s, const char* config_path, tsg_analyzer
   a->s = s;
   a->config_base = tsg::GoBase(config_path ? config_path : "");
   if (const char* w = std::getenv("TSG_TAR_WALK")) a->tar_walk.store(std::strcmp(w, "gpu") == 0 ? 1 : 0);
+  if (const char* w = std::getenv("TSG_TAR_REQUIRED")) a->tar_required.store(std::strcmp(w, "gpu") == 0 ? 1 : 0);
   *out = a;
   return 0;
 }

@@ -50,6 +50,9 @@ struct tsg_analyzer {
   // records, 1 on the GPU (TSG_TAR_WALK=gpu at creation).  Read once per index call.
   std::atomic<int> tar_walk{0};
   std::atomic<uint32_t> tar_fallback_last{0};  // tsg_debug_tar_walk_last_fallback: the last mode-1 call's
+  // tsg_analyzer_set_tar_required: 0 the path work and Required of a resident layer's index on the
+  // host, 1 on the GPU behind the GPU walk (TSG_TAR_REQUIRED=gpu at creation).  Read once per index call.
+  std::atomic<int> tar_required{0};
   // tsg_analyzer_set_tar_skip: LayerTar's skipDirs / skipFiles for every layer walk
   // (NULL: none).  Replaced under walk_mu and tar_skip_mu; a walk or an index call
   // takes a reference of its own (TarSkip()), so a background index keeps its patterns.

@@ -11,7 +11,9 @@
 // tsg_analyzer_index_device_tars takes all layers of an image: in walk mode 1
 // one forest pass (tarforest.hip) walks the chains of all of them, the host half
 // runs per layer, and a layer the pass does not complete takes the single-layer
-// path alone.
+// path alone.  With tsg_analyzer_set_tar_required mode 1 a device stage behind
+// either pass's compaction (tarrequired.hip) runs the path work and Required, and
+// the host half starts from its file records instead (IndexTarFiles).
 #include <hip/hip_runtime_api.h>
 #include <pthread.h>
 
@@ -28,6 +30,7 @@
 #include "collector.h"
 #include "parallel.h"
 #include "tar_index_host.h"
+#include "tar_required_host.h"
 #include "tarindex.h"
 #include "tsg_debug.h"
 #include "xform.h"
@@ -37,6 +40,7 @@ struct tsg_tar_index {
   uint64_t n_bytes = 0;
   tsg::TarIndexData d;
   tsg_tar_walk_stats ws{};  // tsg_tar_index_walk_stats
+  tsg_tar_required_stats rs{};  // tsg_tar_index_required_stats
 };
 
 namespace tsg {
@@ -64,7 +68,17 @@ struct TarIndexCtx {
   uint8_t* h_heads = nullptr;
   uint8_t* h_tables = nullptr;
   uint64_t cap_heads = 0, cap_tables = 0;  // bytes
+  // Required on the GPU (tsg_analyzer_set_tar_required mode 1): the stage's device buffer, its
+  // uploaded tables and the per-layer counts (pinned), its two events
+  uint8_t* d_req = nullptr;
+  uint8_t* h_req = nullptr;
+  uint64_t cap_req = 0, cap_hreq = 0;  // bytes
+  hipEvent_t ev_req[2] = {nullptr, nullptr};
   ~TarIndexCtx() {
+    if (d_req) (void)hipFree(d_req);
+    if (h_req) (void)hipHostFree(h_req);
+    for (hipEvent_t e : ev_req)
+      if (e) (void)hipEventDestroy(e);
     if (h_heads) (void)hipHostFree(h_heads);
     if (h_tables) (void)hipHostFree(h_tables);
     for (hipEvent_t e : ev)
@@ -157,6 +171,16 @@ void GiveCtx(tsg_analyzer* a, std::unique_ptr<TarIndexCtx> c) {
     c->h_tables = nullptr;
     c->cap_tables = 0;
   }
+  if (c->cap_req > kKeepBytes) {
+    (void)hipFree(c->d_req);
+    c->d_req = nullptr;
+    c->cap_req = 0;
+  }
+  if (c->cap_hreq > kKeepBytes) {
+    (void)hipHostFree(c->h_req);
+    c->h_req = nullptr;
+    c->cap_hreq = 0;
+  }
   std::lock_guard<std::mutex> g(a->tar_index->mu);
   if (a->tar_index->free.size() < 2) a->tar_index->free.push_back(std::move(c));  // (else freed here)
 }
@@ -247,12 +271,137 @@ bool Grow(uint8_t** p, uint64_t* cap, uint64_t want, bool pinned, hipError_t* e)
   return true;
 }
 
+// ---- path classify and Required on the GPU (tarrequired.h) ---------------------
+// Why an index call ran Required on the host (tsg_tar_required_stats.reason); 0: the GPU stage ran.
+enum : uint32_t { kReqUsedGpu = 0, kReqSetterOff = 1, kReqWalkHost = 2, kReqSkipOptions = 3, kReqLayerFellBack = 4 };
+uint32_t RequiredReason(const tsg_analyzer* a, int walk_mode) {
+  if (a->tar_required.load() != 1) return kReqSetterOff;
+  if (walk_mode != 1) return kReqWalkHost;
+  const std::shared_ptr<const TarSkipOpts> skip = a->TarSkip();
+  if (skip && skip->any()) return kReqSkipOptions;
+  return kReqUsedGpu;
+}
+
+// One run of the stage behind a compaction on the context's stream, and what it handed over.
+struct ReqPass {
+  const PathTable* d_path = nullptr;  // the scanner's tables in HBM (either may be NULL)
+  const SureTable* d_sure = nullptr;
+  std::string cfg;                    // the analyzer's config base
+  TarRequiredLayout L;
+  const TarRequiredCounts* counts = nullptr;  // per layer (in c->h_req)
+  const tsg_tar_file_rec* recs = nullptr;     // all layers' (in c->h_out)
+  const uint8_t* blob = nullptr;
+  uint64_t n_recs = 0, blob_bytes = 0, bad = 0;
+  double ms_kernel = 0, ms_copy = 0;
+};
+void ReqPassInit(const tsg_analyzer* a, ReqPass* R) {
+  const SecretScanner::AllowTables t = a->s->s->allow_tables();
+  R->d_path = t.dev_path;
+  R->d_sure = t.dev_path ? t.dev_sure : nullptr;
+  R->cfg = a->config_base;
+}
+// The stage over the n records at d_recs and the names at d_names, which the compaction queued on
+// c->s before this call is writing: the counts, then one copy of the file records and one of the
+// paths, into c->h_out.  Synchronises the stream twice.  keep_dec: the decisions are copied out too.
+hipError_t RequiredOnGpu(TarIndexCtx* c, ReqPass* R, const uint8_t* d_recs, const uint8_t* d_names, uint64_t n,
+                         uint64_t name_bytes, const uint64_t* rec_base, const uint64_t* name_base, uint32_t n_layers,
+                         uint32_t grid_cap, std::vector<uint8_t>* keep_dec = nullptr) {
+  hipError_t e = hipSuccess;
+  auto ok = [&](hipError_t r) {
+    if (e == hipSuccess) e = r;
+    return e == hipSuccess;
+  };
+  if (!TarRequiredPlan(n, n_layers, name_bytes, uint32_t(R->cfg.size()), &R->L)) return hipErrorInvalidValue;
+  const TarRequiredLayout& L = R->L;
+  for (hipEvent_t& v : c->ev_req)
+    if (!v) ok(hipEventCreate(&v));
+  const uint64_t cnt_bytes = uint64_t(n_layers) * sizeof(TarRequiredCounts);
+  if (!ok(e) || !Grow(&c->d_req, &c->cap_req, L.bytes, false, &e) ||
+      !Grow(&c->h_req, &c->cap_hreq, L.tables_bytes + cnt_bytes, true, &e))
+    return e;
+  TarRequiredTables(L, rec_base, name_base, R->cfg.data(), c->h_req);
+  if (!(ok(hipEventRecord(c->ev_req[0], c->s)) &&
+        ok(TarRequiredRun(L, c->h_req, d_recs, d_names, R->d_path, R->d_sure, c->d_req, grid_cap, c->s)) &&
+        ok(hipEventRecord(c->ev_req[1], c->s)) &&
+        ok(hipMemcpyAsync(c->h_req + L.tables_bytes, c->d_req + L.counts, cnt_bytes, hipMemcpyDeviceToHost, c->s)) &&
+        ok(hipStreamSynchronize(c->s))))
+    return e;
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, c->ev_req[0], c->ev_req[1]) == hipSuccess) R->ms_kernel = ms;
+  R->counts = reinterpret_cast<const TarRequiredCounts*>(c->h_req + L.tables_bytes);
+  R->n_recs = R->blob_bytes = R->bad = 0;
+  for (uint32_t k = 0; k < n_layers; k++) {
+    if (R->counts[k].rec_first != R->n_recs || R->counts[k].path_first != R->blob_bytes) return hipErrorUnknown;
+    R->n_recs += R->counts[k].records;
+    R->blob_bytes += R->counts[k].path_bytes;
+    R->bad += R->counts[k].bad;
+  }
+  if (R->n_recs > n || R->blob_bytes > L.blob_cap) return hipErrorUnknown;  // (the sums are over n decisions)
+  const uint64_t rec_bytes = (R->n_recs * sizeof(tsg_tar_file_rec) + 255) & ~uint64_t(255);
+  const double t1 = NowMs();
+  if (!Grow(&c->h_out, &c->cap_hout, rec_bytes + R->blob_bytes + 256, true, &e)) return e;
+  if ((R->n_recs == 0 || ok(hipMemcpyAsync(c->h_out, c->d_req + L.recs, R->n_recs * sizeof(tsg_tar_file_rec),
+                                           hipMemcpyDeviceToHost, c->s))) &&
+      (R->blob_bytes == 0 || ok(hipMemcpyAsync(c->h_out + rec_bytes, c->d_req + L.blob, R->blob_bytes,
+                                               hipMemcpyDeviceToHost, c->s))))
+    ok(hipStreamSynchronize(c->s));
+  if (ok(e) && keep_dec && n) {
+    keep_dec->resize(size_t(n) * 16);
+    ok(hipMemcpy(keep_dec->data(), c->d_req + L.dec, size_t(n) * 16, hipMemcpyDeviceToHost));
+  }
+  R->ms_copy = NowMs() - t1;
+  R->recs = reinterpret_cast<const tsg_tar_file_rec*>(c->h_out);
+  R->blob = c->h_out + rec_bytes;
+  return e;
+}
+
+// The host half over one layer's file records (IndexTarFiles): the index, the V1 stats of mode 1 and
+// the required stats' counts.  -1: the records contradict the blob or the counts (error set).
+int FilesToIndex(tsg_analyzer* a, const TarRequiredCounts& cnt, const tsg_tar_file_rec* recs, const uint8_t* blob,
+                 const tsg_tar_stop& stop, uint64_t n_bytes, uint64_t candidates, TarIndexData* d,
+                 tsg_device_tar_stats* st, tsg_tar_required_stats* rs) {
+  const SecretScanner* sc = a->s->s.get();
+  TarRequiredHostStats hs;
+  if (IndexTarFiles(
+          recs, cnt.records, blob, cnt.path_bytes, cnt,
+          [sc](const char* p, uint64_t len, uint64_t rules) {
+            return sc->AllowPathMasked(reinterpret_cast<const uint8_t*>(p), size_t(len), rules);
+          },
+          [sc](const char* p, uint64_t len) { return sc->AllowPath(reinterpret_cast<const uint8_t*>(p), size_t(len)); },
+          [a](const char* p, uint64_t len, int64_t size) { return RequiredPath(a, p, len, size); }, d, EntriesPar(),
+          &hs) < 0)
+    return -1;
+  if (st) {
+    const uint64_t on_chain = stop.ext_visited + cnt.ext_headers + cnt.entries;  // as EntriesToIndex counts them
+    st->tar = d->tar;
+    st->blocks = n_bytes / 512;
+    st->candidates = candidates;
+    st->off_chain = candidates > on_chain ? candidates - on_chain : 0;
+    st->block_fetches = 0;
+    st->ext_bytes = 0;
+  }
+  if (rs) {
+    rs->mode = 1;
+    rs->reason = kReqUsedGpu;
+    rs->entries = cnt.entries;
+    rs->kept = cnt.kept;
+    rs->dropped = cnt.dropped;
+    rs->ask_allow = cnt.ask_allow;
+    rs->ask_name = cnt.ask_name;
+    rs->ask_dropped = hs.ask_dropped;
+    rs->path_bytes = cnt.path_bytes;
+  }
+  return 0;
+}
+
 // The GPU half on the context's stream: 0 with *recs / *names (in c->h_out) and
 // *head filled; 1 the chain is INCOMPLETE (or the pass does not take the layer):
 // ws->fallback says why; -2 a HIP error, its text set.  n_bytes >= 512.
 int ChainOnGpu(TarIndexCtx* c, const uint8_t* dev_tar, uint64_t n_bytes, uint32_t segment_blocks, uint32_t grid_cap,
                const std::string& who, TarChainHead* head, const tsg_tar_entry_rec** recs, const uint8_t** names,
-               tsg_tar_walk_stats* ws) {
+               tsg_tar_walk_stats* ws, ReqPass* rq = nullptr) {
+  // rq != NULL: the Required stage runs behind the compaction, and what comes back is rq's file
+  // records and paths; the entry records and the names stay in HBM (*recs and *names are NULL).
   TarChainLayout L;
   if (!TarChainPlan(n_bytes, segment_blocks, &L)) {
     if (segment_blocks) {
@@ -293,7 +442,20 @@ int ChainOnGpu(TarIndexCtx* c, const uint8_t* dev_tar, uint64_t n_bytes, uint32_
     ws->name_bytes = head->name_bytes;
     ws->device_bytes = L.bytes + out_bytes;
     // (ev[0] again: the allocations above the kernel are not its time)
-    if (Grow(&c->d_out, &c->cap_out, out_bytes, false, &e) && Grow(&c->h_out, &c->cap_hout, out_bytes, true, &e) &&
+    if (rq) {
+      const uint64_t rec_base[2] = {0, head->entries}, name_base[2] = {0, head->name_bytes};
+      if (Grow(&c->d_out, &c->cap_out, out_bytes, false, &e) && ok(hipEventRecord(c->ev[0], c->s)) &&
+          ok(TarChainCompact(dev_tar, n_bytes, L, c->d_work, head->entries, head->name_bytes, c->d_out,
+                             c->d_out + rec_bytes, grid_cap, c->s)) &&
+          ok(hipEventRecord(c->ev[4], c->s)) &&
+          ok(RequiredOnGpu(c, rq, c->d_out, c->d_out + rec_bytes, head->entries, head->name_bytes, rec_base, name_base,
+                           1, grid_cap))) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, c->ev[0], c->ev[4]) == hipSuccess) ws->ms_compact = ms;
+        ws->ms_copy = rq->ms_copy;
+        ws->device_bytes += rq->L.bytes;
+      }
+    } else if (Grow(&c->d_out, &c->cap_out, out_bytes, false, &e) && Grow(&c->h_out, &c->cap_hout, out_bytes, true, &e) &&
         ok(hipEventRecord(c->ev[0], c->s)) &&
         ok(TarChainCompact(dev_tar, n_bytes, L, c->d_work, head->entries, head->name_bytes, c->d_out,
                            c->d_out + rec_bytes, grid_cap, c->s)) &&
@@ -316,8 +478,8 @@ int ChainOnGpu(TarIndexCtx* c, const uint8_t* dev_tar, uint64_t n_bytes, uint32_
     return -2;
   }
   if (incomplete) return 1;
-  *recs = reinterpret_cast<const tsg_tar_entry_rec*>(c->h_out);
-  *names = c->h_out + rec_bytes;
+  *recs = rq ? nullptr : reinterpret_cast<const tsg_tar_entry_rec*>(c->h_out);
+  *names = rq ? nullptr : c->h_out + rec_bytes;
   return 0;
 }
 
@@ -333,7 +495,8 @@ struct ForestPass {
   const uint8_t* names = nullptr;
 };
 int ForestOnGpu(TarIndexCtx* c, const void* const* ptrs, const uint64_t* n_bytes, uint32_t n, uint32_t segment_blocks,
-                uint32_t grid_cap, const std::string& who, ForestPass* P, tsg_tar_forest_stats* fs) {
+                uint32_t grid_cap, const std::string& who, ForestPass* P, tsg_tar_forest_stats* fs,
+                ReqPass* rq = nullptr) {
   TarForestLayout& L = P->L;
   if (!TarForestPlan(n_bytes, n, segment_blocks, &L)) {
     SetError(who + ": segment_blocks must be a power of two from 8 to 8192, and the layers must fit one pass");
@@ -367,7 +530,13 @@ int ForestOnGpu(TarIndexCtx* c, const void* const* ptrs, const uint64_t* n_bytes
     rec_bytes = (entries * sizeof(tsg_tar_entry_rec) + 255) & ~uint64_t(255);
     out_bytes = rec_bytes + name_bytes + 256;
     // one compaction, one copy of all records, one of all names, one synchronisation
-    if (Grow(&c->d_out, &c->cap_out, out_bytes, false, &e) && Grow(&c->h_out, &c->cap_hout, out_bytes, true, &e) &&
+    if (rq) {  // the Required stage behind the compaction: its file records and paths come back instead
+      if (Grow(&c->d_out, &c->cap_out, out_bytes, false, &e) && ok(hipEventRecord(c->ev[5], c->s)) &&
+          ok(TarForestCompact(L, c->d_work, entries, name_bytes, c->d_out, c->d_out + rec_bytes, grid_cap, c->s)) &&
+          ok(hipEventRecord(c->ev[4], c->s)) && ok(hipEventRecord(c->ev[6], c->s)))
+        ok(RequiredOnGpu(c, rq, c->d_out, c->d_out + rec_bytes, entries, name_bytes, P->rec_base.data(),
+                         P->name_base.data(), n, grid_cap));
+    } else if (Grow(&c->d_out, &c->cap_out, out_bytes, false, &e) && Grow(&c->h_out, &c->cap_hout, out_bytes, true, &e) &&
         ok(hipEventRecord(c->ev[5], c->s)) &&
         ok(TarForestCompact(L, c->d_work, entries, name_bytes, c->d_out, c->d_out + rec_bytes, grid_cap, c->s)) &&
         ok(hipEventRecord(c->ev[4], c->s)) &&
@@ -383,8 +552,10 @@ int ForestOnGpu(TarIndexCtx* c, const void* const* ptrs, const uint64_t* n_bytes
     SetError(who + ": " + hipGetErrorString(e));
     return -2;
   }
-  P->recs = reinterpret_cast<const tsg_tar_entry_rec*>(c->h_out);
-  P->names = c->h_out + rec_bytes;
+  P->recs = rq ? nullptr : reinterpret_cast<const tsg_tar_entry_rec*>(c->h_out);  // (rq: they stay in HBM)
+  P->names = rq ? nullptr : c->h_out + rec_bytes;
+  if (rq) out_bytes += rq->L.bytes;
+  if (fs && rq) fs->ms_copy += rq->ms_copy;
   if (fs) {
     float ms = 0;
     if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) fs->ms_candidates += ms;
@@ -453,6 +624,10 @@ static int IndexOneLayer(tsg_analyzer* a, const std::string& who, const uint8_t*
   tsg_tar_walk_stats ws{};
   ws.walk = forced_fallback ? 1u : uint32_t(a->tar_walk.load());
   if (forced_fallback) ws.fallback = *forced_fallback;
+  // Required on the GPU (tsg_analyzer_set_tar_required): only behind a GPU walk that completes the layer
+  tsg_tar_required_stats rs{};
+  rs.reason = RequiredReason(a, int(ws.walk));
+  if (rs.reason == kReqUsedGpu && forced_fallback) rs.reason = kReqLayerFellBack;
   if (ws.walk == 1 && !forced_fallback) {
     // The chain walk on the GPU.  A layer it does not complete falls through to the host walk below,
     // from scratch: that path alone words what is wrong with a malformed archive.
@@ -463,23 +638,37 @@ static int IndexOneLayer(tsg_analyzer* a, const std::string& who, const uint8_t*
     const tsg_tar_entry_rec* recs = nullptr;
     const uint8_t* names = nullptr;
     int rc = 0;
+    ReqPass rq;
+    bool on_gpu = false;  // the Required stage ran
     if (n_bytes < 512) {  // no complete block: the empty archive, or a truncated header
       rc = n_bytes ? 1 : 0;
       if (rc) ws.fallback = kTarTruncated;
     } else {
-      rc = ChainOnGpu(c.get(), dev_tar, n_bytes, 0, 0, who, &head, &recs, &names, &ws);
+      on_gpu = rs.reason == kReqUsedGpu;
+      if (on_gpu) ReqPassInit(a, &rq);
+      rc = ChainOnGpu(c.get(), dev_tar, n_bytes, 0, 0, who, &head, &recs, &names, &ws, on_gpu ? &rq : nullptr);
     }
     a->tar_fallback_last.store(ws.fallback);
     if (rc < 0) {
       GiveCtx(a, std::move(c));
       return -2;
     }
+    if (rc == 1 && rs.reason == kReqUsedGpu) rs.reason = kReqLayerFellBack;
     if (rc == 0) {
       const double th = NowMs();
       tsg_device_tar_stats tmp{};
       double hm[3] = {0, 0, 0};
-      rc = EntriesToIndex(a, recs, head.entries, names, head.name_bytes, head.stop, n_bytes, head.candidates, &ix->d,
-                          st ? st : &tmp, hm);
+      if (on_gpu) {
+        rc = FilesToIndex(a, rq.counts[0], rq.recs, rq.blob, head.stop, n_bytes, head.candidates, &ix->d,
+                          st ? st : &tmp, &rs);
+        rs.ms_kernel = rq.ms_kernel;
+        rs.ms_copy = rq.ms_copy;
+        rs.ms_host = NowMs() - th;
+      } else {
+        if (rs.reason == kReqUsedGpu) rs.mode = 1;  // (an archive without a block: nothing to decide)
+        rc = EntriesToIndex(a, recs, head.entries, names, head.name_bytes, head.stop, n_bytes, head.candidates, &ix->d,
+                            st ? st : &tmp, hm);
+      }
       ws.ms_host = NowMs() - th;
       GiveCtx(a, std::move(c));
       if (rc < 0) return -2;  // (records that contradict the name blob: the layer changed under the pass)
@@ -495,6 +684,7 @@ static int IndexOneLayer(tsg_analyzer* a, const std::string& who, const uint8_t*
                      hm[2], NowMs() - t0,
                      static_cast<unsigned long long>(head.entries));
       ix->ws = ws;
+      ix->rs = rs;
       *out = ix.release();
       return 0;
     }
@@ -562,6 +752,7 @@ static int IndexOneLayer(tsg_analyzer* a, const std::string& who, const uint8_t*
   if (rc < 0) return copy_failed ? -2 : -3;
   FillStats(st, ix->d, src, n_bytes, count, runs, ms_kernel, NowMs() - t0);
   ix->ws = ws;
+  ix->rs = rs;  // (mode 0: the reason says why Required ran on the host)
   *out = ix.release();
   return 0;
 }
@@ -647,7 +838,12 @@ int tsg_analyzer_index_device_tars(tsg_analyzer* a, const tsg_device_tars* t, ts
         continue;
       }
       ForestPass P;
-      if (ForestOnGpu(c.get(), ptrs.data() + first, nb.data() + first, cnt, 0, 0, who, &P, &F) < 0) {
+      ReqPass rq;  // Required on the GPU (tsg_analyzer_set_tar_required): one stage for the pass's layers
+      const uint32_t req_reason = RequiredReason(a, 1);
+      const bool on_gpu = req_reason == kReqUsedGpu;
+      if (on_gpu) ReqPassInit(a, &rq);
+      if (ForestOnGpu(c.get(), ptrs.data() + first, nb.data() + first, cnt, 0, 0, who, &P, &F, on_gpu ? &rq : nullptr) <
+          0) {
         GiveCtx(a, std::move(c));
         return -2;
       }
@@ -668,8 +864,18 @@ int tsg_analyzer_index_device_tars(tsg_analyzer* a, const tsg_device_tars* t, ts
         ix->n_bytes = nb[k];
         tsg_device_tar_stats tmp{};
         tsg_device_tar_stats* sk = st ? &st[k] : &tmp;
-        rcs[j] = EntriesToIndex(a, P.recs + P.rec_base[j], head.entries, P.names + P.name_base[j], head.name_bytes,
-                                head.stop, nb[k], head.candidates, &ix->d, sk);
+        ix->rs.reason = req_reason;
+        if (on_gpu) {
+          const TarRequiredCounts& cn = rq.counts[j];
+          rcs[j] = FilesToIndex(a, cn, rq.recs + cn.rec_first, rq.blob + cn.path_first, head.stop, nb[k],
+                                head.candidates, &ix->d, sk, &ix->rs);
+          ix->rs.ms_kernel = rq.ms_kernel;  // (the stage is shared by the pass's layers, as its copies are)
+          ix->rs.ms_copy = rq.ms_copy;
+          ix->rs.ms_host = NowMs() - tl;
+        } else {
+          rcs[j] = EntriesToIndex(a, P.recs + P.rec_base[j], head.entries, P.names + P.name_base[j], head.name_bytes,
+                                  head.stop, nb[k], head.candidates, &ix->d, sk);
+        }
         if (rcs[j] < 0) return;
         ix->ws.walk = 1;
         ix->ws.chain_entries = head.entries;
@@ -794,6 +1000,185 @@ int tsg_analyzer_get_tar_walk(const tsg_analyzer* a, int* mode) {
     return -1;
   }
   *mode = a->tar_walk.load();
+  return 0;
+}
+
+int tsg_analyzer_set_tar_required(tsg_analyzer* a, int mode) {
+  if (!a) {
+    tsg::SetError("tsg_analyzer_set_tar_required: NULL analyzer");
+    return -1;
+  }
+  if (mode != 0 && mode != 1) {
+    tsg::SetError("tsg_analyzer_set_tar_required: mode " + std::to_string(mode) + " is not 0 (host) or 1 (gpu)");
+    return -1;
+  }
+  a->tar_required.store(mode);
+  return 0;
+}
+
+int tsg_analyzer_get_tar_required(const tsg_analyzer* a, int* mode) {
+  if (!a || !mode) {
+    tsg::SetError("tsg_analyzer_get_tar_required: NULL argument");
+    return -1;
+  }
+  *mode = a->tar_required.load();
+  return 0;
+}
+
+int tsg_tar_index_required_stats(const tsg_tar_index* ix, tsg_tar_required_stats* out) {
+  if (!ix || !out) {
+    tsg::SetError("tsg_tar_index_required_stats: NULL argument");
+    return -1;
+  }
+  if (out->struct_size != TSG_TAR_REQUIRED_STATS_SIZE_V1) {
+    tsg::SetError("tsg_tar_index_required_stats: tsg_tar_required_stats.struct_size " +
+                  std::to_string(out->struct_size) + " is not a size this library knows (v1 = " +
+                  std::to_string(TSG_TAR_REQUIRED_STATS_SIZE_V1) + ")");
+    return -1;
+  }
+  *out = ix->rs;
+  out->struct_size = TSG_TAR_REQUIRED_STATS_SIZE_V1;
+  out->reserved = 0;
+  return 0;
+}
+
+int tsg_debug_tar_required_tables(const tsg_analyzer* a, void* path_table_out, uint64_t path_cap, void* sure_table_out,
+                                  uint64_t sure_cap, uint32_t* have_out) {
+  using namespace tsg;
+  if (!a || !have_out || (path_cap && !path_table_out) || (sure_cap && !sure_table_out)) {
+    SetError("tsg_debug_tar_required_tables: NULL argument");
+    return -1;
+  }
+  const SecretScanner::AllowTables t = a->s->s->allow_tables();
+  *have_out = 0;
+  if (t.host_path) {
+    if (path_cap < sizeof(PathTable)) {
+      SetError("tsg_debug_tar_required_tables: the path table takes " + std::to_string(sizeof(PathTable)) + " bytes");
+      return -1;
+    }
+    std::memcpy(path_table_out, t.host_path, sizeof(PathTable));
+    *have_out |= 1u;
+  }
+  if (t.host_path && t.host_sure) {
+    if (sure_cap < sizeof(SureTable)) {
+      SetError("tsg_debug_tar_required_tables: the sure table takes " + std::to_string(sizeof(SureTable)) + " bytes");
+      return -1;
+    }
+    std::memcpy(sure_table_out, t.host_sure, sizeof(SureTable));
+    *have_out |= 2u;
+  }
+  return 0;
+}
+
+int tsg_debug_tar_required(tsg_analyzer* a, const void* records, uint64_t n_records, const uint8_t* names,
+                           uint64_t name_bytes, const uint64_t* rec_base, const uint64_t* name_base, uint32_t n_layers,
+                           uint32_t grid_cap, uint8_t* verdicts_out, void* file_recs_out, uint64_t rec_cap,
+                           uint64_t* n_file_recs, uint8_t* blob_out, uint64_t blob_cap, uint64_t* blob_bytes,
+                           uint64_t* counts_out) {
+  using namespace tsg;
+  const std::string who = "tsg_debug_tar_required";
+  if (!a || !rec_base || !name_base || n_layers == 0 || !n_file_recs || !blob_bytes || !counts_out ||
+      (n_records && (!records || !verdicts_out)) || (name_bytes && !names) || (rec_cap && !file_recs_out) ||
+      (blob_cap && !blob_out) || n_records >= (uint64_t(1) << 31)) {
+    SetError(who + ": NULL argument, no layer, or too many records");
+    return -2;
+  }
+  // the table the stage searches: ascending, from (0, 0) to (n_records, name_bytes)
+  bool rows_ok = rec_base[0] == 0 && name_base[0] == 0 && rec_base[n_layers] == n_records &&
+                 name_base[n_layers] == name_bytes;
+  for (uint32_t k = 0; rows_ok && k < n_layers; k++)
+    rows_ok = rec_base[k] <= rec_base[k + 1] && name_base[k] <= name_base[k + 1];
+  if (!rows_ok) {
+    SetError(who + ": the layer table does not ascend from (0, 0) to (n_records, name_bytes)");
+    return -2;
+  }
+  *n_file_recs = *blob_bytes = 0;
+  const int device = a->s->s->device();
+  if (device < 0) {
+    SetError(who + ": no GPU engine bound to this analyzer's scanner");
+    return -2;
+  }
+  TarIndexCtx c;
+  uint8_t* d_in = nullptr;
+  const uint64_t rec_bytes = (n_records * sizeof(tsg_tar_entry_rec) + 255) & ~uint64_t(255);
+  hipError_t e = hipSetDevice(device);
+  auto ok = [&](hipError_t r) {
+    if (e == hipSuccess) e = r;
+    return e == hipSuccess;
+  };
+  ReqPass R;
+  ReqPassInit(a, &R);
+  std::vector<uint8_t> dec;
+  if (ok(e) && ok(hipStreamCreateWithFlags(&c.s, hipStreamNonBlocking)) &&
+      ok(hipMalloc(reinterpret_cast<void**>(&d_in), rec_bytes + name_bytes + 256)) &&
+      (n_records == 0 || ok(hipMemcpy(d_in, records, n_records * sizeof(tsg_tar_entry_rec), hipMemcpyHostToDevice))) &&
+      (name_bytes == 0 || ok(hipMemcpy(d_in + rec_bytes, names, name_bytes, hipMemcpyHostToDevice))))
+    ok(RequiredOnGpu(&c, &R, d_in, d_in + rec_bytes, n_records, name_bytes, rec_base, name_base, n_layers, grid_cap, &dec));
+  if (c.s) (void)hipStreamSynchronize(c.s);
+  if (d_in) (void)hipFree(d_in);
+  if (e != hipSuccess) {
+    SetError(who + ": " + hipGetErrorString(e));
+    return -2;
+  }
+  for (uint64_t i = 0; i < n_records; i++) verdicts_out[i] = dec[size_t(i) * 16 + 12];
+  std::memcpy(counts_out, R.counts, size_t(n_layers) * sizeof(TarRequiredCounts));
+  *n_file_recs = R.n_recs;
+  *blob_bytes = R.blob_bytes;
+  if (R.n_recs > rec_cap || R.blob_bytes > blob_cap) {
+    SetError(who + ": the output buffers are too small");
+    return -3;
+  }
+  if (R.n_recs) std::memcpy(file_recs_out, R.recs, size_t(R.n_recs) * sizeof(tsg_tar_file_rec));
+  if (R.blob_bytes) std::memcpy(blob_out, R.blob, size_t(R.blob_bytes));
+  if (R.bad) {
+    SetError(who + ": " + std::to_string(R.bad) + " record(s) have their name outside their layer's name blob");
+    return -4;
+  }
+  return 0;
+}
+
+int tsg_debug_index_tar_files(tsg_analyzer* a, const void* file_recs, uint64_t n_recs, const uint8_t* blob,
+                              uint64_t blob_bytes, const uint64_t* counts, const uint64_t* stop, uint64_t n_bytes,
+                              uint64_t candidates_given, tsg_tar_index** out, tsg_device_tar_stats* st) {
+  using namespace tsg;
+  const char* who = "tsg_debug_index_tar_files";
+  if (out) *out = nullptr;
+  if (!a || !out || !stop || !counts || (n_recs && !file_recs) || (blob_bytes && !blob)) {
+    SetError(std::string(who) + ": NULL argument");
+    return -1;
+  }
+  if (!StatsSizeOk(st, who)) return -1;
+  if (stop[0] != kTarStopEnd) {
+    SetError(std::string(who) + ": the stop is not END (an INCOMPLETE chain is walked by the host walk)");
+    return -1;
+  }
+  const double t0 = NowMs();
+  tsg_tar_stop sp{};
+  sp.kind = uint32_t(stop[0]);
+  sp.reason = uint32_t(stop[1]);
+  sp.offset = stop[2];
+  sp.ext_visited = stop[3];
+  TarRequiredCounts cnt;
+  std::memcpy(&cnt, counts, sizeof(cnt));
+  if (cnt.records != n_recs || cnt.path_bytes != blob_bytes) {
+    SetError(std::string(who) + ": the counts contradict the file records");
+    return -1;
+  }
+  std::unique_ptr<tsg_tar_index> ix(new tsg_tar_index());
+  ix->n_bytes = n_bytes;
+  tsg_device_tar_stats tmp{};
+  if (FilesToIndex(a, cnt, static_cast<const tsg_tar_file_rec*>(file_recs), blob, sp, n_bytes, candidates_given, &ix->d,
+                   st ? st : &tmp, &ix->rs) < 0)
+    return -1;
+  ix->rs.ms_host = NowMs() - t0;
+  if (st) {
+    st->kernel_runs = 0;
+    st->ms_kernel = 0;
+    st->ms_total = NowMs() - t0;
+  }
+  ix->ws.walk = 1;
+  ix->ws.chain_entries = cnt.entries;
+  *out = ix.release();
   return 0;
 }
 
@@ -992,6 +1377,7 @@ int tsg_debug_index_tar_records(tsg_analyzer* a, const uint8_t* host_tar, uint64
   ix->n_bytes = n_bytes;
   if (WalkRecords(a, src, n_bytes, &ix->d) < 0) return src.failed() ? -2 : -3;
   FillStats(st, ix->d, src, n_bytes, n_records, 0, 0, NowMs() - t0);
+  ix->rs.reason = std::max<uint32_t>(RequiredReason(a, 0), kReqSetterOff);
   *out = ix.release();
   return 0;
 }
@@ -1091,6 +1477,7 @@ int tsg_debug_index_tar_entries(tsg_analyzer* a, const void* records, uint64_t n
   ix->ws.walk = 1;
   ix->ws.chain_entries = n_records;
   ix->ws.name_bytes = name_bytes;
+  ix->rs.reason = std::max<uint32_t>(RequiredReason(a, 1), kReqSetterOff);  // (this hook is the host half)
   *out = ix.release();
   return 0;
 }

@@ -56,6 +56,15 @@ struct SureTable {
   uint32_t words;         // 0: no exact form (or the literals do not fit): nothing is surely allowed
 };
 constexpr uint64_t kSureMaxPath = 4096;
+
+// One step of either shift-and for word w and byte c, shared by path_filter_kernel, its host
+// model and the resident layers' Required stage (tarrequired.hip).  The prefilter's table is
+// indexed by the ASCII-lowered byte.  The exact one leaves a literal at its last position (a
+// carry into the next literal's first position would be a start the regex does not have -- a
+// ^ literal starts at offset 0 only).
+#define TSG_PATH_STEP(D, w, c, T_B, T_S) ((((D) << 1) | (T_S)[w]) & (T_B)[c][w])
+#define TSG_SURE_STEP(D, w, c, first, T_B, T_S, T_S0, T_E, T_EZ) \
+  ((((D) & ~((T_E)[w] | (T_EZ)[w])) << 1 | (T_S)[w] | ((first) ? (T_S0)[w] : 0)) & (T_B)[c][w])
 struct SureLit {          // one exact literal: per position the byte(s) it accepts
   std::vector<std::pair<uint8_t, uint8_t>> pos;
   bool begin = false, end = false;
@@ -104,6 +113,9 @@ class PathFilter {
   };
   void SetSureTable(const SureTable& t);  // before the first Submit; a table with words = 0 is ignored
   bool has_sure() const { return d_sure_ != nullptr; }
+  // The two tables in HBM, for kernels outside this class (tarrequired.hip); d_sure() is NULL without one.
+  const PathTable* d_table() const { return d_table_; }
+  const SureTable* d_sure() const { return d_sure_; }
   bool Submit(const uint8_t* d_paths, const uint64_t* d_off, const uint8_t* h_paths, const uint64_t* h_off,
               uint32_t n, bool want_skip, Pending* p, std::string* err);
   bool Finish(Pending* p, std::vector<PathHit>* out, std::string* err);

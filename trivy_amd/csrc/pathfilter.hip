@@ -59,12 +59,6 @@ bool BuildSureTable(const std::vector<SureLit>& lits, SureTable* t) {
   return true;
 }
 
-// One step of the exact shift-and: the state leaves a literal at its last
-// position (a carry into the next literal's first position would be a start
-// the regex does not have -- a ^ literal starts at offset 0 only).
-#define TSG_SURE_STEP(D, w, c, first, T_B, T_S, T_S0, T_E, T_EZ) \
-  ((((D) & ~((T_E)[w] | (T_EZ)[w])) << 1 | (T_S)[w] | ((first) ? (T_S0)[w] : 0)) & (T_B)[c][w])
-
 bool SureAllowHost(const SureTable& t, const uint8_t* p, uint64_t n) {
   if (t.words == 0 || n == 0 || n > kSureMaxPath) return false;
   uint64_t D[4] = {0, 0, 0, 0}, H = 0;
@@ -137,7 +131,7 @@ __global__ __launch_bounds__(kPathThreads) void path_filter_kernel(const uint8_t
         const uint32_t c = r + ((r - 'A') < 26u ? 32u : 0u);
 #pragma unroll
         for (int w = 0; w < 4; w++) {
-          D[w] = ((D[w] << 1) | S[w]) & sB[c][w];
+          D[w] = TSG_PATH_STEP(D[w], w, c, sB, S);
           H[w] |= D[w] & E[w];
         }
         if (kSure) {

@@ -391,6 +391,30 @@ class SecretScanner {
   bool BuildSureAllow(SureTable* t) const;
   // Global.AllowPath (scanner.go:57-59)
   bool AllowPath(const uint8_t* p, size_t n) const;
+  // The allow-path prefilter's tables (pathfilter.h) for a stage outside the scan (tarrequired.hip):
+  // the host's copies, and the ones the path filter holds in HBM.  host_path is NULL when the rules
+  // have no usable table (more than 64 rules, a rule without a usable literal, TSG_GPU_ALLOW_PATH=0),
+  // host_sure when no rule has an exact form (or TSG_GPU_SKIP_ALLOWED=0); the dev_ pointers are NULL
+  // without a GPU engine too.
+  struct AllowTables {
+    const PathTable* host_path = nullptr;
+    const SureTable* host_sure = nullptr;
+    const PathTable* dev_path = nullptr;
+    const SureTable* dev_sure = nullptr;
+  };
+  AllowTables allow_tables() const {
+    AllowTables t;
+    t.host_path = host_path_table_.get();
+    t.host_sure = host_sure_table_.get();
+    if (path_filter_) {
+      t.dev_path = path_filter_->d_table();
+      t.dev_sure = path_filter_->d_sure();
+    }
+    return t;
+  }
+  // AllowPath for an ASCII path of which `lit_rules` are known to be the rules whose PathTable
+  // literal it holds: only those run, exactly.
+  bool AllowPathMasked(const uint8_t* p, size_t n, uint64_t lit_rules) const { return AllowPathRules(p, n, lit_rules); }
 
   const std::vector<RuleSpec>& rules() const { return rules_; }
   const CompiledRules& compiled() const { return cr_; }
@@ -475,6 +499,8 @@ class SecretScanner {
   bool AllowPathRules(const uint8_t* p, size_t n, uint64_t lit_rules) const;
   // GPU allow-path prefilter (pathfilter.h): built when every path rule has usable literals
   std::unique_ptr<PathFilter> path_filter_;
+  std::unique_ptr<PathTable> host_path_table_;  // allow_tables()
+  std::unique_ptr<SureTable> host_sure_table_;
   bool gpu_skip_allowed_ = false;  // the sure table is on the GPU and TSG_GPU_SKIP_ALLOWED is not 0
   std::unique_ptr<FindingMaterializer> mat_;  // GPU findings of HBM-resident batches
   std::atomic<int> gpu_findings_{0};

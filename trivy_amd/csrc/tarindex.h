@@ -12,6 +12,7 @@
 
 #include "tarchain.h"
 #include "tarforest.h"
+#include "tarrequired.h"
 
 namespace tsg {
 
@@ -93,5 +94,23 @@ hipError_t TarForestWalk(const TarForestLayout& L, const uint8_t* h_tables, uint
 // of the heads' name_bytes) of all layers, layer after layer; nothing is written past either.
 hipError_t TarForestCompact(const TarForestLayout& L, const uint8_t* d_work, uint64_t n_entries, uint64_t name_bytes,
                             uint8_t* d_records, uint8_t* d_names, uint32_t grid_cap, hipStream_t s);
+
+// ---- path classify and Required on the GPU (tarrequired.hip; the contract: tarrequired.h) ----
+struct PathTable;  // pathfilter.h
+struct SureTable;
+// The stage's one device buffer for n entries (below 2^31) of n_layers layers (at least one) whose
+// names take name_bytes, with a config base of cfg_len bytes; false: a count out of range.
+bool TarRequiredPlan(uint64_t n, uint32_t n_layers, uint64_t name_bytes, uint32_t cfg_len, TarRequiredLayout* L);
+// The tables of a planned stage into h_tables (L.tables_bytes bytes, host memory): n_layers + 1 record
+// and name bases, the last pair (n, name_bytes), and the config base.
+void TarRequiredTables(const TarRequiredLayout& L, const uint64_t* rec_base, const uint64_t* name_base, const char* cfg,
+                       uint8_t* h_tables);
+// The stage over d_records (64 B each, 16-B aligned) and d_names, as the compaction on the same stream
+// wrote them: afterwards d_req (L.bytes, 256-B aligned) holds a TarRequiredCounts per layer at L.counts,
+// the file records at L.recs and the path blob at L.blob.  d_path / d_sure: the scanner's tables in HBM
+// (SecretScanner::allow_tables), either may be NULL.  h_tables stays valid until the stream has passed the upload.
+hipError_t TarRequiredRun(const TarRequiredLayout& L, const uint8_t* h_tables, const uint8_t* d_records,
+                          const uint8_t* d_names, const PathTable* d_path, const SureTable* d_sure, uint8_t* d_req,
+                          uint32_t grid_cap, hipStream_t s);
 
 }  // namespace tsg

@@ -374,8 +374,9 @@ int tsg_analyzer_get_tar_required(const tsg_analyzer* a, int* mode);
 
 /* How an index's Required ran (versioned, struct_size first).  mode: the one in force
  * for this index (1: the device stage ran); reason, when it is 0: 1 the setter is off,
- * 2 walk mode 0, 3 skip options are set, 4 the GPU walk did not complete the layer
- * (reason 0: the stage ran).  Of the layer's `entries` the device kept `kept` files,
+ * 2 walk mode 0, 3 skip options are set, 4 the GPU walk did not complete the layer,
+ * 5 (only with tsg_analyzer_set_tar_required_skip mode 1) a name the device does not
+ * clean was a skipped directory (reason 0: the stage ran).  Of the layer's `entries` the device kept `kept` files,
  * dropped `dropped` by Required, and asked the host about `ask_allow` (the exact allow
  * rules) and `ask_name` (clean, classify, Required); ask_dropped: asked entries the
  * host then dropped; path_bytes: the path blob handed over.  ms_kernel: the stage (HIP
@@ -390,6 +391,53 @@ typedef struct tsg_tar_required_stats {
 #define TSG_TAR_REQUIRED_STATS_SIZE_V1 ((uint32_t)(offsetof(tsg_tar_required_stats, ms_host) + sizeof(double)))
 /* -1: NULL argument or an unknown struct_size. */
 int tsg_tar_index_required_stats(const tsg_tar_index* ix, tsg_tar_required_stats* out);
+
+/* LayerTar's skip options in that device stage.  Mode 0, host (the
+ * default): with tsg_analyzer_set_tar_skip options set the stage gives way to the host
+ * half (tsg_tar_required_stats.reason 3), as described above.  Mode 1, gpu (opt-in):
+ * the stage honours the options itself when every pattern, as tsg_analyzer_set_tar_skip
+ * received it, has one of four forms -- "L" (the path equals L), "**" "/L" (the path
+ * is L or ends with "/" + L), "L/" "**" (the path is L or begins with L + "/"),
+ * "**" "/" "*S" (the base name ends with S) -- with L a non-empty ASCII literal of at most
+ * 255 bytes without * ? [ ] { } \ and without an empty, "." or ".." element, S such a
+ * literal without '/'; at most 32 directory patterns, 32 file patterns and 2 KiB of
+ * literals.  Three more kernels then mark the directories a pattern matches, the
+ * regular files a pattern matches, and the regular files that lie under a directory
+ * recorded earlier in the same layer (tar.go's underSkippedDir); the index holds only
+ * what survives skip-files, under-skipped-dir and Required, and the index, the stats
+ * and the results are those of the host half with the same options.  In force when
+ * tsg_analyzer_set_tar_required is 1, the walk mode is 1, the GPU walk completed the
+ * layer, options are set and every pattern is taken; with any other pattern the whole
+ * option set goes to the host half (reason 3 stays).  A layer in which a name the
+ * device does not clean is a skipped directory is indexed by the host half alone
+ * (tsg_tar_required_stats.reason 5).  Without options the switch has no effect.
+ * TSG_TAR_REQUIRED_SKIP=gpu (or host) in the environment sets the initial mode of
+ * analyzers made afterwards.  -1: NULL analyzer or another mode (the text names it). */
+int tsg_analyzer_set_tar_required_skip(tsg_analyzer* a, int mode);
+int tsg_analyzer_get_tar_required_skip(const tsg_analyzer* a, int* mode);
+
+/* How an index's skip options were honoured (versioned, struct_size first).  mode: the
+ * switch when the index was made; reason: 0 the device stage honoured them, 1 the
+ * switch is off, 2 no options are set, 3 a pattern (or the set) is outside what the
+ * device takes, 4 the Required stage did not run (tsg_tar_required_stats.reason says
+ * why), 5 a name the device does not clean was a skipped directory: the host half
+ * indexed the layer.  dir_patterns, file_patterns: the options; skipped_dirs,
+ * skipped_files, under_skipped_dir: tsg_tar_index_skip_stats' counts, whichever half
+ * produced them; table_slots: the 16-B slots of the recorded directories' table (0:
+ * no directory was recorded, two kernels did not run); ms_kernel: the stage's three
+ * kernels (HIP events; shared by the layers of one tsg_analyzer_index_device_tars
+ * pass, as table_slots is). */
+typedef struct tsg_tar_required_skip_stats {
+  uint32_t struct_size, reserved;
+  uint32_t mode, reason;
+  uint32_t dir_patterns, file_patterns;
+  uint64_t skipped_dirs, skipped_files, under_skipped_dir, table_slots;
+  double ms_kernel;
+} tsg_tar_required_skip_stats;
+#define TSG_TAR_REQUIRED_SKIP_STATS_SIZE_V1 \
+  ((uint32_t)(offsetof(tsg_tar_required_skip_stats, ms_kernel) + sizeof(double)))
+/* -1: NULL argument or an unknown struct_size. */
+int tsg_tar_index_required_skip_stats(const tsg_tar_index* ix, tsg_tar_required_skip_stats* out);
 
 /* All layers of an image resident in HBM, indexed by one call.  The
  * layers may be separate allocations or 512-B-aligned ranges of one buffer (as inside

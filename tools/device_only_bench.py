@@ -55,6 +55,12 @@ Required of a GPU-walked layer run (SecretAnalyzer.set_tar_required).  gpu and b
 ending in "-req", in the same interleaved blocks; with --index-only their lines carry the stage's
 counts and times ("required").
 
+--required-skip host|gpu|both (with --skip-dirs / --skip-files and --required gpu|both): whether the
+GPU's Required stage honours the skip options itself (SecretAnalyzer.set_tar_required_skip).  gpu
+and both add the modes "...-req+skip@gpu" (--layer) or "...-req@gpu" (--layers, where the options
+then hold for every mode), in the same interleaved blocks; with --index-only their lines carry the
+skip stage's counts, its table size and its kernel time ("required_skip").
+
 Usage: python tools/device_only_bench.py [--gb 4] [--steps 20] [--warmup 5] [--depth 3]
                                          [--analyze [--resident split]] [--layer [--layer-gb 4]]
                                          [--layers N [--layer-mb 2] [--group-mb 1024] [--index-only]]
@@ -111,6 +117,10 @@ def main():
     ap.add_argument("--skip-dirs", default="", help="--layer: LayerTar skipDirs patterns, comma-separated; every mode "
                     "then also runs with the options set (mode name + \"+skip\"), in the same interleaved blocks")
     ap.add_argument("--skip-files", default="", help="--layer: LayerTar skipFiles patterns, comma-separated")
+    ap.add_argument("--required-skip", choices=("host", "gpu", "both"), default="host",
+                    help="with skip options and --required gpu|both: whether the GPU's Required stage honours them "
+                         "(SecretAnalyzer.set_tar_required_skip); gpu and both add the modes ...-req+skip@gpu, and "
+                         "--layers (where the options then hold for every mode) ...-req@gpu")
     ap.add_argument("--fwd", type=int, default=None)
     ap.add_argument("--fwd-cap", type=int, default=None)
     ap.add_argument("--back", type=int, default=None)
@@ -535,8 +545,16 @@ def layer_leg(args):
         walker = NewLayerTar(Option(SkipFiles=[p for p in args.skip_files.split(",") if p],
                                     SkipDirs=[p for p in args.skip_dirs.split(",") if p]))
         modes = tuple(m + v for m in modes for v in ("", "+skip"))
+        if args.required_skip != "host":  # the switch on, beside (both) or instead of (gpu) the switch off
+            modes = tuple(x for m in modes for x in (
+                ((m, m + "@gpu") if args.required_skip == "both" else (m + "@gpu",))
+                if m.endswith("-req+skip") else (m,)))
 
     def step(mode):
+        skip_gpu = mode.endswith("@gpu")
+        mode = mode[:-4] if skip_gpu else mode
+        if skip_gpu or hasattr(an._L, "tsg_analyzer_set_tar_required_skip"):
+            an.set_tar_required_skip("gpu" if skip_gpu else "host")
         if walker is not None:
             an.set_layer_walker(walker if mode.endswith("+skip") else None)
             mode = mode.split("+")[0]
@@ -551,6 +569,7 @@ def layer_leg(args):
             ix = an.IndexDevice(d_layer, n_bytes, stats=st)
             st["walk"] = ix.walk_stats
             st["required_stats"] = ix.required_stats
+            st["required_skip_stats"] = ix.required_skip_stats
             st["files"] = ix.n
         elif mode != "host":
             an.AnalyzeLayerDevice(d_layer, n_bytes, arena_bytes=args.arena_mb << 20, depth=args.depth, stats=st,
@@ -586,7 +605,7 @@ def layer_leg(args):
     if not args.index_only:
         findings = {m: res[m][-1]["scan_findings"] for m in modes}
         for v in ("", "+skip"):  # every mode finds the same, with the options and without
-            assert len({f for m, f in findings.items() if m.endswith("+skip") == bool(v)}) <= 1, findings
+            assert len({f for m, f in findings.items() if ("+skip" in m) == bool(v)}) <= 1, findings
 
     def med(xs):
         return float(statistics.median(xs))
@@ -598,8 +617,8 @@ def layer_leg(args):
         out = {"tool": "device_only_bench --layer", "mode": m, "fetch": args.fetch, "resident": args.resident,
                "format": args.layer_format, "index_only": args.index_only,
                "gb": n_bytes / 1e9, "steps": args.steps, "block": args.block, "depth": args.depth,
-               "arena_mb": args.arena_mb, "ms_per_step": med(per[m]), "blocks_ms": per[m],
-               "gbps": n_bytes / 1e6 / med(per[m]), "host_cpus": med(cpus[m])}
+               "arena_mb": args.arena_mb, "ms_per_step": med(per[m]), "blocks_ms": per[m], "min_ms": min(per[m]),
+               "max_ms": max(per[m]), "gbps": n_bytes / 1e6 / med(per[m]), "host_cpus": med(cpus[m])}
         if not args.index_only:
             out["findings"] = int(findings[m])
         if walker is not None:
@@ -610,12 +629,18 @@ def layer_leg(args):
             keys = ("ms_kernel", "ms_total", "blocks", "candidates", "off_chain", "block_fetches", "ext_bytes",
                     "kernel_runs", "entries", "regular", "required", "files")
             out["index"] = {k: med([r[k] for r in res[m]]) for k in keys}
+            out["index"]["ms_total_min"] = min(r["ms_total"] for r in res[m])
+            out["index"]["ms_total_max"] = max(r["ms_total"] for r in res[m])
             out["index_kernel_gbps"] = n_bytes / 1e6 / out["index"]["ms_kernel"]
             out["walk"] = {k: med([r["walk"][k] for r in res[m]]) for k in last["walk"] if k != "walk"}
             if "required_stats" in last:
                 out["required"] = {k: med([r["required_stats"][k] for r in res[m]]) for k in last["required_stats"]
                                    if k != "mode"}
                 out["required"]["mode"] = last["required_stats"]["mode"]
+            if "required_skip_stats" in last:
+                out["required_skip"] = {k: med([r["required_skip_stats"][k] for r in res[m]])
+                                        for k in last["required_skip_stats"] if k != "mode"}
+                out["required_skip"]["mode"] = last["required_skip_stats"]["mode"]
         else:
             out["walk_s"] = med([r["walk_s"] for r in res[m]])
             out["wait_s"] = med([r["wait_s"] for r in res[m]])
@@ -662,6 +687,13 @@ def layers_leg(args):
     an.set_tar_walk("gpu")
     reqs = ("", "-req") if args.required == "both" else ("-req",) if args.required == "gpu" else ("",)
     modes = tuple(m + r for m in ("batched", "loop") for r in reqs) + (() if args.index_only else ("host",))
+    if args.skip_dirs or args.skip_files:  # the options hold for every mode of this leg
+        from trivy_amd.walker import NewLayerTar, Option
+        an.set_layer_walker(NewLayerTar(Option(SkipFiles=[p for p in args.skip_files.split(",") if p],
+                                               SkipDirs=[p for p in args.skip_dirs.split(",") if p])))
+        if args.required_skip != "host":
+            modes = tuple(x for m in modes for x in (
+                ((m, m + "@gpu") if args.required_skip == "both" else (m + "@gpu",)) if m.endswith("-req") else (m,)))
     unregister = []
     workers = None
     if "host" in modes:
@@ -671,6 +703,10 @@ def layers_leg(args):
 
     def step(mode):
         st = {"findings": 0}
+        skip_gpu = mode.endswith("@gpu")
+        mode = mode[:-4] if skip_gpu else mode
+        if skip_gpu or hasattr(an._L, "tsg_analyzer_set_tar_required_skip"):
+            an.set_tar_required_skip("gpu" if skip_gpu else "host")
         req = mode.endswith("-req")
         mode = mode[:-4] if req else mode
         if req or hasattr(an._L, "tsg_analyzer_set_tar_required"):
@@ -685,6 +721,12 @@ def layers_leg(args):
                 out[k] = max(r[k] for r in rs) if shared else sum(r[k] for r in rs)
             out["ms_host_sum"] = sum(r["ms_host"] for r in rs)
             out["on_gpu_layers"] = sum(r["mode"] == "gpu" for r in rs)
+            ss = [ix.required_skip_stats for ix in ixs]
+            for k in ("skipped_dirs", "skipped_files", "under_skipped_dir"):
+                out[k] = sum(x[k] for x in ss)
+            out["skip_on_gpu_layers"] = sum(x["reason"] == 0 for x in ss)
+            out["skip_table_slots"] = max(x["table_slots"] for x in ss)
+            out["skip_ms_kernel"] = max(x["ms_kernel"] for x in ss) if shared else sum(x["ms_kernel"] for x in ss)
             return out
         if mode == "batched" and args.index_only:
             stats = []

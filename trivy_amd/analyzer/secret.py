@@ -119,7 +119,26 @@ class _CTarRequiredStats(c.Structure):  # tsg_tar_required_stats (versioned)
 TAR_REQUIRED_STATS_SIZE_V1 = _CTarRequiredStats.ms_host.offset + c.sizeof(c.c_double)
 TAR_REQUIRED_MODES = ("host", "gpu")  # tsg_analyzer_set_tar_required
 # tsg_tar_required_stats.reason: why Required ran on the host
-TAR_REQUIRED_REASONS = ("", "setter off", "walk mode host", "skip options", "layer fell back to the host walk")
+TAR_REQUIRED_REASONS = ("", "setter off", "walk mode host", "skip options", "layer fell back to the host walk",
+                        "an asked name was a skipped directory")
+
+
+class _CTarRequiredSkipStats(c.Structure):  # tsg_tar_required_skip_stats (versioned)
+    _fields_ = [("struct_size", c.c_uint32), ("reserved", c.c_uint32), ("mode", c.c_uint32), ("reason", c.c_uint32),
+                ("dir_patterns", c.c_uint32), ("file_patterns", c.c_uint32)] + \
+               [(n, c.c_uint64) for n in ("skipped_dirs", "skipped_files", "under_skipped_dir", "table_slots")] + \
+               [("ms_kernel", c.c_double)]
+
+    def to_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n not in ("struct_size", "reserved", "mode")}
+        d["mode"] = TAR_REQUIRED_MODES[self.mode] if self.mode < len(TAR_REQUIRED_MODES) else self.mode
+        return d
+
+
+TAR_REQUIRED_SKIP_STATS_SIZE_V1 = _CTarRequiredSkipStats.ms_kernel.offset + c.sizeof(c.c_double)
+# tsg_tar_required_skip_stats.reason: why the device stage did not honour the skip options
+TAR_REQUIRED_SKIP_REASONS = ("", "setter off", "no skip options", "patterns unsupported",
+                             "the required stage did not run", "an asked name was a skipped directory")
 
 
 class _CDeviceTars(c.Structure):  # tsg_device_tars (versioned)
@@ -192,6 +211,10 @@ def _declare(L):
         L.tsg_analyzer_set_tar_required.argtypes = [c.c_void_p, c.c_int]
         L.tsg_analyzer_get_tar_required.argtypes = [c.c_void_p, c.POINTER(c.c_int)]
         L.tsg_tar_index_required_stats.argtypes = [c.c_void_p, c.POINTER(_CTarRequiredStats)]
+    if hasattr(L, "tsg_analyzer_set_tar_required_skip"):  # (absent from an older build of the library: TSG_LIB)
+        L.tsg_analyzer_set_tar_required_skip.argtypes = [c.c_void_p, c.c_int]
+        L.tsg_analyzer_get_tar_required_skip.argtypes = [c.c_void_p, c.POINTER(c.c_int)]
+        L.tsg_tar_index_required_skip_stats.argtypes = [c.c_void_p, c.POINTER(_CTarRequiredSkipStats)]
     if hasattr(L, "tsg_analyzer_index_device_tars"):  # (absent from an older build of the library: TSG_LIB)
         L.tsg_analyzer_index_device_tars.argtypes = [c.c_void_p, c.POINTER(_CDeviceTars), c.POINTER(c.c_void_p),
                                                      c.POINTER(_CDeviceTarStats), c.POINTER(_CTarForestStats),
@@ -518,6 +541,20 @@ class DeviceTarIndex:
         if self._an._L.tsg_tar_index_required_stats(self._h, c.byref(rs)) != 0:
             raise RuntimeError("tsg_tar_index_required_stats failed: %s" % _lib.last_error(self._an._L))
         return rs.to_dict()
+
+    @property
+    def required_skip_stats(self) -> dict:
+        """How this index's skip options were honoured (tsg_tar_index_required_skip_stats): the switch, the
+        reason when it was not the device stage (TAR_REQUIRED_SKIP_REASONS), the patterns, the three counts,
+        the table's slots and the stage's kernel time."""
+        ss = _CTarRequiredSkipStats()
+        ss.struct_size = TAR_REQUIRED_SKIP_STATS_SIZE_V1
+        if not hasattr(self._an._L, "tsg_tar_index_required_skip_stats"):  # an older build: the switch is absent
+            ss.reason = 1
+            return ss.to_dict()
+        if self._an._L.tsg_tar_index_required_skip_stats(self._h, c.byref(ss)) != 0:
+            raise RuntimeError("tsg_tar_index_required_skip_stats failed: %s" % _lib.last_error(self._an._L))
+        return ss.to_dict()
 
     @property
     def skip_stats(self) -> dict:
@@ -879,6 +916,23 @@ class SecretAnalyzer:
         m = c.c_int(0)
         if self._L.tsg_analyzer_get_tar_required(self._h, c.byref(m)) != 0:
             raise RuntimeError("tsg_analyzer_get_tar_required failed: %s" % _lib.last_error(self._L))
+        return TAR_REQUIRED_MODES[m.value]
+
+    def set_tar_required_skip(self, mode):
+        """Whether that device stage honours the layer walker's skip options itself
+        (tsg_analyzer_set_tar_required_skip): "host" (the default: with options set the host half runs) or "gpu"
+        (patterns of the forms L, **/L, L/** and **/*S are matched on the GPU, and files under a directory
+        skipped earlier in the layer are dropped there; any other pattern sends the whole option set to the host
+        half).  DeviceTarIndex.required_skip_stats says which ran and why; the index is the same."""
+        if mode not in TAR_REQUIRED_MODES:
+            raise ValueError("set_tar_required_skip: mode must be one of %s" % (TAR_REQUIRED_MODES,))
+        if self._L.tsg_analyzer_set_tar_required_skip(self._h, TAR_REQUIRED_MODES.index(mode)) != 0:
+            raise ValueError("tsg_analyzer_set_tar_required_skip failed: %s" % _lib.last_error(self._L))
+
+    def tar_required_skip(self) -> str:
+        m = c.c_int(0)
+        if self._L.tsg_analyzer_get_tar_required_skip(self._h, c.byref(m)) != 0:
+            raise RuntimeError("tsg_analyzer_get_tar_required_skip failed: %s" % _lib.last_error(self._L))
         return TAR_REQUIRED_MODES[m.value]
 
     def last_tar_fallback(self) -> int:

@@ -250,6 +250,7 @@ int tsg_analyzer_new(const tsg_scanner* s, const char* config_path, tsg_analyzer
   a->config_base = tsg::GoBase(config_path ? config_path : "");
   if (const char* w = std::getenv("TSG_TAR_WALK")) a->tar_walk.store(std::strcmp(w, "gpu") == 0 ? 1 : 0);
   if (const char* w = std::getenv("TSG_TAR_REQUIRED")) a->tar_required.store(std::strcmp(w, "gpu") == 0 ? 1 : 0);
+  if (const char* w = std::getenv("TSG_TAR_REQUIRED_SKIP")) a->tar_required_skip.store(std::strcmp(w, "gpu") == 0 ? 1 : 0);
   *out = a;
   return 0;
 }
@@ -920,6 +921,7 @@ int tsg_analyzer_set_tar_skip(tsg_analyzer* a, const char* const* skip_dirs, uin
     o = std::make_shared<tsg::TarSkipOpts>();
     o->dirs.assign(skip_dirs, skip_dirs + n_dirs);
     o->files.assign(skip_files, skip_files + n_files);
+    o->Classify();  // (the forms the GPU stage of a resident layer takes: tar_skip_dev.h)
   }
   // the cached window's entries were evaluated with the options before: the walk ends here
   std::lock_guard<std::mutex> g(a->walk_mu);

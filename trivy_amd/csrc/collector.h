@@ -53,6 +53,9 @@ struct tsg_analyzer {
   // tsg_analyzer_set_tar_required: 0 the path work and Required of a resident layer's index on the
   // host, 1 on the GPU behind the GPU walk (TSG_TAR_REQUIRED=gpu at creation).  Read once per index call.
   std::atomic<int> tar_required{0};
+  // tsg_analyzer_set_tar_required_skip: 0 skip options send that stage's work back to the host, 1 the
+  // stage honours them on the GPU where it takes every pattern (tar_skip_dev.h)
+  std::atomic<int> tar_required_skip{0};
   // tsg_analyzer_set_tar_skip: LayerTar's skipDirs / skipFiles for every layer walk
   // (NULL: none).  Replaced under walk_mu and tar_skip_mu; a walk or an index call
   // takes a reference of its own (TarSkip()), so a background index keeps its patterns.

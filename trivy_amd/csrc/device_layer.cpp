@@ -41,6 +41,7 @@ struct tsg_tar_index {
   tsg::TarIndexData d;
   tsg_tar_walk_stats ws{};  // tsg_tar_index_walk_stats
   tsg_tar_required_stats rs{};  // tsg_tar_index_required_stats
+  tsg_tar_required_skip_stats ss{};  // tsg_tar_index_required_skip_stats
 };
 
 namespace tsg {
@@ -74,7 +75,15 @@ struct TarIndexCtx {
   uint8_t* h_req = nullptr;
   uint64_t cap_req = 0, cap_hreq = 0;  // bytes
   hipEvent_t ev_req[2] = {nullptr, nullptr};
+  // its skip stage (tsg_analyzer_set_tar_required_skip mode 1): the table of the recorded directories,
+  // and the events around the match kernel and around the build and under kernels
+  uint8_t* d_skip = nullptr;
+  uint64_t cap_skip = 0;  // bytes
+  hipEvent_t ev_skip[4] = {nullptr, nullptr, nullptr, nullptr};
   ~TarIndexCtx() {
+    if (d_skip) (void)hipFree(d_skip);
+    for (hipEvent_t e : ev_skip)
+      if (e) (void)hipEventDestroy(e);
     if (d_req) (void)hipFree(d_req);
     if (h_req) (void)hipHostFree(h_req);
     for (hipEvent_t e : ev_req)
@@ -176,6 +185,11 @@ void GiveCtx(tsg_analyzer* a, std::unique_ptr<TarIndexCtx> c) {
     c->d_req = nullptr;
     c->cap_req = 0;
   }
+  if (c->cap_skip > kKeepBytes) {
+    (void)hipFree(c->d_skip);
+    c->d_skip = nullptr;
+    c->cap_skip = 0;
+  }
   if (c->cap_hreq > kKeepBytes) {
     (void)hipHostFree(c->h_req);
     c->h_req = nullptr;
@@ -273,13 +287,49 @@ bool Grow(uint8_t** p, uint64_t* cap, uint64_t want, bool pinned, hipError_t* e)
 
 // ---- path classify and Required on the GPU (tarrequired.h) ---------------------
 // Why an index call ran Required on the host (tsg_tar_required_stats.reason); 0: the GPU stage ran.
-enum : uint32_t { kReqUsedGpu = 0, kReqSetterOff = 1, kReqWalkHost = 2, kReqSkipOptions = 3, kReqLayerFellBack = 4 };
-uint32_t RequiredReason(const tsg_analyzer* a, int walk_mode) {
-  if (a->tar_required.load() != 1) return kReqSetterOff;
-  if (walk_mode != 1) return kReqWalkHost;
+enum : uint32_t {
+  kReqUsedGpu = 0,
+  kReqSetterOff = 1,
+  kReqWalkHost = 2,
+  kReqSkipOptions = 3,
+  kReqLayerFellBack = 4,
+  kReqAskedSkipDir = 5,  // (only with tsg_analyzer_set_tar_required_skip mode 1)
+};
+// Whether the stage honoured the skip options (tsg_tar_required_skip_stats.reason); 0: it did.
+enum : uint32_t {
+  kSkipRan = 0,
+  kSkipSetterOff = 1,
+  kSkipNoOptions = 2,
+  kSkipPatterns = 3,
+  kSkipNoStage = 4,
+  kSkipAskedDir = 5,
+};
+// *skip_reason (optional) as far as it is known before the walk; *with_skip (optional): the options
+// the stage is to honour (set only with reason 0 and options the device takes).
+uint32_t RequiredReason(const tsg_analyzer* a, int walk_mode, uint32_t* skip_reason = nullptr,
+                        std::shared_ptr<const TarSkipOpts>* with_skip = nullptr) {
   const std::shared_ptr<const TarSkipOpts> skip = a->TarSkip();
-  if (skip && skip->any()) return kReqSkipOptions;
-  return kReqUsedGpu;
+  const bool has = skip && skip->any();
+  uint32_t sr = a->tar_required_skip.load() != 1 ? kSkipSetterOff : !has ? kSkipNoOptions
+                : !skip->dev_ok ? kSkipPatterns : kSkipRan;
+  uint32_t r = kReqUsedGpu;
+  if (a->tar_required.load() != 1) r = kReqSetterOff;
+  else if (walk_mode != 1) r = kReqWalkHost;
+  else if (has && sr != kSkipRan) r = kReqSkipOptions;
+  if (sr == kSkipRan && r != kReqUsedGpu) sr = kSkipNoStage;
+  if (skip_reason) *skip_reason = sr;
+  if (with_skip && r == kReqUsedGpu && has) *with_skip = skip;
+  return r;
+}
+void SkipStatsInit(const tsg_analyzer* a, uint32_t reason, tsg_tar_required_skip_stats* ss) {
+  *ss = tsg_tar_required_skip_stats{};
+  ss->mode = uint32_t(a->tar_required_skip.load());
+  ss->reason = reason;
+  const std::shared_ptr<const TarSkipOpts> skip = a->TarSkip();
+  if (skip) {
+    ss->dir_patterns = uint32_t(skip->dirs.size());
+    ss->file_patterns = uint32_t(skip->files.size());
+  }
 }
 
 // One run of the stage behind a compaction on the context's stream, and what it handed over.
@@ -293,6 +343,13 @@ struct ReqPass {
   const uint8_t* blob = nullptr;
   uint64_t n_recs = 0, blob_bytes = 0, bad = 0;
   double ms_kernel = 0, ms_copy = 0;
+  // the skip stage: the options it honours (NULL: it does not run), a table size forced by the debug
+  // hook (0: TarSkipSlots), and what it did
+  std::shared_ptr<const TarSkipOpts> skip;
+  uint64_t forced_slots = 0;
+  bool bad_slots = false;  // the forced size is no power of two of at least four times the directories
+  uint64_t n_dirs = 0, slots = 0;
+  double ms_skip = 0;
 };
 void ReqPassInit(const tsg_analyzer* a, ReqPass* R) {
   const SecretScanner::AllowTables t = a->s->s->allow_tables();
@@ -311,23 +368,62 @@ hipError_t RequiredOnGpu(TarIndexCtx* c, ReqPass* R, const uint8_t* d_recs, cons
     if (e == hipSuccess) e = r;
     return e == hipSuccess;
   };
-  if (!TarRequiredPlan(n, n_layers, name_bytes, uint32_t(R->cfg.size()), &R->L)) return hipErrorInvalidValue;
+  const TarSkipOpts* skip = R->skip.get();
+  if (!TarRequiredPlan(n, n_layers, name_bytes, uint32_t(R->cfg.size()), &R->L, skip != nullptr))
+    return hipErrorInvalidValue;
   const TarRequiredLayout& L = R->L;
   for (hipEvent_t& v : c->ev_req)
     if (!v) ok(hipEventCreate(&v));
+  if (skip) {
+    for (hipEvent_t& v : c->ev_skip)
+      if (!v) ok(hipEventCreate(&v));
+    if (!c->d_count) ok(hipMalloc(reinterpret_cast<void**>(&c->d_count), 16));
+    if (!c->h_count) ok(hipHostMalloc(reinterpret_cast<void**>(&c->h_count), 16, hipHostMallocDefault));
+  }
   const uint64_t cnt_bytes = uint64_t(n_layers) * sizeof(TarRequiredCounts);
   if (!ok(e) || !Grow(&c->d_req, &c->cap_req, L.bytes, false, &e) ||
       !Grow(&c->h_req, &c->cap_hreq, L.tables_bytes + cnt_bytes, true, &e))
     return e;
-  TarRequiredTables(L, rec_base, name_base, R->cfg.data(), c->h_req);
-  if (!(ok(hipEventRecord(c->ev_req[0], c->s)) &&
-        ok(TarRequiredRun(L, c->h_req, d_recs, d_names, R->d_path, R->d_sure, c->d_req, grid_cap, c->s)) &&
+  TarRequiredTables(L, rec_base, name_base, R->cfg.data(), c->h_req, skip ? &skip->dev : nullptr);
+  R->n_dirs = R->slots = 0;
+  R->ms_skip = 0;
+  if (skip) {
+    // the decisions, the match kernel, and one small copy: the number of directories it recorded
+    // sizes the table, and with none the other two kernels do not run
+    if (!(ok(hipEventRecord(c->ev_req[0], c->s)) &&
+          ok(TarRequiredDecide(L, c->h_req, d_recs, d_names, R->d_path, R->d_sure, c->d_req, grid_cap, c->s)) &&
+          ok(hipEventRecord(c->ev_skip[0], c->s)) &&
+          ok(TarSkipMatchRun(L, d_recs, d_names, c->d_req, c->d_count, grid_cap, c->s)) &&
+          ok(hipEventRecord(c->ev_skip[1], c->s)) &&
+          ok(hipMemcpyAsync(c->h_count, c->d_count, 4, hipMemcpyDeviceToHost, c->s)) && ok(hipStreamSynchronize(c->s))))
+      return e;
+    R->n_dirs = *c->h_count;
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->ev_skip[0], c->ev_skip[1]) == hipSuccess) R->ms_skip = ms;
+    if (R->n_dirs) {
+      R->slots = R->forced_slots ? R->forced_slots : TarSkipSlots(R->n_dirs);
+      if ((R->slots & (R->slots - 1)) || R->slots < 4 * R->n_dirs || R->slots > (uint64_t(1) << 31)) {
+        R->bad_slots = true;
+        return hipErrorInvalidValue;
+      }
+      if (!Grow(&c->d_skip, &c->cap_skip, R->slots * sizeof(TarSkipSlot), false, &e) ||
+          !(ok(hipEventRecord(c->ev_skip[2], c->s)) &&
+            ok(TarSkipUnderRun(L, d_recs, d_names, c->d_req, reinterpret_cast<TarSkipSlot*>(c->d_skip), R->slots, grid_cap,
+                               c->s)) &&
+            ok(hipEventRecord(c->ev_skip[3], c->s))))
+        return e;
+    }
+  }
+  if (!((skip ? ok(TarRequiredFinish(L, d_recs, d_names, c->d_req, grid_cap, c->s))
+              : ok(hipEventRecord(c->ev_req[0], c->s)) &&
+                    ok(TarRequiredRun(L, c->h_req, d_recs, d_names, R->d_path, R->d_sure, c->d_req, grid_cap, c->s))) &&
         ok(hipEventRecord(c->ev_req[1], c->s)) &&
         ok(hipMemcpyAsync(c->h_req + L.tables_bytes, c->d_req + L.counts, cnt_bytes, hipMemcpyDeviceToHost, c->s)) &&
         ok(hipStreamSynchronize(c->s))))
     return e;
   float ms = 0;
   if (hipEventElapsedTime(&ms, c->ev_req[0], c->ev_req[1]) == hipSuccess) R->ms_kernel = ms;
+  if (R->n_dirs && hipEventElapsedTime(&ms, c->ev_skip[2], c->ev_skip[3]) == hipSuccess) R->ms_skip += ms;
   R->counts = reinterpret_cast<const TarRequiredCounts*>(c->h_req + L.tables_bytes);
   R->n_recs = R->blob_bytes = R->bad = 0;
   for (uint32_t k = 0; k < n_layers; k++) {
@@ -357,20 +453,22 @@ hipError_t RequiredOnGpu(TarIndexCtx* c, ReqPass* R, const uint8_t* d_recs, cons
 
 // The host half over one layer's file records (IndexTarFiles): the index, the V1 stats of mode 1 and
 // the required stats' counts.  -1: the records contradict the blob or the counts (error set).
+// skip: the options the stage honoured (NULL: none); then 1: an asked name is a skipped directory --
+// nothing was added, and the caller indexes the layer from the walk's records (reason 5).
 int FilesToIndex(tsg_analyzer* a, const TarRequiredCounts& cnt, const tsg_tar_file_rec* recs, const uint8_t* blob,
                  const tsg_tar_stop& stop, uint64_t n_bytes, uint64_t candidates, TarIndexData* d,
-                 tsg_device_tar_stats* st, tsg_tar_required_stats* rs) {
+                 tsg_device_tar_stats* st, tsg_tar_required_stats* rs, const TarSkipOpts* skip = nullptr) {
   const SecretScanner* sc = a->s->s.get();
   TarRequiredHostStats hs;
-  if (IndexTarFiles(
+  const int rc = IndexTarFiles(
           recs, cnt.records, blob, cnt.path_bytes, cnt,
           [sc](const char* p, uint64_t len, uint64_t rules) {
             return sc->AllowPathMasked(reinterpret_cast<const uint8_t*>(p), size_t(len), rules);
           },
           [sc](const char* p, uint64_t len) { return sc->AllowPath(reinterpret_cast<const uint8_t*>(p), size_t(len)); },
           [a](const char* p, uint64_t len, int64_t size) { return RequiredPath(a, p, len, size); }, d, EntriesPar(),
-          &hs) < 0)
-    return -1;
+          &hs, skip);
+  if (rc != 0) return rc;
   if (st) {
     const uint64_t on_chain = stop.ext_visited + cnt.ext_headers + cnt.entries;  // as EntriesToIndex counts them
     st->tar = d->tar;
@@ -392,6 +490,28 @@ int FilesToIndex(tsg_analyzer* a, const TarRequiredCounts& cnt, const tsg_tar_fi
     rs->path_bytes = cnt.path_bytes;
   }
   return 0;
+}
+
+// A layer whose asked names hold a skipped directory (FilesToIndex returned 1): its entry records
+// and names are still where the compaction wrote them in c->d_out (the records of all layers, then
+// from rec_bytes_all on the names); they are copied out and the host half of the walk indexes it.
+int RefusedLayerToIndex(tsg_analyzer* a, TarIndexCtx* c, const std::string& who, uint64_t rec_bytes_all, uint64_t rec0,
+                        uint64_t name0, const TarChainHead& head, uint64_t n_bytes, TarIndexData* d,
+                        tsg_device_tar_stats* st) {
+  std::vector<uint8_t> buf(size_t(head.entries) * sizeof(tsg_tar_entry_rec) + size_t(head.name_bytes) + 1);
+  uint8_t* names = buf.data() + size_t(head.entries) * sizeof(tsg_tar_entry_rec);
+  hipError_t e = hipSuccess;
+  if (head.entries)
+    e = hipMemcpy(buf.data(), c->d_out + rec0 * sizeof(tsg_tar_entry_rec), size_t(head.entries) * sizeof(tsg_tar_entry_rec),
+                  hipMemcpyDeviceToHost);
+  if (e == hipSuccess && head.name_bytes)
+    e = hipMemcpy(names, c->d_out + rec_bytes_all + name0, size_t(head.name_bytes), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    SetError(who + ": " + hipGetErrorString(e));
+    return -1;
+  }
+  return EntriesToIndex(a, reinterpret_cast<const tsg_tar_entry_rec*>(buf.data()), head.entries, names, head.name_bytes,
+                        head.stop, n_bytes, head.candidates, d, st);
 }
 
 // The GPU half on the context's stream: 0 with *recs / *names (in c->h_out) and
@@ -626,8 +746,15 @@ static int IndexOneLayer(tsg_analyzer* a, const std::string& who, const uint8_t*
   if (forced_fallback) ws.fallback = *forced_fallback;
   // Required on the GPU (tsg_analyzer_set_tar_required): only behind a GPU walk that completes the layer
   tsg_tar_required_stats rs{};
-  rs.reason = RequiredReason(a, int(ws.walk));
-  if (rs.reason == kReqUsedGpu && forced_fallback) rs.reason = kReqLayerFellBack;
+  uint32_t skip_reason = 0;
+  std::shared_ptr<const TarSkipOpts> with_skip;
+  rs.reason = RequiredReason(a, int(ws.walk), &skip_reason, &with_skip);
+  if (rs.reason == kReqUsedGpu && forced_fallback) {
+    rs.reason = kReqLayerFellBack;
+    if (skip_reason == kSkipRan) skip_reason = kSkipNoStage;
+  }
+  tsg_tar_required_skip_stats ss{};
+  SkipStatsInit(a, skip_reason, &ss);
   if (ws.walk == 1 && !forced_fallback) {
     // The chain walk on the GPU.  A layer it does not complete falls through to the host walk below,
     // from scratch: that path alone words what is wrong with a malformed archive.
@@ -646,6 +773,7 @@ static int IndexOneLayer(tsg_analyzer* a, const std::string& who, const uint8_t*
     } else {
       on_gpu = rs.reason == kReqUsedGpu;
       if (on_gpu) ReqPassInit(a, &rq);
+      if (on_gpu) rq.skip = with_skip;
       rc = ChainOnGpu(c.get(), dev_tar, n_bytes, 0, 0, who, &head, &recs, &names, &ws, on_gpu ? &rq : nullptr);
     }
     a->tar_fallback_last.store(ws.fallback);
@@ -653,14 +781,27 @@ static int IndexOneLayer(tsg_analyzer* a, const std::string& who, const uint8_t*
       GiveCtx(a, std::move(c));
       return -2;
     }
-    if (rc == 1 && rs.reason == kReqUsedGpu) rs.reason = kReqLayerFellBack;
+    if (rc == 1 && rs.reason == kReqUsedGpu) {
+      rs.reason = kReqLayerFellBack;
+      if (ss.reason == kSkipRan) ss.reason = kSkipNoStage;
+    }
     if (rc == 0) {
       const double th = NowMs();
       tsg_device_tar_stats tmp{};
       double hm[3] = {0, 0, 0};
       if (on_gpu) {
         rc = FilesToIndex(a, rq.counts[0], rq.recs, rq.blob, head.stop, n_bytes, head.candidates, &ix->d,
-                          st ? st : &tmp, &rs);
+                          st ? st : &tmp, &rs, rq.skip.get());
+        if (rc == 1) {  // an asked name is a skipped directory: the host half of the walk, from its records
+          rs = tsg_tar_required_stats{};
+          rs.reason = kReqAskedSkipDir;
+          ss.reason = kSkipAskedDir;
+          rc = RefusedLayerToIndex(a, c.get(), who, (head.entries * sizeof(tsg_tar_entry_rec) + 255) & ~uint64_t(255), 0,
+                                   0, head, n_bytes, &ix->d, st ? st : &tmp);
+        } else if (rq.skip) {
+          ss.table_slots = rq.slots;
+          ss.ms_kernel = rq.ms_skip;
+        }
         rs.ms_kernel = rq.ms_kernel;
         rs.ms_copy = rq.ms_copy;
         rs.ms_host = NowMs() - th;
@@ -685,6 +826,7 @@ static int IndexOneLayer(tsg_analyzer* a, const std::string& who, const uint8_t*
                      static_cast<unsigned long long>(head.entries));
       ix->ws = ws;
       ix->rs = rs;
+      ix->ss = ss;
       *out = ix.release();
       return 0;
     }
@@ -753,6 +895,7 @@ static int IndexOneLayer(tsg_analyzer* a, const std::string& who, const uint8_t*
   FillStats(st, ix->d, src, n_bytes, count, runs, ms_kernel, NowMs() - t0);
   ix->ws = ws;
   ix->rs = rs;  // (mode 0: the reason says why Required ran on the host)
+  ix->ss = ss;
   *out = ix.release();
   return 0;
 }
@@ -839,9 +982,13 @@ int tsg_analyzer_index_device_tars(tsg_analyzer* a, const tsg_device_tars* t, ts
       }
       ForestPass P;
       ReqPass rq;  // Required on the GPU (tsg_analyzer_set_tar_required): one stage for the pass's layers
-      const uint32_t req_reason = RequiredReason(a, 1);
+      uint32_t skip_reason = 0;
+      std::shared_ptr<const TarSkipOpts> with_skip;
+      const uint32_t req_reason = RequiredReason(a, 1, &skip_reason, &with_skip);
       const bool on_gpu = req_reason == kReqUsedGpu;
       if (on_gpu) ReqPassInit(a, &rq);
+      if (on_gpu) rq.skip = with_skip;
+      std::vector<uint8_t> refused(cnt, 0);  // layers whose asked names hold a skipped directory
       if (ForestOnGpu(c.get(), ptrs.data() + first, nb.data() + first, cnt, 0, 0, who, &P, &F, on_gpu ? &rq : nullptr) <
           0) {
         GiveCtx(a, std::move(c));
@@ -865,10 +1012,18 @@ int tsg_analyzer_index_device_tars(tsg_analyzer* a, const tsg_device_tars* t, ts
         tsg_device_tar_stats tmp{};
         tsg_device_tar_stats* sk = st ? &st[k] : &tmp;
         ix->rs.reason = req_reason;
+        SkipStatsInit(a, skip_reason, &ix->ss);
         if (on_gpu) {
           const TarRequiredCounts& cn = rq.counts[j];
           rcs[j] = FilesToIndex(a, cn, rq.recs + cn.rec_first, rq.blob + cn.path_first, head.stop, nb[k],
-                                head.candidates, &ix->d, sk, &ix->rs);
+                                head.candidates, &ix->d, sk, &ix->rs, rq.skip.get());
+          if (rcs[j] == 1) {  // (indexed below, on this thread: the copies are HIP calls)
+            refused[j] = 1;
+            rcs[j] = 0;
+          } else if (rq.skip) {
+            ix->ss.table_slots = rq.slots;  // (shared by the pass's layers, as ms_kernel is)
+            ix->ss.ms_kernel = rq.ms_skip;
+          }
           ix->rs.ms_kernel = rq.ms_kernel;  // (the stage is shared by the pass's layers, as its copies are)
           ix->rs.ms_copy = rq.ms_copy;
           ix->rs.ms_host = NowMs() - tl;
@@ -887,6 +1042,17 @@ int tsg_analyzer_index_device_tars(tsg_analyzer* a, const tsg_device_tars* t, ts
         sk->ms_total = ix->ws.ms_host;
         ixs[k] = std::move(ix);
       });
+      for (uint32_t j = 0; j < cnt; j++) {
+        if (!refused[j] || rcs[j] < 0) continue;
+        tsg_tar_index* ix = ixs[first + j].get();
+        tsg_device_tar_stats tmp{};
+        ix->rs = tsg_tar_required_stats{};
+        ix->rs.reason = kReqAskedSkipDir;
+        ix->ss.reason = kSkipAskedDir;
+        const uint64_t rec_bytes_all = (P.rec_base[cnt] * sizeof(tsg_tar_entry_rec) + 255) & ~uint64_t(255);
+        rcs[j] = RefusedLayerToIndex(a, c.get(), who, rec_bytes_all, P.rec_base[j], P.name_base[j], P.heads[j],
+                                     nb[first + j], &ix->d, st ? &st[first + j] : &tmp);
+      }
       F.ms_host += NowMs() - th;
       for (uint32_t j = 0; j < cnt; j++) {
         if (rcs[j] < 0) {  // (records that contradict the name blob: the layer changed under the pass)
@@ -1025,6 +1191,48 @@ int tsg_analyzer_get_tar_required(const tsg_analyzer* a, int* mode) {
   return 0;
 }
 
+int tsg_analyzer_set_tar_required_skip(tsg_analyzer* a, int mode) {
+  if (!a) {
+    tsg::SetError("tsg_analyzer_set_tar_required_skip: NULL analyzer");
+    return -1;
+  }
+  if (mode != 0 && mode != 1) {
+    tsg::SetError("tsg_analyzer_set_tar_required_skip: mode " + std::to_string(mode) + " is not 0 (host) or 1 (gpu)");
+    return -1;
+  }
+  a->tar_required_skip.store(mode);
+  return 0;
+}
+
+int tsg_analyzer_get_tar_required_skip(const tsg_analyzer* a, int* mode) {
+  if (!a || !mode) {
+    tsg::SetError("tsg_analyzer_get_tar_required_skip: NULL argument");
+    return -1;
+  }
+  *mode = a->tar_required_skip.load();
+  return 0;
+}
+
+int tsg_tar_index_required_skip_stats(const tsg_tar_index* ix, tsg_tar_required_skip_stats* out) {
+  if (!ix || !out) {
+    tsg::SetError("tsg_tar_index_required_skip_stats: NULL argument");
+    return -1;
+  }
+  if (out->struct_size != TSG_TAR_REQUIRED_SKIP_STATS_SIZE_V1) {
+    tsg::SetError("tsg_tar_index_required_skip_stats: tsg_tar_required_skip_stats.struct_size " +
+                  std::to_string(out->struct_size) + " is not a size this library knows (v1 = " +
+                  std::to_string(TSG_TAR_REQUIRED_SKIP_STATS_SIZE_V1) + ")");
+    return -1;
+  }
+  *out = ix->ss;
+  out->struct_size = TSG_TAR_REQUIRED_SKIP_STATS_SIZE_V1;
+  out->reserved = 0;
+  out->skipped_dirs = ix->d.skip.skipped_dirs;  // (whichever half produced them)
+  out->skipped_files = ix->d.skip.skipped_files;
+  out->under_skipped_dir = ix->d.skip.under_skipped_dir;
+  return 0;
+}
+
 int tsg_tar_index_required_stats(const tsg_tar_index* ix, tsg_tar_required_stats* out) {
   if (!ix || !out) {
     tsg::SetError("tsg_tar_index_required_stats: NULL argument");
@@ -1070,13 +1278,14 @@ int tsg_debug_tar_required_tables(const tsg_analyzer* a, void* path_table_out, u
   return 0;
 }
 
-int tsg_debug_tar_required(tsg_analyzer* a, const void* records, uint64_t n_records, const uint8_t* names,
-                           uint64_t name_bytes, const uint64_t* rec_base, const uint64_t* name_base, uint32_t n_layers,
-                           uint32_t grid_cap, uint8_t* verdicts_out, void* file_recs_out, uint64_t rec_cap,
-                           uint64_t* n_file_recs, uint8_t* blob_out, uint64_t blob_cap, uint64_t* blob_bytes,
-                           uint64_t* counts_out) {
+// tsg_debug_tar_required, and with skip options tsg_debug_tar_required_skip.
+static int DebugTarRequired(const std::string& who, tsg_analyzer* a, const void* records, uint64_t n_records,
+                            const uint8_t* names, uint64_t name_bytes, const uint64_t* rec_base,
+                            const uint64_t* name_base, uint32_t n_layers, uint32_t grid_cap,
+                            std::shared_ptr<const tsg::TarSkipOpts> skip, uint64_t forced_slots, uint8_t* verdicts_out,
+                            void* file_recs_out, uint64_t rec_cap, uint64_t* n_file_recs, uint8_t* blob_out,
+                            uint64_t blob_cap, uint64_t* blob_bytes, uint64_t* counts_out, uint64_t* slots_out) {
   using namespace tsg;
-  const std::string who = "tsg_debug_tar_required";
   if (!a || !rec_base || !name_base || n_layers == 0 || !n_file_recs || !blob_bytes || !counts_out ||
       (n_records && (!records || !verdicts_out)) || (name_bytes && !names) || (rec_cap && !file_recs_out) ||
       (blob_cap && !blob_out) || n_records >= (uint64_t(1) << 31)) {
@@ -1108,6 +1317,8 @@ int tsg_debug_tar_required(tsg_analyzer* a, const void* records, uint64_t n_reco
   };
   ReqPass R;
   ReqPassInit(a, &R);
+  R.skip = skip;
+  R.forced_slots = forced_slots;
   std::vector<uint8_t> dec;
   if (ok(e) && ok(hipStreamCreateWithFlags(&c.s, hipStreamNonBlocking)) &&
       ok(hipMalloc(reinterpret_cast<void**>(&d_in), rec_bytes + name_bytes + 256)) &&
@@ -1116,10 +1327,16 @@ int tsg_debug_tar_required(tsg_analyzer* a, const void* records, uint64_t n_reco
     ok(RequiredOnGpu(&c, &R, d_in, d_in + rec_bytes, n_records, name_bytes, rec_base, name_base, n_layers, grid_cap, &dec));
   if (c.s) (void)hipStreamSynchronize(c.s);
   if (d_in) (void)hipFree(d_in);
+  if (R.bad_slots) {
+    SetError(who + ": table_slots " + std::to_string(forced_slots) + " is no power of two of at least " +
+             std::to_string(4 * R.n_dirs) + " (twice the keys of " + std::to_string(R.n_dirs) + " recorded directories)");
+    return -1;
+  }
   if (e != hipSuccess) {
     SetError(who + ": " + hipGetErrorString(e));
     return -2;
   }
+  if (slots_out) *slots_out = R.slots;
   for (uint64_t i = 0; i < n_records; i++) verdicts_out[i] = dec[size_t(i) * 16 + 12];
   std::memcpy(counts_out, R.counts, size_t(n_layers) * sizeof(TarRequiredCounts));
   *n_file_recs = R.n_recs;
@@ -1135,6 +1352,74 @@ int tsg_debug_tar_required(tsg_analyzer* a, const void* records, uint64_t n_reco
     return -4;
   }
   return 0;
+}
+
+int tsg_debug_tar_required(tsg_analyzer* a, const void* records, uint64_t n_records, const uint8_t* names,
+                           uint64_t name_bytes, const uint64_t* rec_base, const uint64_t* name_base, uint32_t n_layers,
+                           uint32_t grid_cap, uint8_t* verdicts_out, void* file_recs_out, uint64_t rec_cap,
+                           uint64_t* n_file_recs, uint8_t* blob_out, uint64_t blob_cap, uint64_t* blob_bytes,
+                           uint64_t* counts_out) {
+  return DebugTarRequired("tsg_debug_tar_required", a, records, n_records, names, name_bytes, rec_base, name_base,
+                          n_layers, grid_cap, nullptr, 0, verdicts_out, file_recs_out, rec_cap, n_file_recs, blob_out,
+                          blob_cap, blob_bytes, counts_out, nullptr);
+}
+
+int tsg_debug_tar_required_skip(tsg_analyzer* a, const void* records, uint64_t n_records, const uint8_t* names,
+                                uint64_t name_bytes, const uint64_t* rec_base, const uint64_t* name_base,
+                                uint32_t n_layers, uint32_t grid_cap, const char* const* skip_dirs, uint32_t n_dirs,
+                                const char* const* skip_files, uint32_t n_files, uint64_t table_slots,
+                                uint8_t* verdicts_out, void* file_recs_out, uint64_t rec_cap, uint64_t* n_file_recs,
+                                uint8_t* blob_out, uint64_t blob_cap, uint64_t* blob_bytes, uint64_t* counts_out,
+                                uint64_t* table_slots_out) {
+  using namespace tsg;
+  const std::string who = "tsg_debug_tar_required_skip";
+  bool bad = (n_dirs && !skip_dirs) || (n_files && !skip_files) || (n_dirs == 0 && n_files == 0);
+  for (uint32_t k = 0; !bad && k < n_dirs; k++) bad = !skip_dirs[k];
+  for (uint32_t k = 0; !bad && k < n_files; k++) bad = !skip_files[k];
+  if (bad) {
+    SetError(who + ": no pattern, or a NULL pattern");
+    return -1;
+  }
+  auto o = std::make_shared<TarSkipOpts>();
+  o->dirs.assign(skip_dirs, skip_dirs + n_dirs);
+  o->files.assign(skip_files, skip_files + n_files);
+  o->Classify();
+  if (!o->dev_ok) {
+    SetError(who + ": a pattern, or the set, is outside what the device takes");
+    return -1;
+  }
+  if (table_slots_out) *table_slots_out = 0;
+  return DebugTarRequired(who, a, records, n_records, names, name_bytes, rec_base, name_base, n_layers, grid_cap, o,
+                          table_slots, verdicts_out, file_recs_out, rec_cap, n_file_recs, blob_out, blob_cap, blob_bytes,
+                          counts_out, table_slots_out);
+}
+
+int tsg_debug_tar_skip_classify(const char* const* skip_dirs, uint32_t n_dirs, const char* const* skip_files,
+                                uint32_t n_files, uint8_t* forms_out) {
+  using namespace tsg;
+  if ((n_dirs && !skip_dirs) || (n_files && !skip_files)) {
+    SetError("tsg_debug_tar_skip_classify: NULL pattern array with a non-zero count");
+    return -1;
+  }
+  TarSkipOpts o;
+  o.dirs.assign(skip_dirs, skip_dirs + n_dirs);
+  o.files.assign(skip_files, skip_files + n_files);
+  o.Classify();
+  if (!o.dev_ok) return 0;
+  for (uint32_t k = 0; forms_out && k < n_dirs; k++) forms_out[k] = o.dev.pat[k].form;
+  for (uint32_t k = 0; forms_out && k < n_files; k++) forms_out[n_dirs + k] = o.dev.pat[kTarSkipMaxPatterns + k].form;
+  return 1;
+}
+
+int tsg_debug_tar_skip_match(const char* pattern, const uint8_t* fp, uint32_t len) {
+  using namespace tsg;
+  if (!pattern || (len && !fp)) {
+    SetError("tsg_debug_tar_skip_match: NULL argument");
+    return -1;
+  }
+  TarSkipTable t;
+  if (!TarSkipClassify({std::string(pattern)}, {}, &t)) return -1;
+  return TarSkipMatch(&t, false, fp, len) ? 1 : 0;
 }
 
 int tsg_debug_index_tar_files(tsg_analyzer* a, const void* file_recs, uint64_t n_recs, const uint8_t* blob,
@@ -1167,9 +1452,22 @@ int tsg_debug_index_tar_files(tsg_analyzer* a, const void* file_recs, uint64_t n
   std::unique_ptr<tsg_tar_index> ix(new tsg_tar_index());
   ix->n_bytes = n_bytes;
   tsg_device_tar_stats tmp{};
-  if (FilesToIndex(a, cnt, static_cast<const tsg_tar_file_rec*>(file_recs), blob, sp, n_bytes, candidates_given, &ix->d,
-                   st ? st : &tmp, &ix->rs) < 0)
-    return -1;
+  // (with tsg_analyzer_set_tar_required_skip mode 1 and options the device takes, the records are
+  // those of a stage that ran its skip stage)
+  uint32_t skip_reason = 0;
+  std::shared_ptr<const TarSkipOpts> with_skip;
+  const std::shared_ptr<const TarSkipOpts> opts = a->TarSkip();
+  if (a->tar_required_skip.load() == 1 && opts && opts->any() && opts->dev_ok) with_skip = opts;
+  skip_reason = a->tar_required_skip.load() != 1 ? kSkipSetterOff : !(opts && opts->any()) ? kSkipNoOptions
+                : !opts->dev_ok ? kSkipPatterns : kSkipRan;
+  const int rc = FilesToIndex(a, cnt, static_cast<const tsg_tar_file_rec*>(file_recs), blob, sp, n_bytes, candidates_given,
+                              &ix->d, st ? st : &tmp, &ix->rs, with_skip.get());
+  if (rc == 1) {
+    SetError(std::string(who) + ": an asked name is a skipped directory (the layer is indexed from the walk's records)");
+    return 1;
+  }
+  if (rc < 0) return -1;
+  SkipStatsInit(a, skip_reason, &ix->ss);
   ix->rs.ms_host = NowMs() - t0;
   if (st) {
     st->kernel_runs = 0;
@@ -1377,7 +1675,9 @@ int tsg_debug_index_tar_records(tsg_analyzer* a, const uint8_t* host_tar, uint64
   ix->n_bytes = n_bytes;
   if (WalkRecords(a, src, n_bytes, &ix->d) < 0) return src.failed() ? -2 : -3;
   FillStats(st, ix->d, src, n_bytes, n_records, 0, 0, NowMs() - t0);
-  ix->rs.reason = std::max<uint32_t>(RequiredReason(a, 0), kReqSetterOff);
+  uint32_t skip_reason = 0;
+  ix->rs.reason = std::max<uint32_t>(RequiredReason(a, 0, &skip_reason), kReqSetterOff);
+  SkipStatsInit(a, skip_reason == kSkipRan ? uint32_t(kSkipNoStage) : skip_reason, &ix->ss);
   *out = ix.release();
   return 0;
 }
@@ -1477,7 +1777,9 @@ int tsg_debug_index_tar_entries(tsg_analyzer* a, const void* records, uint64_t n
   ix->ws.walk = 1;
   ix->ws.chain_entries = n_records;
   ix->ws.name_bytes = name_bytes;
-  ix->rs.reason = std::max<uint32_t>(RequiredReason(a, 1), kReqSetterOff);  // (this hook is the host half)
+  uint32_t skip_reason = 0;
+  ix->rs.reason = std::max<uint32_t>(RequiredReason(a, 1, &skip_reason), kReqSetterOff);  // (this hook is the host half)
+  SkipStatsInit(a, skip_reason == kSkipRan ? uint32_t(kSkipNoStage) : skip_reason, &ix->ss);
   *out = ix.release();
   return 0;
 }

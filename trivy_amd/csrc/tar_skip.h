@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "skip_path.h"
+#include "tar_skip_dev.h"
 
 namespace tsg {
 
@@ -26,6 +27,11 @@ namespace tsg {
 struct TarSkipOpts {
   std::vector<std::string> dirs, files;
   bool any() const { return !dirs.empty() || !files.empty(); }
+  // the same patterns as the GPU stage reads them (tar_skip_dev.h), where it takes them all:
+  // filled by whoever sets the options (Classify)
+  bool dev_ok = false;
+  TarSkipTable dev;
+  void Classify() { dev_ok = TarSkipClassify(dirs, files, &dev); }
 };
 
 struct TarSkipCounts {

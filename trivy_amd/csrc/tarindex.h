@@ -98,19 +98,36 @@ hipError_t TarForestCompact(const TarForestLayout& L, const uint8_t* d_work, uin
 // ---- path classify and Required on the GPU (tarrequired.hip; the contract: tarrequired.h) ----
 struct PathTable;  // pathfilter.h
 struct SureTable;
+struct TarSkipTable;  // tar_skip_dev.h
 // The stage's one device buffer for n entries (below 2^31) of n_layers layers (at least one) whose
 // names take name_bytes, with a config base of cfg_len bytes; false: a count out of range.
-bool TarRequiredPlan(uint64_t n, uint32_t n_layers, uint64_t name_bytes, uint32_t cfg_len, TarRequiredLayout* L);
+// skip: the stage will run with LayerTar's skip options (room for their table in the upload).
+bool TarRequiredPlan(uint64_t n, uint32_t n_layers, uint64_t name_bytes, uint32_t cfg_len, TarRequiredLayout* L,
+                     bool skip = false);
 // The tables of a planned stage into h_tables (L.tables_bytes bytes, host memory): n_layers + 1 record
-// and name bases, the last pair (n, name_bytes), and the config base.
+// and name bases, the last pair (n, name_bytes), the config base, and (L.skip) the skip patterns.
 void TarRequiredTables(const TarRequiredLayout& L, const uint64_t* rec_base, const uint64_t* name_base, const char* cfg,
-                       uint8_t* h_tables);
+                       uint8_t* h_tables, const TarSkipTable* skip = nullptr);
 // The stage over d_records (64 B each, 16-B aligned) and d_names, as the compaction on the same stream
 // wrote them: afterwards d_req (L.bytes, 256-B aligned) holds a TarRequiredCounts per layer at L.counts,
 // the file records at L.recs and the path blob at L.blob.  d_path / d_sure: the scanner's tables in HBM
 // (SecretScanner::allow_tables), either may be NULL.  h_tables stays valid until the stream has passed the upload.
+// It is TarRequiredDecide followed by TarRequiredFinish; with skip options the two steps of the skip
+// stage go between them: TarSkipMatchRun, which leaves the number of recorded directories in
+// *d_n_dirs (4 B, zeroed on the stream here), and -- when the caller has read that count and it is
+// not zero -- TarSkipUnderRun with a table of `slots` TarSkipSlot (a power of two, at least four
+// times the recorded directories), which it clears on the stream first.
 hipError_t TarRequiredRun(const TarRequiredLayout& L, const uint8_t* h_tables, const uint8_t* d_records,
                           const uint8_t* d_names, const PathTable* d_path, const SureTable* d_sure, uint8_t* d_req,
                           uint32_t grid_cap, hipStream_t s);
+hipError_t TarRequiredDecide(const TarRequiredLayout& L, const uint8_t* h_tables, const uint8_t* d_records,
+                             const uint8_t* d_names, const PathTable* d_path, const SureTable* d_sure, uint8_t* d_req,
+                             uint32_t grid_cap, hipStream_t s);
+hipError_t TarRequiredFinish(const TarRequiredLayout& L, const uint8_t* d_records, const uint8_t* d_names,
+                             uint8_t* d_req, uint32_t grid_cap, hipStream_t s);
+hipError_t TarSkipMatchRun(const TarRequiredLayout& L, const uint8_t* d_records, const uint8_t* d_names, uint8_t* d_req,
+                           uint32_t* d_n_dirs, uint32_t grid_cap, hipStream_t s);
+hipError_t TarSkipUnderRun(const TarRequiredLayout& L, const uint8_t* d_records, const uint8_t* d_names, uint8_t* d_req,
+                           TarSkipSlot* d_table, uint64_t slots, uint32_t grid_cap, hipStream_t s);
 
 }  // namespace tsg

@@ -40,6 +40,28 @@
 // worst case (a record per entry, every name plus its NUL) and nothing is written past the
 // counted sizes.  A record whose name lies outside its layer's name blob is kReqBad: it is
 // counted, never read, and the pass's result is refused.
+//
+// With LayerTar's skip options (tsg_analyzer_set_tar_required_skip mode 1, every pattern one of
+// tar_skip_dev.h's forms) three more kernels run between the decisions and the sums, and
+// rewrite the verdict byte of the entries the options drop (tar_skip.h is the host's side):
+//
+//   match   a non-marker directory (kReqOther with typeflag '5', or '\0' with a name that ends
+//           in '/') whose fp a directory pattern matches becomes kReqSkipDir: it is recorded.
+//           A regular non-marker (kReqDrop, kReqKeep, kReqAskAllow) whose fp a file pattern
+//           matches becomes kReqSkipFile.  Markers and kReqAskName entries are not tested.
+//   build   an open-addressing table in HBM of the recorded directories: (layer, fp) and
+//           (layer, direct parent of fp) -> the lowest rank (header chain start) recorded, as
+//           TarSkipDirs::first_ and parent_first_.  A slot is owned by an entry index, claimed
+//           by compare-and-swap; a key is compared byte by byte with the owner's name.
+//   under   a regular survivor whose fp, or an ancestor of fp, is a recorded directory of its
+//           layer, or whose fp is the direct parent of one, with a rank below its own, becomes
+//           kReqSkipUnder.  On the names the device decides (clean, not empty, no ".."
+//           element) that is tar.go's underSkippedDir: filepath.Rel never fails there, and
+//           its result avoids the "../" prefix in exactly those three cases.
+//
+// kReqSkipFile and kReqSkipUnder entries stay in `regular`, are counted and have no record;
+// a kReqSkipDir entry has a record (fp + NUL, its rank in `start`), so the host knows the
+// recorded list for the names it was asked about.
 #pragma once
 #include <cstdint>
 
@@ -54,6 +76,10 @@ enum : uint8_t {
   kReqAskAllow = 5,  // a regular file up to the allow paths: the host runs the exact rules
   kReqAskName = 6,   // a name the device does not clean: the host runs ClassifyPath and Required
   kReqBad = 7,       // the record's name lies outside its layer's name blob
+  // only when the skip stage ran:
+  kReqSkipDir = 8,    // decided: a directory that skipDirs matches (recorded; it has a record)
+  kReqSkipFile = 9,   // decided: a regular file that skipFiles matches
+  kReqSkipUnder = 10, // decided: a regular file under a directory recorded before it
 };
 
 struct tsg_tar_file_rec {
@@ -63,7 +89,7 @@ struct tsg_tar_file_rec {
   uint64_t path_off;  // in the layer's part of the path blob; a NUL follows the path
   uint32_t path_len;
   uint8_t typeflag;   // as written (what kReqAskName's host half needs)
-  uint8_t verdict;    // kReqKeep, kReqAskAllow, kReqAskName
+  uint8_t verdict;    // kReqKeep, kReqAskAllow, kReqAskName; kReqSkipDir with skip options
   uint8_t all_rules;  // kReqAskAllow: run every allow rule (non-ASCII, or no PathTable)
   uint8_t pad;
   uint64_t rules;     // kReqAskAllow without all_rules: bit i = allow rule i has a literal in fp
@@ -77,22 +103,44 @@ struct TarRequiredRow {
 struct TarRequiredCounts {       // per layer
   uint64_t entries;              // all of the layer's entries
   uint64_t regular, whiteouts, opaque_dirs;  // among the decided entries (kReqAskName ones are the host's)
-  uint64_t records, path_bytes;  // what the layer has in the two outputs
-  uint64_t kept, dropped, ask_allow, ask_name, bad;  // verdict totals
+  uint64_t records, path_bytes;  // what the layer has in the two outputs (kReqSkipDir records included)
+  uint64_t kept, dropped, ask_allow, ask_name, bad;  // verdict totals (after the skip stage, where it ran)
   uint64_t ext_headers;          // the sum of the entries' n_ext (tsg_device_tar_stats.off_chain)
   uint64_t rec_first, path_first;  // where the layer's records / paths begin in the outputs
+  // the skip stage's verdict totals (zero where it did not run): pad[0] = kReqSkipDir,
+  // pad[1] = kReqSkipFile | kReqSkipUnder << 32 (a stage has fewer than 2^31 entries)
   uint64_t pad[2];
+  uint64_t skipped_dirs() const { return pad[0]; }
+  uint64_t skipped_files() const { return pad[1] & 0xFFFFFFFFu; }
+  uint64_t under_skipped_dir() const { return pad[1] >> 32; }
 };
 static_assert(sizeof(TarRequiredCounts) == 128, "sixteen 8-B words per layer");
 
 // The one device buffer of a stage over n entries of n_layers layers: byte offsets of its
 // parts (256-B aligned) and its size.  `tables` (rows, then the config base) is filled by
-// the host (TarRequiredTables) and uploaded.
+// the host (TarRequiredTables) and uploaded.  skip_tab: the TarSkipTable behind the config base,
+// part of `tables` and of the upload only when the stage was planned with skip options.
 struct TarRequiredLayout {
   uint64_t n = 0, name_bytes = 0;
   uint32_t n_layers = 0, cfg_len = 0;
-  uint64_t tables = 0, cfg = 0, counts = 0, dec = 0, rrank = 0, brank = 0, temp = 0, recs = 0, blob = 0;
+  bool skip = false;
+  uint64_t tables = 0, cfg = 0, skip_tab = 0, counts = 0, dec = 0, rrank = 0, brank = 0, temp = 0, recs = 0, blob = 0;
   uint64_t tables_bytes = 0, temp_bytes = 0, blob_cap = 0, bytes = 0;
 };
+
+// A slot of the skip stage's table: the entry (bit 31: the key is its direct parent) that claimed
+// it, and the lowest rank recorded for the key.  Empty: all ones.
+struct TarSkipSlot {
+  uint32_t owner, pad;
+  uint64_t rank;
+};
+static_assert(sizeof(TarSkipSlot) == 16, "one 16-B slot");
+// Slots for n_dirs recorded directories: every one may bring two keys, and the table is four
+// times the keys, rounded up to a power of two.
+inline uint64_t TarSkipSlots(uint64_t n_dirs) {
+  uint64_t s = 8;
+  while (s < 8 * n_dirs) s <<= 1;
+  return s;
+}
 
 }  // namespace tsg

@@ -14,6 +14,16 @@
 //            bases from the sums at its two ends.
 //  emit    : a lane per emitted entry writes the 48-B record and copies fp (or the raw
 //            name) and a NUL.
+//
+// With skip options three kernels go between decide and ranks (tarrequired.h says what they
+// decide); these use ordinary vector atomics on HBM -- a counter, a compare-and-swap per
+// claimed slot, a 64-bit minimum per key:
+//
+//  match   : a lane per entry, the patterns staged in LDS; bounded byte compares.
+//  build   : a lane per recorded directory inserts its path and its direct parent.
+//  under   : a lane per regular survivor reads fp once with a running hash, and looks up
+//            every ancestor at its '/', then fp itself in both roles.
+// A probe sequence ends at an empty slot or after as many steps as the table has slots.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +31,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "pathfilter.h"
+#include "tar_skip_dev.h"
 #include "tarindex.h"
 
 namespace tsg {
@@ -40,7 +51,7 @@ inline uint32_t GridFor(uint64_t items, uint32_t grid_cap) {
 // before its NUL; w = verdict | skip << 8 | n_ext << 16 | all_rules << 24, skip being where
 // those bytes begin in the raw name.
 __device__ __forceinline__ uint32_t dec_verdict(const uint4& d) { return d.w & 0xFFu; }
-__device__ __host__ __forceinline__ bool emits(uint32_t v) { return v >= kReqKeep && v <= kReqAskName; }
+__device__ __host__ __forceinline__ bool emits(uint32_t v) { return (v >= kReqKeep && v <= kReqAskName) || v == kReqSkipDir; }
 
 // The layer of entry i: the last row whose rec_base is at or below i (rows[n_layers].rec_base = n > i).
 __device__ __forceinline__ uint32_t layer_of(const TarRequiredRow* __restrict__ rows, uint32_t n_layers, uint64_t i) {
@@ -210,6 +221,156 @@ __global__ __launch_bounds__(kRThreads) void req_decide_kernel(const uint4* __re
   }
 }
 
+// ---- the skip stage ------------------------------------------------------------------
+// fp of entry i as the decide kernel found it (its verdict is not kReqBad): a view of the raw name.
+struct ReqName {
+  const uint8_t* fp;
+  uint32_t len, layer;
+};
+__device__ __forceinline__ ReqName name_of(const uint4* __restrict__ recs, const uint8_t* __restrict__ names,
+                                           const TarRequiredRow* __restrict__ rows, uint32_t n_layers,
+                                           const uint4* __restrict__ dec, uint64_t i) {
+  const uint4 w2 = recs[i * 4 + 2], d = dec[i];
+  ReqName r;
+  r.layer = layer_of(rows, n_layers, i);
+  r.fp = names + rows[r.layer].name_base + (uint64_t(w2.x) | (uint64_t(w2.y) << 32)) + ((d.w >> 8) & 0xFFu);
+  r.len = d.z;
+  return r;
+}
+__device__ __forceinline__ bool regular_verdict(uint32_t v) { return v == kReqDrop || v == kReqKeep || v == kReqAskAllow; }
+
+__global__ __launch_bounds__(kRThreads) void skip_match_kernel(const uint4* __restrict__ recs,
+                                                               const uint8_t* __restrict__ names, uint64_t n,
+                                                               const TarRequiredRow* __restrict__ rows, uint32_t n_layers,
+                                                               const TarSkipTable* __restrict__ pats,
+                                                               uint4* __restrict__ dec, uint32_t* __restrict__ n_dirs) {
+  __shared__ uint32_t s_words[sizeof(TarSkipTable) / 4];
+  for (uint32_t k = threadIdx.x; k < sizeof(TarSkipTable) / 4; k += kRThreads)
+    s_words[k] = reinterpret_cast<const uint32_t*>(pats)[k];
+  __syncthreads();
+  const TarSkipTable* s_pat = reinterpret_cast<const TarSkipTable*>(s_words);
+  for (uint64_t i = uint64_t(blockIdx.x) * kRThreads + threadIdx.x; i < n; i += uint64_t(gridDim.x) * kRThreads) {
+    const uint32_t w = dec[i].w, v = w & 0xFFu;
+    if (v != kReqOther && !regular_verdict(v)) continue;
+    const ReqName nm = name_of(recs, names, rows, n_layers, dec, i);
+    uint32_t to = v;
+    if (v == kReqOther) {
+      // a directory: typeflag '5', or '\0' (then the decide kernel saw trailing slashes: it is not regular)
+      const uint32_t typeflag = recs[i * 4 + 2].w & 0xFFu;
+      if ((typeflag == '5' || typeflag == 0) && TarSkipMatch(s_pat, false, nm.fp, nm.len)) {
+        to = kReqSkipDir;
+        atomicAdd(n_dirs, 1u);
+      }
+    } else if (TarSkipMatch(s_pat, true, nm.fp, nm.len)) {
+      to = kReqSkipFile;
+    }
+    if (to != v) dec[i].w = (w & ~0xFFu) | to;
+  }
+}
+
+constexpr uint32_t kSlotEmpty = 0xFFFFFFFFu;
+constexpr uint32_t kHash0 = 2166136261u, kHashMul = 16777619u;  // FNV-1a over fp's bytes, from the left
+__device__ __forceinline__ uint32_t slot_of(uint32_t h, uint32_t layer, uint32_t parent, uint32_t mask) {
+  uint32_t x = h ^ (layer * 0x9E3779B1u) ^ (parent ? 0x7F4A7C15u : 0u);
+  x ^= x >> 16;
+  x *= 0x85EBCA6Bu;
+  x ^= x >> 13;
+  x *= 0xC2B2AE35u;
+  x ^= x >> 16;
+  return x & mask;
+}
+// Is the key of a slot's owner (its fp, or the direct parent of its fp) the klen bytes at key, in `layer`?
+__device__ __forceinline__ bool owner_is(uint32_t owner, uint32_t parent, uint32_t layer, const uint8_t* __restrict__ key,
+                                         uint32_t klen, const uint4* __restrict__ recs,
+                                         const uint8_t* __restrict__ names, const TarRequiredRow* __restrict__ rows,
+                                         uint32_t n_layers, const uint4* __restrict__ dec) {
+  if ((owner >> 31) != parent) return false;
+  const ReqName o = name_of(recs, names, rows, n_layers, dec, owner & 0x7FFFFFFFu);
+  if (o.layer != layer || o.len < klen) return false;
+  if (parent ? (o.len == klen || o.fp[klen] != '/') : o.len != klen) return false;
+  for (uint32_t k = 0; k < klen; k++)
+    if (o.fp[k] != key[k]) return false;
+  if (parent)  // the direct parent: no further '/' below it
+    for (uint32_t k = klen + 1; k < o.len; k++)
+      if (o.fp[k] == '/') return false;
+  return true;
+}
+
+__global__ __launch_bounds__(kRThreads) void skip_build_kernel(const uint4* __restrict__ recs,
+                                                               const uint8_t* __restrict__ names, uint64_t n,
+                                                               const TarRequiredRow* __restrict__ rows, uint32_t n_layers,
+                                                               const uint4* __restrict__ dec,
+                                                               TarSkipSlot* __restrict__ tab, uint32_t mask) {
+  for (uint64_t i = uint64_t(blockIdx.x) * kRThreads + threadIdx.x; i < n; i += uint64_t(gridDim.x) * kRThreads) {
+    if ((dec[i].w & 0xFFu) != kReqSkipDir) continue;
+    const ReqName nm = name_of(recs, names, rows, n_layers, dec, i);
+    const uint4 w0 = recs[i * 4];
+    const unsigned long long rank = uint64_t(w0.x) | (uint64_t(w0.y) << 32);
+    uint32_t h = kHash0, h_parent = 0, parent_len = 0;
+    for (uint32_t j = 0; j < nm.len; j++) {
+      const uint32_t c = nm.fp[j];
+      if (c == '/') {
+        parent_len = j;
+        h_parent = h;
+      }
+      h = (h ^ c) * kHashMul;
+    }
+    for (uint32_t parent = 0; parent < 2; parent++) {
+      if (parent && parent_len == 0) break;  // (a clean fp has no '/' at 0)
+      const uint32_t klen = parent ? parent_len : nm.len, me = uint32_t(i) | (parent << 31);
+      uint32_t slot = slot_of(parent ? h_parent : h, nm.layer, parent, mask);
+      for (uint32_t step = 0; step <= mask; step++, slot = (slot + 1) & mask) {
+        const uint32_t was = atomicCAS(&tab[slot].owner, kSlotEmpty, me);
+        if (was == kSlotEmpty || was == me ||
+            owner_is(was, parent, nm.layer, nm.fp, klen, recs, names, rows, n_layers, dec)) {
+          atomicMin(reinterpret_cast<unsigned long long*>(&tab[slot].rank), rank);
+          break;
+        }
+      }
+    }
+  }
+}
+
+// The lowest rank recorded for a key; all ones: none.
+__device__ __forceinline__ uint64_t skip_find(const TarSkipSlot* __restrict__ tab, uint32_t mask, uint32_t h, uint32_t parent,
+                                              uint32_t layer, const uint8_t* __restrict__ key, uint32_t klen,
+                                              const uint4* __restrict__ recs, const uint8_t* __restrict__ names,
+                                              const TarRequiredRow* __restrict__ rows, uint32_t n_layers,
+                                              const uint4* __restrict__ dec) {
+  uint32_t slot = slot_of(h, layer, parent, mask);
+  for (uint32_t step = 0; step <= mask; step++, slot = (slot + 1) & mask) {
+    const uint32_t owner = tab[slot].owner;
+    if (owner == kSlotEmpty) break;
+    if (owner_is(owner, parent, layer, key, klen, recs, names, rows, n_layers, dec)) return tab[slot].rank;
+  }
+  return ~uint64_t(0);
+}
+
+__global__ __launch_bounds__(kRThreads) void skip_under_kernel(const uint4* __restrict__ recs,
+                                                               const uint8_t* __restrict__ names, uint64_t n,
+                                                               const TarRequiredRow* __restrict__ rows, uint32_t n_layers,
+                                                               uint4* __restrict__ dec,
+                                                               const TarSkipSlot* __restrict__ tab, uint32_t mask) {
+  for (uint64_t i = uint64_t(blockIdx.x) * kRThreads + threadIdx.x; i < n; i += uint64_t(gridDim.x) * kRThreads) {
+    const uint32_t w = dec[i].w;
+    if (!regular_verdict(w & 0xFFu)) continue;
+    const ReqName nm = name_of(recs, names, rows, n_layers, dec, i);
+    const uint4 w0 = recs[i * 4];
+    const uint64_t rank = uint64_t(w0.x) | (uint64_t(w0.y) << 32);
+    uint32_t h = kHash0;
+    bool under = false;
+    for (uint32_t j = 0; j < nm.len && !under; j++) {
+      const uint32_t c = nm.fp[j];
+      if (c == '/')  // an ancestor of fp
+        under = skip_find(tab, mask, h, 0, nm.layer, nm.fp, j, recs, names, rows, n_layers, dec) < rank;
+      h = (h ^ c) * kHashMul;
+    }
+    under = under || skip_find(tab, mask, h, 0, nm.layer, nm.fp, nm.len, recs, names, rows, n_layers, dec) < rank ||
+            skip_find(tab, mask, h, 1, nm.layer, nm.fp, nm.len, recs, names, rows, n_layers, dec) < rank;
+    if (under) dec[i].w = (w & ~0xFFu) | kReqSkipUnder;
+  }
+}
+
 // The inputs of the two rank scans: whether entry i has a record, and its bytes in the blob.
 struct ReqFlag {
   const uint4* dec;
@@ -225,7 +386,8 @@ struct ReqBytes {
 using ReqFlagIter = hipcub::TransformInputIterator<uint64_t, ReqFlag, hipcub::CountingInputIterator<uint32_t>>;
 using ReqBytesIter = hipcub::TransformInputIterator<uint64_t, ReqBytes, hipcub::CountingInputIterator<uint32_t>>;
 
-constexpr int kCountSlots = 9;  // the eight verdicts and the extension headers
+constexpr int kVerdicts = 11;
+constexpr int kCountSlots = kVerdicts + 1;  // the verdicts and the extension headers
 
 __global__ __launch_bounds__(kRThreads) void req_totals_kernel(const uint4* __restrict__ dec,
                                                                const uint64_t* __restrict__ rrank,
@@ -240,8 +402,8 @@ __global__ __launch_bounds__(kRThreads) void req_totals_kernel(const uint4* __re
     for (uint64_t i = i0 + threadIdx.x; i < i1; i += kRThreads) {
       const uint32_t w = dec[i].w;
 #pragma unroll
-      for (int v = 0; v < 8; v++) cnt[v] += (w & 0xFFu) == uint32_t(v);
-      cnt[8] += (w >> 16) & 0xFFu;
+      for (int v = 0; v < kVerdicts; v++) cnt[v] += (w & 0xFFu) == uint32_t(v);
+      cnt[kVerdicts] += (w >> 16) & 0xFFu;
     }
 #pragma unroll
     for (int v = 0; v < kCountSlots; v++) {
@@ -260,7 +422,7 @@ __global__ __launch_bounds__(kRThreads) void req_totals_kernel(const uint4* __re
       const uint64_t b0 = i0 ? brank[i0 - 1] : 0, b1 = i1 ? brank[i1 - 1] : 0;
       TarRequiredCounts c;
       c.entries = i1 - i0;
-      c.regular = t[kReqDrop] + t[kReqKeep] + t[kReqAskAllow];
+      c.regular = t[kReqDrop] + t[kReqKeep] + t[kReqAskAllow] + t[kReqSkipFile] + t[kReqSkipUnder];
       c.whiteouts = t[kReqWhiteout];
       c.opaque_dirs = t[kReqOpaque];
       c.records = r1 - r0;
@@ -270,10 +432,11 @@ __global__ __launch_bounds__(kRThreads) void req_totals_kernel(const uint4* __re
       c.ask_allow = t[kReqAskAllow];
       c.ask_name = t[kReqAskName];
       c.bad = t[kReqBad];
-      c.ext_headers = t[8];
+      c.ext_headers = t[kVerdicts];
       c.rec_first = r0;
       c.path_first = b0;
-      c.pad[0] = c.pad[1] = 0;
+      c.pad[0] = t[kReqSkipDir];
+      c.pad[1] = t[kReqSkipFile] | (t[kReqSkipUnder] << 32);
       counts[l] = c;
     }
     __syncthreads();
@@ -315,13 +478,15 @@ __global__ __launch_bounds__(kRThreads) void req_emit_kernel(const uint4* __rest
 
 }  // namespace
 
-bool TarRequiredPlan(uint64_t n, uint32_t n_layers, uint64_t name_bytes, uint32_t cfg_len, TarRequiredLayout* L) {
+bool TarRequiredPlan(uint64_t n, uint32_t n_layers, uint64_t name_bytes, uint32_t cfg_len, TarRequiredLayout* L,
+                     bool skip) {
   if (n_layers == 0 || n >= (uint64_t(1) << 31)) return false;
   *L = TarRequiredLayout();
   L->n = n;
   L->n_layers = n_layers;
   L->name_bytes = name_bytes;
   L->cfg_len = cfg_len;
+  L->skip = skip;
   size_t t1 = 0, t2 = 0;
   const int items = int(std::max<uint64_t>(n, 1));
   (void)hipcub::DeviceScan::InclusiveSum(nullptr, t1, ReqFlagIter(hipcub::CountingInputIterator<uint32_t>(0), ReqFlag{nullptr}),
@@ -331,7 +496,7 @@ bool TarRequiredPlan(uint64_t n, uint32_t n_layers, uint64_t name_bytes, uint32_
                                          static_cast<uint64_t*>(nullptr), items);
   L->temp_bytes = std::max({t1, t2, size_t(256)});
   const uint64_t row_bytes = (uint64_t(n_layers) + 1) * sizeof(TarRequiredRow);
-  L->tables_bytes = Up256(row_bytes) + Up256(cfg_len);
+  L->tables_bytes = Up256(row_bytes) + Up256(cfg_len) + (skip ? Up256(sizeof(TarSkipTable)) : 0);
   L->blob_cap = name_bytes + n;  // every name and its NUL
   uint64_t at = 0;
   auto take = [&](uint64_t bytes) {
@@ -341,6 +506,7 @@ bool TarRequiredPlan(uint64_t n, uint32_t n_layers, uint64_t name_bytes, uint32_
   };
   L->tables = take(L->tables_bytes);
   L->cfg = L->tables + Up256(row_bytes);
+  L->skip_tab = L->cfg + Up256(cfg_len);
   L->counts = take(uint64_t(n_layers) * sizeof(TarRequiredCounts));
   L->dec = take(n * 16);
   L->rrank = take(n * 8);
@@ -353,23 +519,28 @@ bool TarRequiredPlan(uint64_t n, uint32_t n_layers, uint64_t name_bytes, uint32_
 }
 
 void TarRequiredTables(const TarRequiredLayout& L, const uint64_t* rec_base, const uint64_t* name_base, const char* cfg,
-                       uint8_t* h_tables) {
+                       uint8_t* h_tables, const TarSkipTable* skip) {
   std::memset(h_tables, 0, size_t(L.tables_bytes));
   TarRequiredRow* rows = reinterpret_cast<TarRequiredRow*>(h_tables);
   for (uint32_t k = 0; k <= L.n_layers; k++) rows[k] = TarRequiredRow{rec_base[k], name_base[k]};
   if (L.cfg_len) std::memcpy(h_tables + (L.cfg - L.tables), cfg, L.cfg_len);
+  if (L.skip && skip) std::memcpy(h_tables + (L.skip_tab - L.tables), skip, sizeof(TarSkipTable));
 }
 
 hipError_t TarRequiredRun(const TarRequiredLayout& L, const uint8_t* h_tables, const uint8_t* d_records,
                           const uint8_t* d_names, const PathTable* d_path, const SureTable* d_sure, uint8_t* d_req,
                           uint32_t grid_cap, hipStream_t s) {
+  const hipError_t e = TarRequiredDecide(L, h_tables, d_records, d_names, d_path, d_sure, d_req, grid_cap, s);
+  return e != hipSuccess ? e : TarRequiredFinish(L, d_records, d_names, d_req, grid_cap, s);
+}
+
+hipError_t TarRequiredDecide(const TarRequiredLayout& L, const uint8_t* h_tables, const uint8_t* d_records,
+                             const uint8_t* d_names, const PathTable* d_path, const SureTable* d_sure, uint8_t* d_req,
+                             uint32_t grid_cap, hipStream_t s) {
   hipError_t e = hipMemcpyAsync(d_req + L.tables, h_tables, L.tables_bytes, hipMemcpyHostToDevice, s);
   if (e != hipSuccess) return e;
   const TarRequiredRow* rows = reinterpret_cast<const TarRequiredRow*>(d_req + L.tables);
-  TarRequiredCounts* counts = reinterpret_cast<TarRequiredCounts*>(d_req + L.counts);
   uint4* dec = reinterpret_cast<uint4*>(d_req + L.dec);
-  uint64_t* rrank = reinterpret_cast<uint64_t*>(d_req + L.rrank);
-  uint64_t* brank = reinterpret_cast<uint64_t*>(d_req + L.brank);
   const uint4* recs = reinterpret_cast<const uint4*>(d_records);
   const uint64_t n = L.n;
   if (n) {
@@ -384,6 +555,48 @@ hipError_t TarRequiredRun(const TarRequiredLayout& L, const uint8_t* h_tables, c
       req_decide_kernel<false, false><<<grid, kRThreads, 0, s>>>(recs, d_names, n, rows, L.n_layers, L.name_bytes,
                                                                  d_req + L.cfg, L.cfg_len, nullptr, nullptr, dec);
     if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t TarSkipMatchRun(const TarRequiredLayout& L, const uint8_t* d_records, const uint8_t* d_names, uint8_t* d_req,
+                           uint32_t* d_n_dirs, uint32_t grid_cap, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(d_n_dirs, 0, 4, s);
+  if (e != hipSuccess || L.n == 0) return e;
+  if (!L.skip) return hipErrorInvalidValue;
+  skip_match_kernel<<<GridFor((L.n + kRThreads - 1) / kRThreads, grid_cap), kRThreads, 0, s>>>(
+      reinterpret_cast<const uint4*>(d_records), d_names, L.n, reinterpret_cast<const TarRequiredRow*>(d_req + L.tables),
+      L.n_layers, reinterpret_cast<const TarSkipTable*>(d_req + L.skip_tab), reinterpret_cast<uint4*>(d_req + L.dec),
+      d_n_dirs);
+  return hipGetLastError();
+}
+
+hipError_t TarSkipUnderRun(const TarRequiredLayout& L, const uint8_t* d_records, const uint8_t* d_names, uint8_t* d_req,
+                           TarSkipSlot* d_table, uint64_t slots, uint32_t grid_cap, hipStream_t s) {
+  if (L.n == 0 || slots < 2 || (slots & (slots - 1)) || slots > (uint64_t(1) << 31)) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(d_table, 0xFF, slots * sizeof(TarSkipSlot), s);
+  if (e != hipSuccess) return e;
+  const uint32_t grid = GridFor((L.n + kRThreads - 1) / kRThreads, grid_cap);
+  const uint4* recs = reinterpret_cast<const uint4*>(d_records);
+  const TarRequiredRow* rows = reinterpret_cast<const TarRequiredRow*>(d_req + L.tables);
+  uint4* dec = reinterpret_cast<uint4*>(d_req + L.dec);
+  skip_build_kernel<<<grid, kRThreads, 0, s>>>(recs, d_names, L.n, rows, L.n_layers, dec, d_table, uint32_t(slots - 1));
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  skip_under_kernel<<<grid, kRThreads, 0, s>>>(recs, d_names, L.n, rows, L.n_layers, dec, d_table, uint32_t(slots - 1));
+  return hipGetLastError();
+}
+
+hipError_t TarRequiredFinish(const TarRequiredLayout& L, const uint8_t* d_records, const uint8_t* d_names,
+                             uint8_t* d_req, uint32_t grid_cap, hipStream_t s) {
+  hipError_t e = hipSuccess;
+  const TarRequiredRow* rows = reinterpret_cast<const TarRequiredRow*>(d_req + L.tables);
+  TarRequiredCounts* counts = reinterpret_cast<TarRequiredCounts*>(d_req + L.counts);
+  uint4* dec = reinterpret_cast<uint4*>(d_req + L.dec);
+  uint64_t* rrank = reinterpret_cast<uint64_t*>(d_req + L.rrank);
+  uint64_t* brank = reinterpret_cast<uint64_t*>(d_req + L.brank);
+  const uint4* recs = reinterpret_cast<const uint4*>(d_records);
+  const uint64_t n = L.n;
+  if (n) {
     size_t tb = L.temp_bytes;
     if ((e = hipcub::DeviceScan::InclusiveSum(d_req + L.temp, tb,
                                               ReqFlagIter(hipcub::CountingInputIterator<uint32_t>(0), ReqFlag{dec}), rrank,

@@ -57,6 +57,54 @@ int tsg_debug_transform_census(int device, const uint8_t* raw, uint64_t n_bytes,
  * the kernel and read back after it, so every byte no file owns returns as given. */
 int tsg_debug_gather_device(int device, const uint8_t* raw, uint64_t n_bytes, const uint64_t* src_off,
                             const uint64_t* dst_off, uint32_t n_files, uint8_t* out);
+/* ---- the kernels that only move file bytes ----
+ * Each is one synchronous call on HIP device `device`; the device allocations
+ * have exactly the sizes stated; the argument checks come before any HIP call
+ * (-2, text via tsg_last_error()); a HIP error is -1.
+ *
+ * The gather of transformed files (trivy_amd/csrc/xform.hip GatherFiles).  src
+ * holds n_bytes + 64 bytes, uploaded as given (the caller chooses the tail);
+ * xoff has n_files + 1 ascending entries ending at or before n_bytes; `files`
+ * lists n file ids in any order and dst_off their n destinations: file files[i]
+ * lands at out + dst_off[i].  out holds dst_bytes + 64 bytes; it is uploaded
+ * before the kernel and read back after it, so every byte no file owns returns
+ * as given.  Destinations that leave dst_bytes or overlap are refused. */
+int tsg_debug_gather_files(int device, const uint8_t* src, uint64_t n_bytes, const uint64_t* xoff, uint32_t n_files,
+                           const uint32_t* files, const uint64_t* dst_off, uint32_t n, uint8_t* out,
+                           uint64_t dst_bytes);
+/* The gather from mapped host memory (xform.hip GatherHostFiles).  The n_bytes
+ * of src are copied into page-locked host memory mapped into the device's
+ * address space, which the kernel reads through its device pointer, as in
+ * production.  File i is src[src_off[i] .. src_off[i] + len[i]) and lands at
+ * out + dst_off[i]; the (file, piece) items are built as the engine builds
+ * them, one per 16 KiB.  out and dst_bytes as above.  A file with src_off < 32
+ * or src_off + len + 32 > n_bytes is refused: the kernel's aligned loads touch
+ * up to 30 bytes before a file and 31 after it. */
+int tsg_debug_gather_host(int device, const uint8_t* src, uint64_t n_bytes, const uint64_t* src_off,
+                          const uint64_t* len, const uint64_t* dst_off, uint32_t n_files, uint8_t* out,
+                          uint64_t dst_bytes);
+/* The files fetch of device-only batches (trivy_amd/csrc/fetch.hip): FetchPlan,
+ * then the FetchPack rounds as GpuEngine::IssueFetch drives them.  The arena is
+ * uploaded into an allocation of exactly n_bytes + 64 (the tail 0xEE); offsets
+ * run from 0 to n_bytes.  The marked files come either from 64-B Candidate
+ * records (flags NULL: the device buffer holds min(n_cands, cand_cap) records
+ * while the device count says n_cands) or from `flags`, one u32 per file (cands
+ * NULL, n_cands 0: the route FetchPlan takes without a candidate list).
+ * stage_bytes is rounded down to 16 KiB, at least one; copy_bytes 0 means the
+ * plan's packed_bytes, else a multiple of 16 below or above it.  The staging
+ * allocation of stage_bytes + 64 is filled with 0xA5 before each round; a
+ * round's bytes [0, w1 - w0) go to packed_out + w0, and a byte from there to the
+ * allocation's end that is no longer 0xA5 is -4 (the text names round and
+ * offset).  -3: packed_cap is below the bytes to copy.  list_out (n_files
+ * entries) and lpoff_out (n_files + 1) receive the n_packed ids and n_packed + 1
+ * packed offsets of the compacted list.  counters: packed_bytes, n_packed,
+ * n_direct, n_files, file_bytes (fetch.h FetchCounters), rounds.  Files of
+ * direct_bytes or more are counted, not copied. */
+int tsg_debug_fetch_files_device(int device, const uint8_t* arena, uint64_t n_bytes, const uint64_t* offsets,
+                                 uint32_t n_files, const void* cands, uint64_t n_cands, uint32_t cand_cap,
+                                 const uint32_t* flags, uint64_t direct_bytes, uint64_t stage_bytes,
+                                 uint64_t copy_bytes, uint8_t* packed_out, uint64_t packed_cap, uint32_t* list_out,
+                                 uint64_t* lpoff_out, uint64_t counters[6]);
 /* regexp.MatchString: 1 = match, 0 = no match, <0 = compile error. */
 int tsg_regex_match(const char* pattern, const uint8_t* text, uint64_t n);
 

@@ -156,9 +156,9 @@ typedef struct tsg_batch_ext {
    * device-mapped host memory (tsg_host_register_mapped; a tar layer as the
    * analyzer's collectors hold it): the GPU gathers them itself, no host copy.
    * host_offsets still lay out the batch (the files back to back).  The GPU
-   * reads aligned 16-B blocks: the 16 bytes before each file's data and the 32
-   * after its end must lie in the mapped region too (a tar's 512-B headers and
-   * padding provide them). */
+   * reads aligned 16-B blocks: the 32 bytes before each file's data and the 32
+   * after its end must lie in the mapped region too (the loads touch up to 30
+   * before and 31 after; a tar's 512-B headers and padding provide them). */
   const uint8_t* gather_base;
   const uint64_t* gather_src;
 } tsg_batch_ext;

@@ -120,6 +120,106 @@ def gather_device(raw: bytes, src_off, dst_off, out: bytes, tail: bytes = b"", d
     return ob.raw
 
 
+FETCH_SEG = 16384  # csrc/fetch.h kFetchSeg
+
+
+class HookRefused(ValueError):
+    """A debug hook's argument check refused the call (-2) before any HIP call."""
+
+
+def _hook_rc(L, rc):
+    if rc == -2:
+        raise HookRefused(last_error(L))
+    if rc != 0:
+        raise RuntimeError("rc %d: %s" % (rc, last_error(L)))
+
+
+def _u64s(xs, at_least=1):
+    xs = [int(x) for x in xs]
+    return (ctypes.c_uint64 * max(at_least, len(xs)))(*xs)
+
+
+def gather_files(src: bytes, xoff, files, dst_off, out: bytes, tail: bytes = b"", device=0) -> bytes:
+    """tsg_debug_gather_files: `out` (dst_bytes + 64) with file files[i], src[xoff[f] .. xoff[f + 1]), written at
+    dst_off[i]; every other byte of it as given.  tail: up to 64 bytes placed behind src (0x00 after)."""
+    L = lib()
+    c = ctypes
+    n_files, n = len(xoff) - 1, len(files)
+    if len(dst_off) != n or len(out) < 64 or len(tail) > 64:
+        raise ValueError("gather_files: one destination per listed file, an output of dst_bytes + 64 bytes")
+    buf = c.create_string_buffer(bytes(src) + bytes(tail).ljust(64, b"\0"), len(src) + 64)
+    fl = (c.c_uint32 * max(1, n))(*[int(x) for x in files])
+    ob = c.create_string_buffer(bytes(out), len(out))
+    L.tsg_debug_gather_files.restype = c.c_int
+    L.tsg_debug_gather_files.argtypes = [c.c_int, c.c_void_p, c.c_uint64, c.c_void_p, c.c_uint32, c.c_void_p,
+                                         c.c_void_p, c.c_uint32, c.c_void_p, c.c_uint64]
+    _hook_rc(L, L.tsg_debug_gather_files(int(device), buf, len(src), _u64s(xoff), n_files, fl, _u64s(dst_off), n, ob,
+                                         len(out) - 64))
+    return ob.raw
+
+
+def gather_host(src: bytes, src_off, lens, dst_off, out: bytes, device=0) -> bytes:
+    """tsg_debug_gather_host: `out` (dst_bytes + 64) with file i, src[src_off[i] .. + lens[i]) read from mapped host
+    memory, written at dst_off[i]; every other byte of it as given."""
+    L = lib()
+    c = ctypes
+    n = len(src_off)
+    if len(lens) != n or len(dst_off) != n or len(out) < 64:
+        raise ValueError("gather_host: a source, a length and a destination per file, an output of dst_bytes + 64")
+    buf = c.create_string_buffer(bytes(src), max(1, len(src)))
+    ob = c.create_string_buffer(bytes(out), len(out))
+    L.tsg_debug_gather_host.restype = c.c_int
+    L.tsg_debug_gather_host.argtypes = [c.c_int, c.c_void_p, c.c_uint64, c.c_void_p, c.c_void_p, c.c_void_p,
+                                        c.c_uint32, c.c_void_p, c.c_uint64]
+    _hook_rc(L, L.tsg_debug_gather_host(int(device), buf, len(src), _u64s(src_off), _u64s(lens), _u64s(dst_off), n, ob,
+                                        len(out) - 64))
+    return ob.raw
+
+
+def fetch_files_device(arena: bytes, offsets, flags=None, cands=None, n_cands=None, cand_cap=None, direct_bytes=1 << 62,
+                       stage_bytes=1 << 22, copy_bytes=0, device=0):
+    """tsg_debug_fetch_files_device.  The marked files: `flags` (one per file, nonzero: fetch) or `cands` (64-B
+    Candidate records as bytes; n_cands, default the records given, is what the device count says; cand_cap, default
+    the same, bounds the records uploaded).  -> dict: packed (bytes: copy_bytes, or packed_bytes when 0), list,
+    lpoff, and the counters packed_bytes, n_packed, n_direct, n_files, file_bytes, rounds."""
+    L = lib()
+    c = ctypes
+    n_files = len(offsets) - 1
+    if flags is not None:
+        if len(flags) != n_files:
+            raise ValueError("fetch_files_device: one flag per file")
+        fl = (c.c_uint32 * max(1, n_files))(*[int(x) for x in flags])
+        cb, nc, cap = None, 0, 0
+    else:
+        fl = None
+        cands = bytes(cands or b"")
+        nc = len(cands) // 64 if n_cands is None else int(n_cands)
+        cap = nc if cand_cap is None else int(cand_cap)
+        cb = c.create_string_buffer(cands, max(1, len(cands)))
+    off = _u64s(offsets)
+    # every file rounded up to 16 bounds the plan's packed_bytes
+    packed_cap = int(copy_bytes) if copy_bytes else len(arena) + 16 * n_files + 16
+    packed = c.create_string_buffer(max(1, packed_cap))
+    lst = (c.c_uint32 * (n_files + 1))()
+    lpoff = (c.c_uint64 * (n_files + 2))()
+    ctr = (c.c_uint64 * 6)()
+    ab = c.create_string_buffer(bytes(arena), max(1, len(arena)))
+    L.tsg_debug_fetch_files_device.restype = c.c_int
+    L.tsg_debug_fetch_files_device.argtypes = [c.c_int, c.c_void_p, c.c_uint64, c.c_void_p, c.c_uint32, c.c_void_p,
+                                               c.c_uint64, c.c_uint32, c.c_void_p, c.c_uint64, c.c_uint64, c.c_uint64,
+                                               c.c_void_p, c.c_uint64, c.c_void_p, c.c_void_p, c.c_void_p]
+    _hook_rc(L, L.tsg_debug_fetch_files_device(int(device), ab, len(arena), off, n_files, cb, nc, cap, fl,
+                                               int(direct_bytes), int(stage_bytes), int(copy_bytes), packed,
+                                               packed_cap, lst, lpoff, ctr))
+    names = ("packed_bytes", "n_packed", "n_direct", "n_files", "file_bytes", "rounds")
+    r = dict(zip(names, (int(x) for x in ctr)))
+    n_packed = r["n_packed"]
+    r["packed"] = packed.raw[:int(copy_bytes) if copy_bytes else r["packed_bytes"]]
+    r["list"] = list(lst[:n_packed])
+    r["lpoff"] = list(lpoff[:n_packed + 1])
+    return r
+
+
 def go_bytes_to_lower(b: bytes) -> bytes:
     out = ctypes.create_string_buffer(len(b) * 3 + 4)
     n = lib().tsg_go_bytes_to_lower(b, len(b), out, len(out))

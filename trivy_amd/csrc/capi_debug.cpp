@@ -6,11 +6,13 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "capi_internal.h"
 #include "census.h"
 #include "classify.h"
+#include "fetch.h"
 #include "fetch_host.h"
 #include "fetch_windows.h"
 #include "filter.h"
@@ -225,6 +227,250 @@ int tsg_debug_gather_device(int device, const uint8_t* raw, uint64_t n_bytes, co
     return -1;
   }
   return 0;
+}
+
+// The destinations [dst_off[i], dst_off[i] + len(i)) lie inside dst_bytes and no two of them share a byte.
+static bool GatherDstOk(const char* who, const uint64_t* dst_off, const std::vector<uint64_t>& len,
+                        uint64_t dst_bytes) {
+  std::vector<std::pair<uint64_t, uint64_t>> span;
+  for (size_t i = 0; i < len.size(); i++) {
+    if (dst_off[i] > dst_bytes || len[i] > dst_bytes - dst_off[i]) {
+      tsg::SetError(std::string(who) + ": a destination leaves the output");
+      return false;
+    }
+    if (len[i]) span.emplace_back(dst_off[i], dst_off[i] + len[i]);
+  }
+  std::sort(span.begin(), span.end());
+  for (size_t i = 1; i < span.size(); i++)
+    if (span[i].first < span[i - 1].second) {
+      tsg::SetError(std::string(who) + ": two destinations overlap");
+      return false;
+    }
+  return true;
+}
+
+int tsg_debug_gather_files(int device, const uint8_t* src, uint64_t n_bytes, const uint64_t* xoff, uint32_t n_files,
+                           const uint32_t* files, const uint64_t* dst_off, uint32_t n, uint8_t* out,
+                           uint64_t dst_bytes) {
+  const char* who = "tsg_debug_gather_files";
+  if (!src || !xoff || !out || (n && (!files || !dst_off))) {
+    tsg::SetError(std::string(who) + ": NULL argument");
+    return -2;
+  }
+  for (uint32_t f = 0; f < n_files; f++)
+    if (xoff[f + 1] < xoff[f]) {
+      tsg::SetError(std::string(who) + ": offsets must ascend");
+      return -2;
+    }
+  if (xoff[n_files] > n_bytes) {
+    tsg::SetError(std::string(who) + ": a file leaves the arena");
+    return -2;
+  }
+  std::vector<uint64_t> len(n);
+  for (uint32_t i = 0; i < n; i++) {
+    if (files[i] >= n_files) {
+      tsg::SetError(std::string(who) + ": no such file");
+      return -2;
+    }
+    len[i] = xoff[files[i] + 1] - xoff[files[i]];
+  }
+  if (!GatherDstOk(who, dst_off, len, dst_bytes)) return -2;
+  void *d_src = nullptr, *d_xoff = nullptr, *d_files = nullptr, *d_dst = nullptr, *d_out = nullptr;
+  hipStream_t s = nullptr;
+  hipError_t e = hipSetDevice(device);
+  auto ok = [&](hipError_t r) {
+    if (e == hipSuccess) e = r;
+    return e == hipSuccess;
+  };
+  if (ok(e) && ok(hipStreamCreate(&s)) && ok(hipMalloc(&d_src, n_bytes + 64)) &&
+      ok(hipMalloc(&d_xoff, (size_t(n_files) + 1) * 8)) && ok(hipMalloc(&d_files, (size_t(n) + 1) * 4)) &&
+      ok(hipMalloc(&d_dst, (size_t(n) + 1) * 8)) && ok(hipMalloc(&d_out, dst_bytes + 64)) &&
+      ok(hipMemcpy(d_src, src, n_bytes + 64, hipMemcpyHostToDevice)) &&  // (the caller's tail with it)
+      ok(hipMemcpy(d_xoff, xoff, (size_t(n_files) + 1) * 8, hipMemcpyHostToDevice)) &&
+      (n == 0 || (ok(hipMemcpy(d_files, files, size_t(n) * 4, hipMemcpyHostToDevice)) &&
+                  ok(hipMemcpy(d_dst, dst_off, size_t(n) * 8, hipMemcpyHostToDevice)))) &&
+      ok(hipMemcpy(d_out, out, dst_bytes + 64, hipMemcpyHostToDevice)) &&  // (what no file owns comes back as it was)
+      ok(tsg::GatherFiles(static_cast<const uint8_t*>(d_src), static_cast<const uint64_t*>(d_xoff),
+                          static_cast<const uint32_t*>(d_files), static_cast<const uint64_t*>(d_dst), n,
+                          static_cast<uint8_t*>(d_out), s)) &&
+      ok(hipStreamSynchronize(s)))
+    ok(hipMemcpy(out, d_out, dst_bytes + 64, hipMemcpyDeviceToHost));
+  for (void* p : {d_src, d_xoff, d_files, d_dst, d_out})
+    if (p) (void)hipFree(p);
+  if (s) (void)hipStreamDestroy(s);
+  if (e != hipSuccess) {
+    tsg::SetError(std::string(who) + ": " + hipGetErrorString(e));
+    return -1;
+  }
+  return 0;
+}
+
+// gather_host_kernel's read contract (xform.hip), per item [d0, d1) of a file whose byte d0 has the
+// source s0: with b_lo = d0 & ~15 the first destination block's source is b_lo + s0 - d0 = s0 - (d0 & 15)
+// >= s0 - 15, and a_lo is that rounded down to 16, so a_lo >= s0 - 15 - 15: up to 30 bytes before the
+// item (before the file, for its first item).  A lane loads block j at a_lo + 16 j while b_lo + 16 j <
+// d1 + 16, i.e. b_lo + 16 j <= d1 + 15 -- lane 63's extra load obeys the same bound -- and a_lo <= b_lo +
+// s0 - d0, so the load ends at a_lo + 16 j + 16 <= (d1 + s0 - d0) + 15 + 16: up to 31 bytes past the
+// item's last source byte (past the file, for its last item).  The hook asks for 32 on either side.
+int tsg_debug_gather_host(int device, const uint8_t* src, uint64_t n_bytes, const uint64_t* src_off,
+                          const uint64_t* len, const uint64_t* dst_off, uint32_t n_files, uint8_t* out,
+                          uint64_t dst_bytes) {
+  const char* who = "tsg_debug_gather_host";
+  if (!out || (n_bytes && !src) || (n_files && (!src_off || !len || !dst_off)) || n_files > 0x7FFFFFFFu) {
+    tsg::SetError(std::string(who) + ": NULL argument");
+    return -2;
+  }
+  // The kernel takes a file's end from the next file's start.  Here a file is entry 2 i of the offsets
+  // and entry 2 i + 1 (a file without items) holds its end, so the destinations need not be contiguous.
+  std::vector<uint64_t> so(2 * size_t(n_files) + 1, 0), dofs(2 * size_t(n_files) + 1, 0);
+  std::vector<tsg::GatherItem> items;
+  for (uint32_t f = 0; f < n_files; f++) {
+    if (src_off[f] < 32 || src_off[f] > n_bytes || len[f] > n_bytes - src_off[f] ||
+        n_bytes - src_off[f] - len[f] < 32) {
+      tsg::SetError(std::string(who) + ": file " + std::to_string(f) +
+                    " lacks the 32 readable bytes before or after it");
+      return -2;
+    }
+    so[2 * size_t(f)] = src_off[f];
+    dofs[2 * size_t(f)] = dst_off[f];
+    dofs[2 * size_t(f) + 1] = dst_off[f] + len[f];
+    for (uint32_t q = 0; uint64_t(q) * tsg::kGatherPiece < len[f]; q++) items.push_back(tsg::GatherItem{2 * f, q});
+  }
+  if (!GatherDstOk(who, dst_off, std::vector<uint64_t>(len, len + n_files), dst_bytes)) return -2;
+  const size_t item_bytes = items.size() * sizeof(tsg::GatherItem);
+  void *h_src = nullptr, *d_view = nullptr, *d_so = nullptr, *d_dofs = nullptr, *d_items = nullptr, *d_out = nullptr;
+  hipStream_t s = nullptr;
+  hipError_t e = hipSetDevice(device);
+  auto ok = [&](hipError_t r) {
+    if (e == hipSuccess) e = r;
+    return e == hipSuccess;
+  };
+  // the source as production has it: page-locked host memory mapped into the device's address space
+  if (ok(e) && ok(hipStreamCreate(&s)) &&
+      ok(hipHostMalloc(&h_src, std::max<uint64_t>(n_bytes, 1), hipHostMallocMapped)) &&
+      ok(hipHostGetDevicePointer(&d_view, h_src, 0)) && ok(hipMalloc(&d_so, so.size() * 8)) &&
+      ok(hipMalloc(&d_dofs, dofs.size() * 8)) && ok(hipMalloc(&d_items, item_bytes + 8)) &&
+      ok(hipMalloc(&d_out, dst_bytes + 64))) {
+    if (n_bytes) std::memcpy(h_src, src, n_bytes);
+    if (ok(hipMemcpy(d_so, so.data(), so.size() * 8, hipMemcpyHostToDevice)) &&
+        ok(hipMemcpy(d_dofs, dofs.data(), dofs.size() * 8, hipMemcpyHostToDevice)) &&
+        (items.empty() || ok(hipMemcpy(d_items, items.data(), item_bytes, hipMemcpyHostToDevice))) &&
+        ok(hipMemcpy(d_out, out, dst_bytes + 64, hipMemcpyHostToDevice)) &&  // (what no file owns comes back as it was)
+        ok(tsg::GatherHostFiles(static_cast<const uint8_t*>(d_view), static_cast<const uint64_t*>(d_so),
+                                static_cast<const uint64_t*>(d_dofs), static_cast<const tsg::GatherItem*>(d_items),
+                                uint32_t(items.size()), static_cast<uint8_t*>(d_out), s)) &&
+        ok(hipStreamSynchronize(s)))
+      ok(hipMemcpy(out, d_out, dst_bytes + 64, hipMemcpyDeviceToHost));
+  }
+  for (void* p : {d_so, d_dofs, d_items, d_out})
+    if (p) (void)hipFree(p);
+  if (h_src) (void)hipHostFree(h_src);
+  if (s) (void)hipStreamDestroy(s);
+  if (e != hipSuccess) {
+    tsg::SetError(std::string(who) + ": " + hipGetErrorString(e));
+    return -1;
+  }
+  return 0;
+}
+
+// FetchPlan and the FetchPack rounds of GpuEngine::IssueFetch on one stream, each round waited for and
+// read back whole: the staging buffer has 64 bytes more than a round may fill, and what a round leaves of
+// the 0xA5 it was filled with shows where the kernel stored.
+int tsg_debug_fetch_files_device(int device, const uint8_t* arena, uint64_t n_bytes, const uint64_t* offsets,
+                                 uint32_t n_files, const void* cands, uint64_t n_cands, uint32_t cand_cap,
+                                 const uint32_t* flags, uint64_t direct_bytes, uint64_t stage_bytes,
+                                 uint64_t copy_bytes, uint8_t* packed_out, uint64_t packed_cap, uint32_t* list_out,
+                                 uint64_t* lpoff_out, uint64_t counters[6]) {
+  const char* who = "tsg_debug_fetch_files_device";
+  auto refuse = [&](const char* why) {
+    tsg::SetError(std::string(who) + ": " + why);
+    return -2;
+  };
+  if (!offsets || !packed_out || !list_out || !lpoff_out || !counters || (n_bytes && !arena))
+    return refuse("NULL argument");
+  if (offsets[0] != 0) return refuse("offsets must start at 0");
+  for (uint32_t f = 0; f < n_files; f++)
+    if (offsets[f + 1] < offsets[f]) return refuse("offsets must ascend");
+  if (offsets[n_files] != n_bytes) return refuse("offsets must end at n_bytes");
+  if (flags && (cands || n_cands)) return refuse("candidate records or file flags, not both");
+  if (n_cands > 0xFFFFFFFFull) return refuse("more candidates than the device count holds");
+  const size_t held = size_t(std::min<uint64_t>(n_cands, cand_cap));
+  if (!flags && held && !cands) return refuse("candidate records missing");
+  if (copy_bytes % 16) return refuse("copy_bytes must be a multiple of 16");
+  stage_bytes = std::max<uint64_t>(stage_bytes / tsg::kFetchSeg, 1) * tsg::kFetchSeg;
+  const uint32_t count = uint32_t(n_cands);
+  const size_t stage_alloc = size_t(stage_bytes) + 64;
+  void *d_arena = nullptr, *d_off = nullptr, *d_cands = nullptr, *d_count = nullptr, *d_sc = nullptr, *d_ctr = nullptr,
+       *d_stage = nullptr;
+  hipStream_t s = nullptr;
+  int rc = 0;
+  hipError_t e = hipSetDevice(device);
+  auto ok = [&](hipError_t r) {
+    if (e == hipSuccess) e = r;
+    return e == hipSuccess;
+  };
+  tsg::FetchCounters ctr = {};
+  // the arena as the library's callers give it: n_bytes + 64 readable bytes and no more (0xEE: not file bytes)
+  if (ok(e) && ok(hipStreamCreate(&s)) && ok(hipMalloc(&d_arena, n_bytes + 64)) &&
+      ok(hipMalloc(&d_off, (size_t(n_files) + 1) * 8)) && ok(hipMalloc(&d_cands, (held + 1) * sizeof(tsg::Candidate))) &&
+      ok(hipMalloc(&d_count, 4)) && ok(hipMalloc(&d_sc, tsg::FetchScratchBytes(n_files))) &&
+      ok(hipMalloc(&d_ctr, sizeof ctr)) && ok(hipMalloc(&d_stage, stage_alloc)) &&
+      ok(hipMemset(d_arena, 0xEE, n_bytes + 64)) &&
+      (n_bytes == 0 || ok(hipMemcpy(d_arena, arena, n_bytes, hipMemcpyHostToDevice))) &&
+      ok(hipMemcpy(d_off, offsets, (size_t(n_files) + 1) * 8, hipMemcpyHostToDevice)) &&
+      (held == 0 || ok(hipMemcpy(d_cands, cands, held * sizeof(tsg::Candidate), hipMemcpyHostToDevice))) &&
+      ok(hipMemcpy(d_count, &count, 4, hipMemcpyHostToDevice)) &&
+      (!flags || n_files == 0 ||
+       ok(hipMemcpy(tsg::FetchFlags(d_sc, n_files), flags, size_t(n_files) * 4, hipMemcpyHostToDevice))) &&
+      ok(tsg::FetchPlan(flags ? nullptr : static_cast<const tsg::Candidate*>(d_cands),
+                        static_cast<const uint32_t*>(d_count), cand_cap, static_cast<const uint64_t*>(d_off), n_files,
+                        direct_bytes, d_sc, static_cast<tsg::FetchCounters*>(d_ctr), s)) &&
+      ok(hipMemcpyAsync(&ctr, d_ctr, sizeof ctr, hipMemcpyDeviceToHost, s)) && ok(hipStreamSynchronize(s))) {
+    const uint64_t copy = copy_bytes ? copy_bytes : ctr.packed_bytes;
+    uint64_t rounds = 0;
+    if (ctr.n_packed > n_files || copy > packed_cap) {
+      tsg::SetError(std::string(who) + (copy > packed_cap ? ": packed_cap is below the bytes to copy"
+                                                          : ": the plan packs more files than there are"));
+      rc = -3;
+    }
+    std::vector<uint8_t> round(rc == 0 ? stage_alloc : 0);
+    for (uint64_t w0 = 0; rc == 0 && w0 < copy && e == hipSuccess; w0 += stage_bytes, rounds++) {
+      const uint64_t w1 = std::min(w0 + stage_bytes, copy);
+      if (!(ok(hipMemsetAsync(d_stage, 0xA5, stage_alloc, s)) &&
+            ok(tsg::FetchPack(static_cast<const uint8_t*>(d_arena), static_cast<const uint64_t*>(d_off), n_files, d_sc,
+                              static_cast<const tsg::FetchCounters*>(d_ctr), w0, w1, static_cast<uint8_t*>(d_stage),
+                              s)) &&
+            ok(hipStreamSynchronize(s)) && ok(hipMemcpy(round.data(), d_stage, stage_alloc, hipMemcpyDeviceToHost))))
+        break;
+      std::memcpy(packed_out + w0, round.data(), size_t(w1 - w0));
+      for (size_t i = size_t(w1 - w0); i < stage_alloc; i++)
+        if (round[i] != 0xA5) {  // a store past the round's bytes
+          tsg::SetError(std::string(who) + ": round " + std::to_string(rounds) + " wrote staging byte " +
+                        std::to_string(i) + ", past its " + std::to_string(w1 - w0));
+          rc = -4;
+          break;
+        }
+    }
+    if (rc == 0 && e == hipSuccess && ctr.n_packed)
+      ok(hipMemcpy(list_out, tsg::FetchList(d_sc, n_files), size_t(ctr.n_packed) * 4, hipMemcpyDeviceToHost));
+    if (rc == 0 && e == hipSuccess)
+      ok(hipMemcpy(lpoff_out, tsg::FetchListOffsets(d_sc, n_files), (size_t(ctr.n_packed) + 1) * 8,
+                   hipMemcpyDeviceToHost));
+    counters[0] = ctr.packed_bytes;
+    counters[1] = ctr.n_packed;
+    counters[2] = ctr.n_direct;
+    counters[3] = ctr.n_files;
+    counters[4] = ctr.file_bytes;
+    counters[5] = rounds;
+  }
+  for (void* p : {d_arena, d_off, d_cands, d_count, d_sc, d_ctr, d_stage})
+    if (p) (void)hipFree(p);
+  if (s) (void)hipStreamDestroy(s);
+  if (e != hipSuccess) {
+    tsg::SetError(std::string(who) + ": " + hipGetErrorString(e));
+    return -1;
+  }
+  return rc;
 }
 
 int tsg_regex_match(const char* pattern, const uint8_t* text, uint64_t n) {

@@ -36,6 +36,11 @@ size_t FetchScratchBytes(uint32_t n_files);
 // The per-file flags of the scratch (n_files u32): FetchPlan's input when no
 // candidate list is given -- the caller fills them (nonzero: fetch the file).
 uint32_t* FetchFlags(void* scratch, uint32_t n_files);
+// What FetchPlan left in the scratch for FetchPack (device addresses; tests read
+// them back): the packed files' ids in file order (ctr->n_packed entries) and
+// their packed offsets (n_packed + 1: the last is packed_bytes).
+const uint32_t* FetchList(const void* scratch, uint32_t n_files);
+const uint64_t* FetchListOffsets(const void* scratch, uint32_t n_files);
 
 // Marks the files of the candidates cands[0 .. min(*cand_count, cand_cap)) that
 // the host will see (not kCandDrop) -- or, with cands == nullptr, takes the

@@ -199,6 +199,14 @@ uint32_t* FetchFlags(void* scratch, uint32_t n_files) {
   return reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(scratch) + LayoutOf(n_files).flag);
 }
 
+const uint32_t* FetchList(const void* scratch, uint32_t n_files) {
+  return reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(scratch) + LayoutOf(n_files).list);
+}
+
+const uint64_t* FetchListOffsets(const void* scratch, uint32_t n_files) {
+  return reinterpret_cast<const uint64_t*>(static_cast<const uint8_t*>(scratch) + LayoutOf(n_files).lpoff);
+}
+
 hipError_t FetchPlan(const Candidate* cands, const uint32_t* cand_count, uint32_t cand_cap, const uint64_t* off,
                      uint32_t n_files, uint64_t direct_bytes, void* scratch, FetchCounters* ctr, hipStream_t s) {
   const FetchLayout L = LayoutOf(n_files);

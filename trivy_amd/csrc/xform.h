@@ -51,9 +51,11 @@ hipError_t GatherFiles(const uint8_t* src, const uint64_t* xoff, const uint32_t*
 // wave per item of up to kGatherPiece bytes of one file (items: (file, piece),
 // built by the host); 16-B aligned destination stores (byte stores at a file's
 // two ragged ends), source words by aligned loads and a byte shift.  The reads
-// may touch up to 16 bytes before a file's data and 32 past its end, which a tar
-// holds (the 512-B header before, the 512-B block padding and the end-of-archive
-// blocks after).
+// may touch up to 30 bytes before a file's data and 31 past its end (the first
+// aligned destination block begins up to 15 bytes before the file's, its aligned
+// source block up to 15 more; likewise the block after the last one's source:
+// derived at capi_debug.cpp tsg_debug_gather_host), which a tar holds (the 512-B header before, the 512-B
+// block padding and the end-of-archive blocks after).
 constexpr uint32_t kGatherPiece = 16384;
 struct GatherItem {
   uint32_t file, piece;

@@ -182,9 +182,10 @@ int tsg_debug_scanner_engine(struct tsg_scanner* s, uint64_t out[4]);
 int tsg_debug_filter_orform(const tsg_compiled* c, uint32_t out[1024]);
 
 /* Where a scanner makes the findings of HBM-resident batches (tsg_batch.dev_arena):
- * mode 1 the GPU (trivy_amd/csrc/materialize.h), 0 the host, 2 (the default;
- * TSG_GPU_FINDINGS at scanner creation) the GPU while the exact host pass is
- * the bound (the last scan's outlasted 1.5x its GPU phase).  Returns the
+ * mode 0 the host (the default; TSG_GPU_FINDINGS at scanner creation sets
+ * another), 1 the GPU (trivy_amd/csrc/materialize.h), 2 the GPU while the exact
+ * host pass is the bound (the last scan's outlasted 1.5x its GPU phase).  A
+ * windows-mode device-only batch takes the GPU whatever the mode.  Returns the
  * previous mode, -1 for a scanner without a GPU engine.  (A/B and parity tests.) */
 int tsg_debug_scanner_gpu_findings(struct tsg_scanner* s, int mode);
 
@@ -459,6 +460,65 @@ int tsg_debug_tar_skip_match(const char* pattern, const uint8_t* fp, uint32_t le
 int tsg_debug_index_tar_files(struct tsg_analyzer* a, const void* file_recs, uint64_t n_recs, const uint8_t* blob,
                               uint64_t blob_bytes, const uint64_t* counts, const uint64_t* stop, uint64_t n_bytes,
                               uint64_t candidates_given, struct tsg_tar_index** out, struct tsg_device_tar_stats* st);
+
+/* ---- the findings kernels and the path filter ----
+ * Each is one synchronous call on HIP device `device`; the argument checks come
+ * before any HIP call (-2, text via tsg_last_error()); a HIP error is -1.
+ *
+ * mat_locate_kernel and mat_write_kernel (trivy_amd/csrc/materialize.hip) through
+ * the real FindingMaterializer (Begin, fill, Run, End).  arena holds n_bytes + 64
+ * bytes, uploaded as given into an allocation of exactly that size (the caller
+ * chooses the tail); offsets has n_files + 1 entries from 0 to n_bytes.
+ * mat_files, matches and spans are MatFile (24 B), MatMatch (40 B) and MatSpan
+ * (24 B) records as materialize.h lays them out; text_bound is the scanner's own
+ * (the sum of MatTextBound over the locations).  Refused (-2): a location outside
+ * its file, with e < s, with a_wlo > s, or (when not empty) covered by no span;
+ * spans of a file that are unsorted, touch, overlap, leave the file or lack the
+ * sentinel (s = e = INT64_MAX) as their last; m0 / s0 that are not the sums of
+ * the nm / ns of the file records before, a location whose fidx is not the record
+ * that holds it, records that leave locations or spans over.  MatFile.file may
+ * come in any order and repeat.
+ * Out: findings_out, n_match FindingOut records (40 B); pref_out, n_match + 1
+ * words (text offset << 32 | line index, exclusive, global to the call); up to
+ * lines_cap LineOut records (24 B) and up to text_cap text bytes; totals =
+ * {lines, text bytes}, set whenever the locate pass came back.  -3: a cap is
+ * below its total (findings and pref are written).  -5: Run's "line search and
+ * line count disagree" (the kernel's error word).  -6: the totals are past
+ * text_bound or 4 lines per location.  guard != 0 turns on the materializer's
+ * guard bytes (FindingMaterializer::set_guard): the three device output buffers
+ * are 0xA5 over their whole capacity before the first kernel, and a byte past
+ * the n_match findings, the lines or the text that is not 0xA5 after the write
+ * kernel is -4 (the text names the buffer and the offset). */
+int tsg_debug_materialize(int device, const uint8_t* arena, uint64_t n_bytes, const uint64_t* offsets, uint32_t n_files,
+                          const void* mat_files, uint32_t n_mat_files, const void* matches, uint32_t n_match,
+                          const void* spans, uint32_t n_span, int guard, void* findings_out, uint64_t* pref_out,
+                          void* lines_out, uint64_t lines_cap, uint8_t* text_out, uint64_t text_cap,
+                          uint64_t totals[2]);
+/* BuildPathTable / BuildSureTable (trivy_amd/csrc/pathfilter.h) on given literals, without a GPU.
+ * The prefilter's: literal i is lit_bytes[lit_off[i] .. lit_off[i + 1]) with rule id lit_rule[i].
+ * The exact ones: literal i has positions sure_off[i] .. sure_off[i + 1], position p accepting the
+ * two bytes sure_pairs[2 p], sure_pairs[2 p + 1] (equal for a case-sensitive one); sure_flags[i]:
+ * bit 0 begin (^), bit 1 end ($).  The raw PathTable and SureTable are written (sizes as for
+ * tsg_debug_tar_required_tables; zeroed when not built).  Returns bit 0: the path table was built,
+ * bit 1: the sure table; -1: an argument error or a buffer too small. */
+int tsg_debug_path_tables(const uint8_t* lit_bytes, const uint64_t* lit_off, const uint32_t* lit_rule, uint32_t n_lits,
+                          const uint8_t* sure_pairs, const uint64_t* sure_off, const uint8_t* sure_flags,
+                          uint32_t n_sure, void* path_table_out, uint64_t path_cap, void* sure_table_out,
+                          uint64_t sure_cap);
+/* path_filter_kernel (trivy_amd/csrc/pathfilter.hip) through one PathFilter built from the raw
+ * path_table and (unless NULL) sure_table: the batches run one after another through Submit /
+ * Finish / Release, so the slot, its counter parity and the last record count carry over from
+ * batch to batch.  Batch b holds paths batch_first[b] .. batch_first[b + 1]; path i is
+ * paths[off[i] .. off[i + 1]).  flags: bit 0 the paths go through Submit's host-packed route
+ * (else into a device allocation of exactly the batch's path bytes, offsets from 0), bit 1
+ * want_skip.  Out: batch b's PathHit records (16 B) at hits_out + batch_first[b] and their count
+ * in n_hits_out[b]; have_skip_out[b] = 1 when the batch had skip bytes (want_skip and a sure
+ * table), then copied after the `ready` event from Pending::d_skip to skip_out +
+ * batch_first[b]; the slot's skip bytes are 0xEE when allocated (PathFilter::set_skip_fill), so
+ * a byte the kernel leaves unwritten shows.  hits_out and skip_out hold one entry per path. */
+int tsg_debug_path_filter(int device, const void* path_table, const void* sure_table, const uint8_t* paths,
+                          const uint64_t* off, const uint32_t* batch_first, uint32_t n_batches, uint32_t flags,
+                          void* hits_out, uint32_t* n_hits_out, uint8_t* skip_out, uint8_t* have_skip_out);
 
 /* Thread-local text of the last error. */
 const char* tsg_last_error(void);

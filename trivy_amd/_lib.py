@@ -220,6 +220,128 @@ def fetch_files_device(arena: bytes, offsets, flags=None, cands=None, n_cands=No
     return r
 
 
+class HookStatus(RuntimeError):
+    """A debug hook came back with a status of its own (neither 0 nor the -2 of a refusal)."""
+
+    def __init__(self, rc, text):
+        RuntimeError.__init__(self, "rc %d: %s" % (rc, text))
+        self.rc = rc
+
+
+def materialize(arena: bytes, offsets, files, matches, spans, guard=True, lines_cap=None, text_cap=None, device=0):
+    """tsg_debug_materialize.  arena: the n_bytes + 64 bytes to upload (offsets end at n_bytes); files, matches,
+    spans: the raw MatFile / MatMatch / MatSpan records (bytes, or numpy arrays of 24 / 40 / 24-B items).
+    -> dict: findings (40-B records), pref (u64 list), lines (24-B records), text, n_lines, n_text, all bytes
+    but pref.  HookRefused for -2, HookStatus (its rc: -3 a cap too small, -4 a guard byte, -5 the kernel's
+    own check, -6 totals past their bounds) otherwise."""
+    L = lib()
+    c = ctypes
+    n_files = len(offsets) - 1
+    n_bytes = len(arena) - 64
+    fb, mb, sb = (x if isinstance(x, bytes) else x.tobytes() for x in (files, matches, spans))
+    if n_bytes < 0 or len(fb) % 24 or len(mb) % 40 or len(sb) % 24:
+        raise ValueError("materialize: an arena with its 64-B tail, records of 24 / 40 / 24 bytes")
+    nf, nm, ns = len(fb) // 24, len(mb) // 40, len(sb) // 24
+    lines_cap = 4 * nm if lines_cap is None else int(lines_cap)
+    if text_cap is None:  # the scanner's own bound
+        import numpy as np
+        m = np.frombuffer(mb, dtype=np.int64).reshape(-1, 5)
+        text_cap = int((np.maximum(100, m[:, 2] - m[:, 1] + 50) + 400).sum()) if nm else 0
+    ab = c.create_string_buffer(bytes(arena), len(arena))
+    fo = c.create_string_buffer(max(1, 40 * nm))
+    pref = (c.c_uint64 * (nm + 1))()
+    lo = c.create_string_buffer(max(1, 24 * lines_cap))
+    tx = c.create_string_buffer(max(1, text_cap))
+    tot = (c.c_uint64 * 2)()
+    L.tsg_debug_materialize.restype = c.c_int
+    L.tsg_debug_materialize.argtypes = [c.c_int, c.c_void_p, c.c_uint64, c.c_void_p, c.c_uint32, c.c_char_p, c.c_uint32,
+                                        c.c_char_p, c.c_uint32, c.c_char_p, c.c_uint32, c.c_int, c.c_void_p, c.c_void_p,
+                                        c.c_void_p, c.c_uint64, c.c_void_p, c.c_uint64, c.c_void_p]
+    rc = L.tsg_debug_materialize(int(device), ab, n_bytes, _u64s(offsets), n_files, fb, nf, mb, nm, sb, ns,
+                                 1 if guard else 0, fo, pref, lo, lines_cap, tx, text_cap, tot)
+    if rc == -2:
+        raise HookRefused(last_error(L))
+    n_lines, n_text = int(tot[0]), int(tot[1])
+    if rc != 0:
+        e = HookStatus(rc, last_error(L))
+        e.n_lines, e.n_text = n_lines, n_text
+        raise e
+    return dict(findings=fo.raw[:40 * nm], pref=list(pref), lines=lo.raw[:24 * n_lines], text=tx.raw[:n_text],
+                n_lines=n_lines, n_text=n_text)
+
+
+PATH_TABLE_BYTES = 8520  # sizeof(PathTable), csrc/pathfilter.h
+SURE_TABLE_BYTES = 8328  # sizeof(SureTable)
+PATH_NON_ASCII = 0x80000000  # kPathNonAscii
+
+
+def path_tables(lits, sure_lits):
+    """tsg_debug_path_tables (no GPU).  lits: [(lowercased literal bytes, rule id)]; sure_lits: [(positions,
+    begin, end)] with positions a list of (byte, byte) pairs.  -> (raw PathTable or None, raw SureTable or
+    None): None where the builder refused."""
+    L = lib()
+    c = ctypes
+    lb = b"".join(bytes(x) for x, _ in lits)
+    lo, at = [0], 0
+    for x, _ in lits:
+        at += len(x)
+        lo.append(at)
+    rules = (c.c_uint32 * max(1, len(lits)))(*[int(r) for _, r in lits])
+    pairs = bytes(b for pos, _, _ in sure_lits for pr in pos for b in pr)
+    so, at = [0], 0
+    for pos, _, _ in sure_lits:
+        at += len(pos)
+        so.append(at)
+    fl = bytes((1 if b else 0) | (2 if e else 0) for _, b, e in sure_lits)
+    pt, st = c.create_string_buffer(PATH_TABLE_BYTES), c.create_string_buffer(SURE_TABLE_BYTES)
+    L.tsg_debug_path_tables.restype = c.c_int
+    L.tsg_debug_path_tables.argtypes = [c.c_char_p, c.c_void_p, c.c_void_p, c.c_uint32, c.c_char_p, c.c_void_p,
+                                        c.c_char_p, c.c_uint32, c.c_void_p, c.c_uint64, c.c_void_p, c.c_uint64]
+    rc = L.tsg_debug_path_tables(lb or b"\0", _u64s(lo), rules, len(lits), pairs or b"\0", _u64s(so), fl or b"\0",
+                                 len(sure_lits), pt, PATH_TABLE_BYTES, st, SURE_TABLE_BYTES)
+    if rc < 0:
+        raise ValueError(last_error(L))
+    return (pt.raw if rc & 1 else None, st.raw if rc & 2 else None)
+
+
+def path_filter(path_table: bytes, sure_table, batches, host_packed=False, want_skip=True, device=0):
+    """tsg_debug_path_filter: `batches` (lists of path bytes) one after another on one PathFilter.  -> one
+    (hits, skip) per batch: hits a list of (file, pad, rules) records as the filter returned them, skip the
+    batch's skip bytes or None when it had none."""
+    L = lib()
+    c = ctypes
+    paths = [p for b in batches for p in b]
+    first, at = [0], 0
+    for b in batches:
+        at += len(b)
+        first.append(at)
+    blob = b"".join(paths)
+    off, at = [0], 0
+    for p in paths:
+        at += len(p)
+        off.append(at)
+    n = len(paths)
+    import numpy as np
+    off = np.array(off, dtype=np.uint64)
+    hits = np.zeros((max(1, n), 2), dtype=np.uint64)
+    skip = np.full(max(1, n), 0x77, dtype=np.uint8)
+    n_hits = (c.c_uint32 * max(1, len(batches)))()
+    have = (c.c_uint8 * max(1, len(batches)))()
+    bf = (c.c_uint32 * len(first))(*first)
+    L.tsg_debug_path_filter.restype = c.c_int
+    L.tsg_debug_path_filter.argtypes = [c.c_int, c.c_char_p, c.c_char_p, c.c_char_p, c.c_void_p, c.c_void_p, c.c_uint32,
+                                        c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+    _hook_rc(L, L.tsg_debug_path_filter(int(device), path_table, sure_table, blob or b"\0", off.ctypes.data, bf,
+                                        len(batches), (1 if host_packed else 0) | (2 if want_skip else 0),
+                                        hits.ctypes.data, n_hits, skip.ctypes.data, have))
+    out = []
+    for b in range(len(batches)):
+        h = hits[first[b]:first[b] + int(n_hits[b])]
+        recs = [(int(x) & 0xFFFFFFFF, int(x) >> 32, int(r)) for x, r in h]
+        out.append((recs, skip[first[b]:first[b + 1]].tobytes() if have[b] else None))
+    return out
+
+
 def go_bytes_to_lower(b: bytes) -> bytes:
     out = ctypes.create_string_buffer(len(b) * 3 + 4)
     n = lib().tsg_go_bytes_to_lower(b, len(b), out, len(out))

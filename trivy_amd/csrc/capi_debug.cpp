@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstdint>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -18,7 +19,9 @@
 #include "filter.h"
 #include "goregex.h"
 #include "k1_orform.h"
+#include "materialize.h"
 #include "parallel.h"
+#include "pathfilter.h"
 #include "xform.h"
 
 namespace tsg {
@@ -850,6 +853,251 @@ int tsg_debug_sure_allow(const char* const* patterns, uint32_t n_patterns, const
   if (has_form && n_patterns) std::memcpy(has_form, form.data(), n_patterns);
   for (uint32_t i = 0; i < n_paths; i++) sure[i] = tsg::SureAllowHost(t, paths + off[i], off[i + 1] - off[i]) ? 1 : 0;
   return 0;
+}
+
+// ---- the findings kernels and the path filter ----
+
+int tsg_debug_materialize(int device, const uint8_t* arena, uint64_t n_bytes, const uint64_t* offsets, uint32_t n_files,
+                          const void* mat_files, uint32_t n_mat_files, const void* matches, uint32_t n_match,
+                          const void* spans, uint32_t n_span, int guard, void* findings_out, uint64_t* pref_out,
+                          void* lines_out, uint64_t lines_cap, uint8_t* text_out, uint64_t text_cap,
+                          uint64_t totals[2]) {
+  const char* who = "tsg_debug_materialize";
+  auto refuse = [&](const std::string& why) {
+    tsg::SetError(std::string(who) + ": " + why);
+    return -2;
+  };
+  if (!arena || !offsets || !totals || (n_mat_files && !mat_files) || (n_match && (!matches || !findings_out)) ||
+      !pref_out || (n_span && !spans) || (lines_cap && !lines_out) || (text_cap && !text_out))
+    return refuse("NULL argument");
+  totals[0] = totals[1] = 0;
+  if (offsets[0] != 0) return refuse("offsets must start at 0");
+  for (uint32_t f = 0; f < n_files; f++)
+    if (offsets[f + 1] < offsets[f]) return refuse("offsets must ascend");
+  if (offsets[n_files] != n_bytes) return refuse("offsets must end at n_bytes");
+  const tsg::MatFile* F = static_cast<const tsg::MatFile*>(mat_files);
+  const tsg::MatMatch* M = static_cast<const tsg::MatMatch*>(matches);
+  const tsg::MatSpan* Sp = static_cast<const tsg::MatSpan*>(spans);
+  // the records as the scanner builds them: each file's locations and spans follow those of the file before
+  uint64_t m_at = 0, s_at = 0, text_bound = 0;
+  for (uint32_t i = 0; i < n_mat_files; i++) {
+    const std::string fi = "file record " + std::to_string(i);
+    if (F[i].file >= n_files) return refuse(fi + ": no such file");
+    if (F[i].m0 != m_at) return refuse(fi + ": m0 contradicts the locations of the records before it");
+    if (F[i].s0 != s_at) return refuse(fi + ": s0 contradicts the spans of the records before it");
+    m_at += F[i].nm;
+    s_at += F[i].ns;
+    if (m_at > n_match || s_at > n_span) return refuse(fi + ": its locations or spans leave the arrays");
+    const int64_t len = int64_t(offsets[F[i].file + 1] - offsets[F[i].file]);
+    const tsg::MatSpan* sp = Sp + F[i].s0;
+    if (F[i].ns == 0 || sp[F[i].ns - 1].s != INT64_MAX || sp[F[i].ns - 1].e != INT64_MAX)
+      return refuse(fi + ": its spans lack the sentinel");
+    for (uint32_t k = 0; k + 1 < F[i].ns; k++) {
+      if (sp[k].s < 0 || sp[k].e <= sp[k].s || sp[k].e > len) return refuse(fi + ": span " + std::to_string(k) + " is empty or outside its file");
+      if (k && sp[k].s <= sp[k - 1].e)
+        return refuse(fi + ": span " + std::to_string(k) + " is unsorted, touches or overlaps the one before");
+    }
+    for (uint32_t q = 0; q < F[i].nm; q++) {
+      const tsg::MatMatch& m = M[F[i].m0 + q];
+      const std::string mi = "location " + std::to_string(F[i].m0 + q);
+      if (m.fidx != i) return refuse(mi + ": fidx contradicts the file record that holds it");
+      if (m.e < m.s) return refuse(mi + ": e < s");
+      if (m.s < 0 || m.e > len) return refuse(mi + ": outside its file");
+      if (m.a_wlo < 0 || m.a_wlo > m.s || m.a_nl < 0) return refuse(mi + ": a_wlo > s (or a negative anchor)");
+      if (m.e > m.s) {  // EndLine = StartLine holds because a location is censored whole
+        bool covered = false;
+        for (uint32_t k = 0; k + 1 < F[i].ns && !covered; k++) covered = sp[k].s <= m.s && m.e <= sp[k].e;
+        if (!covered) return refuse(mi + ": no span covers it");
+      }
+      text_bound += tsg::MatTextBound(m.s, m.e);
+    }
+  }
+  if (m_at != n_match || s_at != n_span) return refuse("locations or spans that no file record holds");
+  void *d_arena = nullptr, *d_off = nullptr;
+  hipError_t e = hipSetDevice(device);
+  auto ok = [&](hipError_t r) {
+    if (e == hipSuccess) e = r;
+    return e == hipSuccess;
+  };
+  int rc = 0;
+  std::string err;
+  // the arena as the caller gives it, tail included, in an allocation of exactly that size
+  if (ok(e) && ok(hipMalloc(&d_arena, n_bytes + 64)) && ok(hipMalloc(&d_off, (size_t(n_files) + 1) * 8)) &&
+      ok(hipMemcpy(d_arena, arena, n_bytes + 64, hipMemcpyHostToDevice)) &&
+      ok(hipMemcpy(d_off, offsets, (size_t(n_files) + 1) * 8, hipMemcpyHostToDevice))) {
+    std::unique_ptr<tsg::FindingMaterializer> mat(new tsg::FindingMaterializer(device));
+    mat->set_guard(guard != 0);
+    tsg::FindingMaterializer::Job* job = mat->ok() ? mat->Begin(n_mat_files, n_match, n_span, text_bound, &err) : nullptr;
+    if (!job) {
+      if (err.empty()) err = mat->error();
+      rc = -1;
+    } else {
+      if (n_mat_files) std::memcpy(mat->files(job), F, size_t(n_mat_files) * sizeof(tsg::MatFile));
+      if (n_match) std::memcpy(mat->matches(job), M, size_t(n_match) * sizeof(tsg::MatMatch));
+      if (n_span) std::memcpy(mat->spans(job), Sp, size_t(n_span) * sizeof(tsg::MatSpan));
+      const bool ran = mat->Run(job, static_cast<const uint8_t*>(d_arena), static_cast<const uint64_t*>(d_off), &err);
+      const uint64_t tot = mat->totals(job);
+      totals[0] = uint32_t(tot);
+      totals[1] = tot >> 32;
+      if (!ran) {
+        switch (mat->fail(job)) {
+          case tsg::FindingMaterializer::kSelfCheck: rc = -5; break;
+          case tsg::FindingMaterializer::kGuard: rc = -4; break;
+          case tsg::FindingMaterializer::kBounds: rc = -6; break;
+          default: rc = -1;
+        }
+      } else if (n_match) {
+        std::memcpy(findings_out, mat->findings(job), size_t(n_match) * sizeof(tsg::FindingOut));
+        std::memcpy(pref_out, mat->pref(job), (size_t(n_match) + 1) * 8);
+        if (totals[0] > lines_cap || totals[1] > text_cap) {
+          err = "lines_cap or text_cap is below the totals";
+          rc = -3;
+        } else {
+          if (totals[0]) std::memcpy(lines_out, mat->lines(job), size_t(totals[0]) * sizeof(tsg::LineOut));
+          if (totals[1]) std::memcpy(text_out, mat->text(job), size_t(totals[1]));
+        }
+      } else {
+        pref_out[0] = 0;
+      }
+      mat->End(job);
+    }
+  }
+  for (void* p : {d_arena, d_off})
+    if (p) (void)hipFree(p);
+  if (e != hipSuccess) {
+    tsg::SetError(std::string(who) + ": " + hipGetErrorString(e));
+    return -1;
+  }
+  if (rc != 0) tsg::SetError(std::string(who) + ": " + err);
+  return rc;
+}
+
+int tsg_debug_path_tables(const uint8_t* lit_bytes, const uint64_t* lit_off, const uint32_t* lit_rule, uint32_t n_lits,
+                          const uint8_t* sure_pairs, const uint64_t* sure_off, const uint8_t* sure_flags,
+                          uint32_t n_sure, void* path_table_out, uint64_t path_cap, void* sure_table_out,
+                          uint64_t sure_cap) {
+  if ((n_lits && (!lit_bytes || !lit_off || !lit_rule)) || (n_sure && (!sure_pairs || !sure_off || !sure_flags)) ||
+      !path_table_out || !sure_table_out || path_cap < sizeof(tsg::PathTable) || sure_cap < sizeof(tsg::SureTable)) {
+    tsg::SetError("tsg_debug_path_tables: NULL argument or a buffer too small");
+    return -1;
+  }
+  std::vector<std::pair<std::string, uint32_t>> lits;
+  for (uint32_t i = 0; i < n_lits; i++) {
+    if (lit_off[i + 1] < lit_off[i]) {
+      tsg::SetError("tsg_debug_path_tables: literal offsets must ascend");
+      return -1;
+    }
+    lits.emplace_back(std::string(reinterpret_cast<const char*>(lit_bytes) + lit_off[i], size_t(lit_off[i + 1] - lit_off[i])),
+                      lit_rule[i]);
+  }
+  std::vector<tsg::SureLit> sure;
+  for (uint32_t i = 0; i < n_sure; i++) {
+    if (sure_off[i + 1] < sure_off[i]) {
+      tsg::SetError("tsg_debug_path_tables: literal offsets must ascend");
+      return -1;
+    }
+    tsg::SureLit l;
+    for (uint64_t p = sure_off[i]; p < sure_off[i + 1]; p++) l.pos.emplace_back(sure_pairs[2 * p], sure_pairs[2 * p + 1]);
+    l.begin = (sure_flags[i] & 1) != 0;
+    l.end = (sure_flags[i] & 2) != 0;
+    sure.push_back(std::move(l));
+  }
+  tsg::PathTable pt;
+  tsg::SureTable st;
+  int have = 0;
+  if (tsg::BuildPathTable(lits, &pt)) have |= 1;
+  else std::memset(&pt, 0, sizeof pt);
+  if (tsg::BuildSureTable(sure, &st)) have |= 2;
+  std::memcpy(path_table_out, &pt, sizeof pt);
+  std::memcpy(sure_table_out, &st, sizeof st);
+  return have;
+}
+
+int tsg_debug_path_filter(int device, const void* path_table, const void* sure_table, const uint8_t* paths,
+                          const uint64_t* off, const uint32_t* batch_first, uint32_t n_batches, uint32_t flags,
+                          void* hits_out, uint32_t* n_hits_out, uint8_t* skip_out, uint8_t* have_skip_out) {
+  const char* who = "tsg_debug_path_filter";
+  auto refuse = [&](const char* why) {
+    tsg::SetError(std::string(who) + ": " + why);
+    return -2;
+  };
+  if (!path_table || !off || !batch_first || !hits_out || !n_hits_out || !skip_out || !have_skip_out || (flags & ~3u))
+    return refuse("NULL argument or an unknown flag");
+  for (uint32_t b = 0; b < n_batches; b++)
+    if (batch_first[b + 1] < batch_first[b]) return refuse("batch_first must ascend");
+  const uint32_t n_paths = batch_first[n_batches];
+  for (uint32_t i = batch_first[0]; i < n_paths; i++)
+    if (off[i + 1] < off[i]) return refuse("off must ascend");
+  if (n_paths > batch_first[0] && off[n_paths] > off[batch_first[0]] && !paths) return refuse("paths missing");
+  tsg::PathTable pt;
+  std::memcpy(&pt, path_table, sizeof pt);
+  if (pt.words < 1 || pt.words > 4) return refuse("the path table's words must be 1..4");
+  for (uint32_t i = 0; i < 256; i++)
+    if (pt.rule_of[i] >= 64) return refuse("the path table names a rule past 63");
+  tsg::SureTable st;
+  if (sure_table) {
+    std::memcpy(&st, sure_table, sizeof st);
+    if (st.words < 1 || st.words > 4) return refuse("the sure table's words must be 1..4");
+  }
+  const bool host_packed = (flags & 1u) != 0, want_skip = (flags & 2u) != 0;
+  hipError_t e = hipSetDevice(device);
+  auto ok = [&](hipError_t r) {
+    if (e == hipSuccess) e = r;
+    return e == hipSuccess;
+  };
+  std::string err;
+  int rc = 0;
+  if (ok(e)) {
+    // one filter for the whole sequence: the slot, its counter parity and the last count carry over
+    std::unique_ptr<tsg::PathFilter> pf(new tsg::PathFilter(device, pt));
+    if (sure_table) pf->SetSureTable(st);
+    pf->set_skip_fill(true);
+    if (!pf->ok() || (sure_table && !pf->has_sure())) {
+      err = pf->ok() ? "the sure table did not reach the device" : pf->error();
+      rc = -1;
+    }
+    std::vector<tsg::PathHit> hits;
+    std::vector<uint64_t> rel;
+    for (uint32_t b = 0; rc == 0 && e == hipSuccess && b < n_batches; b++) {
+      const uint32_t first = batch_first[b], n = batch_first[b + 1] - first;
+      const uint64_t p0 = off[first], nb = off[first + n] - p0;
+      void *d_paths = nullptr, *d_off = nullptr;
+      tsg::PathFilter::Pending p;
+      bool done = false;
+      if (host_packed) {
+        done = pf->Submit(nullptr, nullptr, paths, off + first, n, want_skip, &p, &err);
+      } else {
+        // the paths in an allocation of exactly their bytes, the offsets from 0
+        rel.resize(size_t(n) + 1);
+        for (uint32_t i = 0; i <= n; i++) rel[i] = off[first + i] - p0;
+        if ((nb == 0 || (ok(hipMalloc(&d_paths, nb)) && ok(hipMemcpy(d_paths, paths + p0, nb, hipMemcpyHostToDevice)))) &&
+            ok(hipMalloc(&d_off, rel.size() * 8)) && ok(hipMemcpy(d_off, rel.data(), rel.size() * 8, hipMemcpyHostToDevice)))
+          done = pf->Submit(static_cast<const uint8_t*>(d_paths), static_cast<const uint64_t*>(d_off), nullptr, nullptr, n,
+                            want_skip, &p, &err);
+      }
+      have_skip_out[b] = 0;
+      if (done && p.d_skip) {  // as the scan's stream does: behind `ready`
+        if (ok(hipEventSynchronize(p.ready)) && ok(hipMemcpy(skip_out + first, p.d_skip, n, hipMemcpyDeviceToHost)))
+          have_skip_out[b] = 1;
+      }
+      if (done && e == hipSuccess) done = pf->Finish(&p, &hits, &err);
+      pf->Release(&p);
+      if (e == hipSuccess && !done) rc = -1;
+      if (rc == 0 && e == hipSuccess) {
+        n_hits_out[b] = uint32_t(hits.size());
+        if (!hits.empty())  // (Finish refuses a count above n)
+          std::memcpy(static_cast<tsg::PathHit*>(hits_out) + first, hits.data(), hits.size() * sizeof(tsg::PathHit));
+      }
+      for (void* q : {d_paths, d_off})
+        if (q) (void)hipFree(q);
+    }
+  }
+  if (e != hipSuccess) {
+    tsg::SetError(std::string(who) + ": " + hipGetErrorString(e));
+    return -1;
+  }
+  if (rc != 0) tsg::SetError(std::string(who) + ": " + err);
+  return rc;
 }
 
 int tsg_debug_result_skip(const struct tsg_result* r, uint64_t out[6]) {

@@ -75,6 +75,14 @@ struct MatSpan {     // a merged censor span [s, e)
 
 static_assert(sizeof(MatFile) == 24 && sizeof(MatMatch) == 40 && sizeof(MatSpan) == 24, "upload records");
 
+// The text bytes location [s, e) can take (Begin's text_bound is the sum over a
+// call's locations): the match text is a line of at most 100 B or the cut
+// [s - 30, e + 20), and each of the up to three other lines gives at most 100 B.
+inline uint64_t MatTextBound(int64_t s, int64_t e) {
+  const int64_t m = e - s + 50;
+  return uint64_t(m > 100 ? m : 100) + 400;
+}
+
 class FindingMaterializer {
  public:
   explicit FindingMaterializer(int device);
@@ -87,7 +95,7 @@ class FindingMaterializer {
   // Run uploads, runs the kernels over the resident arena and reads the
   // records back (blocking, the thread sleeps); the outputs stay valid until
   // End.  text_bound: an upper bound of the text bytes (sum over locations of
-  // max(100, e - s + 50) + 400).
+  // MatTextBound).
   struct Job;
   Job* Begin(uint32_t n_files, uint32_t n_match, uint32_t n_span, uint64_t text_bound, std::string* err);
   MatFile* files(Job* j);
@@ -103,6 +111,18 @@ class FindingMaterializer {
   const uint64_t* pref(Job* j) const;
   void End(Job* j);
 
+  // Why the last Run of a job failed (tests tell the causes apart by it).
+  enum Fail { kNone = 0, kHip, kSelfCheck, kBounds, kGuard };
+  Fail fail(Job* j) const;
+  // The totals of the last Run (text bytes << 32 | lines), set once the locate pass is back.
+  uint64_t totals(Job* j) const;
+  // Test-only guard bytes, off by default (no work when off).  On: Run fills the
+  // three device output buffers with 0xA5 over their whole capacity before the
+  // first kernel, and after the write kernel every byte past the nm findings,
+  // the n_lines records and the n_text bytes must still be 0xA5, else Run fails
+  // (kGuard; the text names the buffer and the offset).
+  void set_guard(bool on) { guard_ = on; }
+
  private:
   static constexpr int kSlots = 6;  // (a depth-6 pipeline's exact passes at once)
   struct Slot;
@@ -110,6 +130,7 @@ class FindingMaterializer {
   std::mutex mu_;
   std::condition_variable cv_;
   int device_ = 0;
+  bool guard_ = false;
   std::string err_;
 };
 

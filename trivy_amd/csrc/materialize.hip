@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <thread>
+#include <vector>
 
 namespace tsg {
 
@@ -331,6 +332,8 @@ struct FindingMaterializer::Slot {
   size_t h_pref_cap = 0;
   uint64_t* h_tot = nullptr;  // [0] totals, [1] error word
   uint64_t text_bound = 0;
+  uint64_t totals = 0;        // of the last Run
+  FindingMaterializer::Fail why = FindingMaterializer::kNone;
 };
 
 struct FindingMaterializer::Job {
@@ -420,6 +423,8 @@ FindingMaterializer::Job* FindingMaterializer::Begin(uint32_t n_files, uint32_t 
   S->nm = n_match;
   S->ns = n_span;
   S->text_bound = text_bound;
+  S->totals = 0;
+  S->why = kNone;
   S->off_match = Up(size_t(n_files) * sizeof(MatFile));
   S->off_span = S->off_match + Up(size_t(n_match) * sizeof(MatMatch));
   const size_t up = S->off_span + Up(size_t(n_span) * sizeof(MatSpan));
@@ -440,6 +445,8 @@ const FindingOut* FindingMaterializer::findings(Job* j) const { return j->s->h_f
 const LineOut* FindingMaterializer::lines(Job* j) const { return j->s->h_lines; }
 const char* FindingMaterializer::text(Job* j) const { return j->s->h_text; }
 const uint64_t* FindingMaterializer::pref(Job* j) const { return j->s->h_pref; }
+FindingMaterializer::Fail FindingMaterializer::fail(Job* j) const { return j->s->why; }
+uint64_t FindingMaterializer::totals(Job* j) const { return j->s->totals; }
 
 void FindingMaterializer::End(Job* j) {
   {
@@ -456,6 +463,7 @@ bool FindingMaterializer::Run(Job* j, const uint8_t* d_arena, const uint64_t* d_
   if (nm == 0) return true;
   auto fail = [&](const char* what, hipError_t e) {
     *err = std::string("FindingMaterializer: ") + what + ": " + hipGetErrorString(e);
+    S.why = kHip;
     return false;
   };
   // sleep-poll (as GpuEngine::WaitEvent): a spinning wait takes a core from the host pool
@@ -491,6 +499,10 @@ bool FindingMaterializer::Run(Job* j, const uint8_t* d_arena, const uint64_t* d_
   const MatMatch* mm = reinterpret_cast<const MatMatch*>(S.d_up + S.off_match);
   const MatSpan* sp = reinterpret_cast<const MatSpan*>(S.d_up + S.off_span);
   const uint32_t grid = uint32_t(std::min<uint64_t>((uint64_t(nm) + kMatWaves - 1) / kMatWaves, 16384));
+  if (guard_ && ((e = hipMemsetAsync(S.d_find, 0xA5, S.find_cap, S.stream)) != hipSuccess ||
+                 (e = hipMemsetAsync(S.d_lines, 0xA5, S.lines_cap, S.stream)) != hipSuccess ||
+                 (e = hipMemsetAsync(S.d_text, 0xA5, S.text_cap, S.stream)) != hipSuccess))
+    return fail("guard fill", e);
   // the upload, the locate pass, the scan; the totals and the error word back
   if ((e = hipMemcpyAsync(S.d_up, S.h_up, up, hipMemcpyHostToDevice, S.stream)) != hipSuccess ||
       (e = hipMemsetAsync(derr, 0, 4, S.stream)) != hipSuccess)
@@ -506,12 +518,15 @@ bool FindingMaterializer::Run(Job* j, const uint8_t* d_arena, const uint64_t* d_
     return fail("totals", e);
   const uint64_t tot = S.h_tot[0];
   const uint64_t n_text = tot >> 32, n_lines = uint32_t(tot);
+  S.totals = tot;
   if (uint32_t(S.h_tot[1]) != 0) {
     *err = "FindingMaterializer: line search and line count disagree (mat_locate_kernel)";
+    S.why = kSelfCheck;
     return false;
   }
   if (n_text > S.text_bound || n_lines > uint64_t(nm) * 4) {
     *err = "FindingMaterializer: text / line totals past their bounds";
+    S.why = kBounds;
     return false;
   }
   if ((e = GrowHost(&S.h_lines, &S.h_lines_cap, size_t(n_lines) * sizeof(LineOut))) != hipSuccess ||
@@ -529,6 +544,31 @@ bool FindingMaterializer::Run(Job* j, const uint8_t* d_arena, const uint64_t* d_
                      hipSuccess) ||
       (e = wait()) != hipSuccess)
     return fail("read-back", e);
+  if (guard_) {  // what the write kernel left of the fill past each buffer's records
+    struct {
+      const char* name;
+      const void* d;
+      size_t used, cap;
+    } const bufs[3] = {{"findings", S.d_find, size_t(nm) * sizeof(FindingOut), S.find_cap},
+                       {"lines", S.d_lines, size_t(n_lines) * sizeof(LineOut), S.lines_cap},
+                       {"text", S.d_text, size_t(n_text), S.text_cap}};
+    std::vector<uint8_t> back;
+    for (const auto& b : bufs) {
+      back.resize(b.cap - b.used);
+      if (back.empty()) continue;
+      if ((e = hipMemcpyAsync(back.data(), static_cast<const uint8_t*>(b.d) + b.used, back.size(),
+                              hipMemcpyDeviceToHost, S.stream)) != hipSuccess ||
+          (e = wait()) != hipSuccess)
+        return fail("guard read-back", e);
+      for (size_t i = 0; i < back.size(); i++)
+        if (back[i] != 0xA5) {
+          *err = std::string("FindingMaterializer: guard: the ") + b.name + " buffer was written at byte " +
+                 std::to_string(b.used + i) + ", past its " + std::to_string(b.used);
+          S.why = kGuard;
+          return false;
+        }
+    }
+  }
   return true;
 }
 

@@ -113,6 +113,9 @@ class PathFilter {
   };
   void SetSureTable(const SureTable& t);  // before the first Submit; a table with words = 0 is ignored
   bool has_sure() const { return d_sure_ != nullptr; }
+  // Test-only, off by default: a slot's skip bytes are filled with 0xEE when they are
+  // allocated, so a byte the kernel leaves unwritten shows (tsg_debug_path_filter).
+  void set_skip_fill(bool on) { skip_fill_ = on; }
   // The two tables in HBM, for kernels outside this class (tarrequired.hip); d_sure() is NULL without one.
   const PathTable* d_table() const { return d_table_; }
   const SureTable* d_sure() const { return d_sure_; }
@@ -155,6 +158,7 @@ class PathFilter {
   Slot slots_[kSlots];
   std::atomic<uint32_t> last_k_{0};  // records of the last call: one read-back when the count repeats
   int device_ = 0;
+  bool skip_fill_ = false;
   std::string err_;
   PathTable* d_table_ = nullptr;
   SureTable* d_sure_ = nullptr;

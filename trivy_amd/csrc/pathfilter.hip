@@ -274,6 +274,8 @@ bool PathFilter::Submit(const uint8_t* d_paths, const uint64_t* d_off, const uin
     S->skip_cap = 0;
     const size_t cap = size_t(n) + size_t(n) / 4 + 256;
     if ((e = hipMalloc(reinterpret_cast<void**>(&S->d_skip), cap)) != hipSuccess) return fail("hipMalloc (skip)", e);
+    if (skip_fill_ && (e = hipMemsetAsync(S->d_skip, 0xEE, cap, S->stream)) != hipSuccess)
+      return fail("hipMemsetAsync (skip)", e);
     S->skip_cap = cap;
   }
   if (h_paths) {  // host-packed paths: offsets (rebased to 0) and bytes via pinned staging to HBM

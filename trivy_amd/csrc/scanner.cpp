@@ -1598,7 +1598,7 @@ bool SecretScanner::GpuFindingsInput(const uint8_t* content, const Candidate* c,
       a_nl = it->second;
     }
     out->gm.push_back({mt.first, 0, st, en, a_wlo, a_nl});
-    tb += uint64_t(std::max<int64_t>(100, en - st + 50)) + 400;  // match text + <= 4 lines of <= 100 B
+    tb += MatTextBound(st, en);
   }
   out->text_bound = tb;
   out->gpu = true;
